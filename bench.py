@@ -9,14 +9,21 @@ HBM.  Multi-GPU is weak scaling: every rank owns one config-2-sized shard of a c
 N x 1e5 documents (contiguous "docN" strcmp ranges; idf uses the global N).
 
     python bench.py [--gpus N --steps K --warmup W]      (N > 1: one process, N GPUs, tfidf_group)
+    python bench.py --full ...                           (the headline line plus everything below)
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...   (one process per GPU)
 
-Rank 0 prints one JSON line.  `roofline` is priced on the dominant kernel (K1
-tokenize+count), algorithmic bytes per launch = C + 12*P, divided by K1's
+Rank 0 prints one JSON line.  A plain run sets up, warms up, times the K steps, writes
+`--dump-outputs DIR` if asked and prints the line; whatever takes runs of its own (the
+per-stage breakdown, the output-emission measurement, the HBM peak probe, the CPU baseline,
+the c3 strong follow-up of a multi-GPU line) is measured only with `--full`, and its fields
+are null without it.  `--dump-outputs DIR` writes the arrays a caller of the timed path
+receives from its last timed step (tfidf_fetch) as DIR/<name>.npy (float64; a fixed, seeded
+sample of the arrays that are larger than the size limit).
+`roofline` is priced on the dominant kernel (K1 tokenize+count), algorithmic bytes per launch = C + 12*P, divided by K1's
 average duration measured with HIP events on the engine's stream inside the timed steps.
-`roofline.measured_read_peak` / `measured_copy_peak` are this device's streaming read and
+`roofline.measured_read_peak` / `measured_copy_peak` (--full) are this device's streaming read and
 copy rates (tfidf_hbm_probe, 2 GiB, outside the timed region).
-`cpu_baseline` (N = 1 only) times the oracle restatement on the host cores (one thread per document
+`cpu_baseline` (--full, N = 1 only) times the oracle restatement on the host cores (one thread per document
 shard, OMP_NUM_THREADS = 16 threads on the GPU box) on a bounded sample, with a
 single-thread leg alongside.
 """
@@ -146,6 +153,37 @@ def cpu_baseline(cfg: str, ndocs_sample: int, threads: int, info: dict):
     return out
 
 
+DUMP_PAIR_CAP = 1 << 20   # sampled elements of each per-pair array (6 arrays x 8 MiB as float64)
+DUMP_ROW_CAP = 1 << 19    # ... of each per-document / per-term array (3 arrays x 4 MiB): 60 MiB in all
+
+
+def dump_outputs(eng, out_dir: str, rank: int = 0, nranks: int = 1):
+    """--dump-outputs: the last run's result as a caller receives it (tfidf_fetch: the pairs in
+    output order, the documents, the terms' df) written as <name>.npy in float64, which holds
+    every u32 exactly.  An array longer than its cap is sampled at fixed positions (sorted
+    draws of a generator seeded with a constant), the same for every run of the same
+    arguments; the caps are divided among the ranks, and rank r > 0 writes <name>.rank<r>.npy."""
+    os.makedirs(out_dir, exist_ok=True)
+    sfx = "" if rank == 0 else f".rank{rank}"
+
+    picks = {}
+
+    def sample(a, cap):
+        if len(a) > cap:
+            if (len(a), cap) not in picks:
+                picks[len(a), cap] = np.sort(np.random.default_rng(20240607).choice(len(a), size=cap, replace=False))
+            a = a[picks[len(a), cap]]
+        return np.ascontiguousarray(a, dtype=np.float64)
+
+    with eng.fetched() as r:
+        for key in ("doc", "term", "count", "docsize", "df", "score"):
+            np.save(os.path.join(out_dir, f"pair_{key}{sfx}.npy"), sample(r[key], max(1, DUMP_PAIR_CAP // nranks)))
+        for key in ("doc_id", "doc_size", "term_df"):
+            np.save(os.path.join(out_dir, f"{key}{sfx}.npy"), sample(r[key], max(1, DUMP_ROW_CAP // nranks)))
+        np.save(os.path.join(out_dir, f"sizes{sfx}.npy"),
+                np.array([r["npairs"], r["ndocs"], r["nterms"], r["ndocs_total"]], dtype=np.float64))
+
+
 def main_shards(args):
     """K shards of one config on one GPU through tfidf_group (LocalXport): the exchange
     stage (key all-gather by device copies, union sort, DF all-reduce) at K ranks."""
@@ -175,6 +213,9 @@ def main_shards(args):
     hip_device_sync()
     elapsed = time.perf_counter() - t0
     a1 = g.ranks[0].alloc_counters()
+    if args.dump_outputs:
+        for r, e in enumerate(g.ranks):
+            dump_outputs(e, args.dump_outputs, r, K)
     infos = steps[-1]
     C_all = sum(i["nbytes"] for i in infos)
     P_all = sum(i["npairs"] for i in infos)
@@ -254,6 +295,9 @@ def main_group(args):
     hip_device_sync_all(N)
     elapsed = time.perf_counter() - t0
     a2 = g.ranks[0].alloc_counters()
+    if args.dump_outputs:
+        for r, e in enumerate(g.ranks):
+            dump_outputs(e, args.dump_outputs, r, N)
     infos = steps[-1]
     C_all = float(sum(i["nbytes"] for i in infos))
     P_all = float(sum(i["npairs"] for i in infos))
@@ -327,7 +371,8 @@ def main_group(args):
 
 
 def want_c3(args) -> bool:
-    return args.gpus >= 2 and args.config == "c2" and not args.strong and not args.no_c3 and args.scale == 1.0
+    return (args.full and args.gpus >= 2 and args.config == "c2" and not args.strong and not args.no_c3
+            and args.scale == 1.0)
 
 
 def hip_device_sync_all(n: int):
@@ -352,9 +397,9 @@ def plan_summary(cfg: str, ngpu: int, strong: bool, scale: float = 1.0) -> dict:
             "est_bytes_total": int(sum(x["est_bytes"] for x in shards)), "shards": shards}
 
 
-# BASELINE.json config 3 ("10M docs, ~40 GB Zipfian corpus sharded over 8 MI355X"): a --gpus N
-# run (N >= 2) of the default c2 line measures it too, after the headline steps, so the
-# driver's scaling runs carry it unattended (not in `value`; --no-c3 skips it)
+# BASELINE.json config 3 ("10M docs, ~40 GB Zipfian corpus sharded over 8 MI355X"): a --full
+# --gpus N run (N >= 2) of the default c2 line measures it too, after the headline steps, so
+# the driver's scaling runs carry it unattended (not in `value`; --no-c3 skips it)
 C3_STRONG_STEPS, C3_STRONG_WARMUP = 3, 1
 
 
@@ -388,6 +433,13 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: the per-stage breakdown (--stage-steps), the "
+                         "output emission, the HBM peak probe, the CPU baseline, and the c3 strong follow-up of a "
+                         "multi-GPU c2 line (each with its own --no-* switch); off: those fields are null")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write the last timed step's result (tfidf_fetch) as "
+                         "DIR/<name>.npy in float64 (large arrays: a fixed, seeded sample)")
     ap.add_argument("--config", default="c2")
     ap.add_argument("--scale", type=float, default=1.0)
     ap.add_argument("--cpu-sample-docs", type=int, default=48000)
@@ -415,6 +467,8 @@ def main():
                          "GPU (tfidf_group, in-process transport): measures the multi-rank path and the DF "
                          "exchange (xGMI time excluded); not the headline line")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
     if args.shards >= 2:
         return main_shards(args)
 
@@ -498,18 +552,21 @@ def main():
     idf_steps = [(tt["idf_logs"] / nrun, tt["ms_idf_host"] / nrun, tt["ms_idf_wait"] / nrun)]
     info = eng.info()
     C_bytes, P_pairs, T_tok = info["nbytes"], info["npairs"], info["ntokens"]
-    # the stage breakdown, after the timed region: every stage's events
-    eng.set_timing(True)
+    if args.dump_outputs:
+        dump_outputs(eng, args.dump_outputs, rank, world)
+    # the stage breakdown (--full), after the timed region: every stage's events
     stage_steps = []
-    for _ in range(max(1, args.stage_steps)):
-        eng.run_corpus(corpus)
-        stage_steps.append(eng.info()["stages"])
-    info = eng.info()
+    if args.full:
+        eng.set_timing(True)
+        for _ in range(max(1, args.stage_steps)):
+            eng.run_corpus(corpus)
+            stage_steps.append(eng.info()["stages"])
+        info = eng.info()
 
-    # output emission, outside the timed region and not in `value`:
+    # output emission (--full), outside the timed region and not in `value`:
     # GPU %.16f formatting of the last step's lines, then the pinned D2H + write path
     emit = None
-    if not args.no_emit:
+    if args.full and not args.no_emit:
         # 1) the CLI's path: formatting in document groups overlapped with the pinned D2H
         #    (first call: also pins the context's staging ring); 2) the text again (already
         #    formatted, ring warm): the D2H rate alone
@@ -542,8 +599,8 @@ def main():
     else:
         C_all, P_all, T_all = float(C_bytes), float(P_pairs), float(T_tok)
 
-    # measured streaming peaks, outside the timed region, rank 0 only
-    probe = eng.hbm_probe(2 << 30, 10) if (rank == 0 and not args.no_probe) else None
+    # measured streaming peaks (--full), outside the timed region, rank 0 only
+    probe = eng.hbm_probe(2 << 30, 10) if (args.full and rank == 0 and not args.no_probe) else None
 
     c3_line = None
     if want_c3(args) and world > 1:   # BASELINE config 3 after the headline steps (not in value)
@@ -596,11 +653,14 @@ def main():
             "pairs_per_s": round(P_all * args.steps / elapsed, 1),
             "tokens_per_s": round(T_all * args.steps / elapsed, 1),
             "device_ms_per_step": round(float(np.mean(tot_ms)), 4),
-            "stage_ms": {k: round(v, 4) for k, v in info["stages"].items()},
-            "stage_ms_mean": {k: round(float(np.mean([st[k] for st in stage_steps])), 4) for k in info["stages"]},
-            "stage_ms_max": {k: round(float(np.max([st[k] for st in stage_steps])), 4) for k in info["stages"]},
+            "stage_ms": {k: round(v, 4) for k, v in info["stages"].items()} if args.full else None,
+            "stage_ms_mean": {k: round(float(np.mean([st[k] for st in stage_steps])), 4)
+                              for k in info["stages"]} if args.full else None,
+            "stage_ms_max": {k: round(float(np.max([st[k] for st in stage_steps])), 4)
+                             for k in info["stages"]} if args.full else None,
             "stage_ms_source": f"{len(stage_steps)} untimed steps after the timed ones, with per-stage HIP events "
-                               f"(the timed steps record K1's and the whole run's events only)",
+                               f"(the timed steps record K1's and the whole run's events only)"
+                               if args.full else "not measured (--full)",
             # the idf table (log(N/df) on the host's libm, TFIDF.c:243) is rebuilt inside every
             # timed step on host threads beside the device stages (no cache across runs)
             "idf": {"idf_cached": False,
@@ -631,7 +691,7 @@ def main():
         }
         if c3_line is not None:
             line["c3_strong"] = c3_line
-        if not args.no_cpu_baseline and world == 1:   # rank 0 at N=1 only
+        if args.full and not args.no_cpu_baseline and world == 1:   # rank 0 at N=1 only
             hi = host_cpu_info()
             thr = args.cpu_threads or hi["affinity"]
             if hi["cgroup_cpus"]:

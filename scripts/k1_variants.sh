@@ -7,6 +7,7 @@ set -o pipefail
 cd "${GRAFT_REPO_ROOT:-/root/repo}"
 mkdir -p gpurun_out/var
 timeout -k 10 600 make -j16 -C parallel-systems-mpi-tfidf_amd > gpurun_out/make.log 2>&1 || { echo "make failed"; tail -30 gpurun_out/make.log; exit 1; }
+BENCH_ARGS="--full ${BENCH_ARGS:-}"   # the stage times printed below are measured with --full only
 for v in base ${VARIANTS}; do
   lib=$v; [ "$v" = base ] && lib=""
   TFIDF_LIB=$lib timeout -k 10 200 python -u bench.py --steps ${STEPS:-10} --warmup 2 --no-cpu-baseline --no-probe --no-emit ${BENCH_ARGS:-} > gpurun_out/var/$v.json 2> gpurun_out/var/$v.err || { echo "$v bench failed"; tail -5 gpurun_out/var/$v.err; exit 1; }

@@ -9,10 +9,10 @@ T=${1:-cfgs}
 OUT=$R/gpurun_out/$T
 mkdir -p $OUT
 for cfg in ${CFGS:-c4 c5}; do
-  timeout -k 10 300 python3 -u bench.py --config $cfg --steps ${STEPS:-5} --warmup 2 --no-cpu-baseline --no-probe > $OUT/bench_$cfg.json 2> $OUT/bench_$cfg.err || { echo "bench $cfg failed"; tail -5 $OUT/bench_$cfg.err; exit 1; }
+  timeout -k 10 300 python3 -u bench.py --full --config $cfg --steps ${STEPS:-5} --warmup 2 --no-cpu-baseline --no-probe > $OUT/bench_$cfg.json 2> $OUT/bench_$cfg.err || { echo "bench $cfg failed"; tail -5 $OUT/bench_$cfg.err; exit 1; }
   python3 -c "import json;d=json.load(open('$OUT/bench_$cfg.json'));print('$cfg', d['value'], 'GB/s', d['ms_per_step'], 'ms/step K1', d['roofline']['k1_avg_ms'], d['k1_work'], d['stage_ms'])"
   if [ "${KSTATS:-1}" = 1 ]; then
-    bash scripts/kstats.sh ${T}_$cfg --config $cfg > $OUT/kernel_stats_$cfg.txt 2>&1 || { echo "kstats $cfg failed"; tail -5 $OUT/kernel_stats_$cfg.txt; exit 1; }
+    bash scripts/kstats.sh ${T}_$cfg --full --config $cfg > $OUT/kernel_stats_$cfg.txt 2>&1 || { echo "kstats $cfg failed"; tail -5 $OUT/kernel_stats_$cfg.txt; exit 1; }
     head -12 $OUT/kernel_stats_$cfg.txt
   fi
   if [ "${PMC:-1}" = 1 ]; then

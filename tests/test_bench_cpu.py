@@ -55,13 +55,25 @@ def test_plan_c3_strong_two_way_split():
 
 
 def test_plan_multi_gpu_c2_carries_c3_followup():
-    """A `--gpus N` (N >= 2) weak c2 run also measures the c3 strong split afterwards (nested
-    `c3_strong` object, not in `value`), so the driver's scaling runs carry config 3."""
+    """A `--full --gpus N` (N >= 2) weak c2 run also measures the c3 strong split afterwards
+    (nested `c3_strong` object, not in `value`), so the driver's scaling runs carry config 3;
+    a plain run measures its headline line only."""
     import json
-    p = _bench(["--gpus", "4", "--plan-only"])
+    p = _bench(["--gpus", "4", "--plan-only", "--full"])
     assert p.returncode == 0, p.stderr
     d = json.loads(p.stdout.strip().splitlines()[-1])
     assert d["config"] == "c2" and d["scaling"] == "weak" and d["docs_total"] == 400_000
     assert d["c3_strong"]["n_gpus"] == 4 and d["c3_strong"]["docs_in_shards"] == 10_000_000
-    p1 = _bench(["--gpus", "1", "--plan-only"])
+    p1 = _bench(["--gpus", "1", "--plan-only", "--full"])
     assert "c3_strong" not in json.loads(p1.stdout.strip().splitlines()[-1])
+    p4 = _bench(["--gpus", "4", "--plan-only"])
+    assert p4.returncode == 0, p4.stderr
+    d4 = json.loads(p4.stdout.strip().splitlines()[-1])
+    assert d4["docs_total"] == 400_000 and "c3_strong" not in d4
+
+
+def test_steps_zero_rejected():
+    """--steps sets the number of timed steps; a run without a timed step has no ms_per_step."""
+    p = _bench(["--gpus", "1", "--steps", "0", "--plan-only"])
+    assert p.returncode != 0
+    assert "--steps" in p.stderr
