@@ -1149,12 +1149,16 @@ int launch_df_mark(const uint32_t* df, uint32_t V, uint32_t* present, hipStream_
 }
 /* vals[k] = k-th distinct df value; present_scan = exclusive scan of present (nvals+1) */
 __global__ void k_df_list(const uint32_t* __restrict__ ps, uint64_t nvals, uint32_t* __restrict__ vals) {
-    uint64_t x = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (x >= nvals) return;
-    if (ps[x + 1] != ps[x]) vals[ps[x]] = (uint32_t)x;
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t x = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; x < nvals; x += stride)
+        if (ps[x + 1] != ps[x]) vals[ps[x]] = (uint32_t)x;
 }
 int launch_df_list(const uint32_t* present_scan, uint64_t nvals, uint32_t* vals, hipStream_t s) {
-    k_df_list<<<grid_for(nvals), NT, 0, s>>>(present_scan, nvals, vals);
+    /* nvals = N + 1 reaches 2^32 (ndocs_total = 2^32 - 1), and a grid of 2^24 blocks of 256
+     * threads is more work-items than a launch takes: at most 2^20 blocks, each striding
+     * (one step for every N up to 2^28) */
+    const unsigned full = grid_for(nvals), cap = 1u << 20;
+    k_df_list<<<full < cap ? full : cap, NT, 0, s>>>(present_scan, nvals, vals);
     return ok();
 }
 

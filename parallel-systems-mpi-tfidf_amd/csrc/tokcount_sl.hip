@@ -287,7 +287,7 @@ __device__ __noinline__ uint32_t resolve_slow(const uint8_t* __restrict__ bytes,
     }
     make_long_key(bytes + p0, n, &klo, &khi);
     /* rep = (length << 40) | offset holds 24 length bits (TFIDF_E_CAPACITY beyond) */
-    if (n >= 0xFFFFFFull) atomicOr(status, ST_TERM_LONG);
+    if (n > 0xFFFFFFull) atomicOr(status, ST_TERM_LONG);   /* 2^24 - 1 bytes still fit */
     const uint64_t rep = ((n < 0xFFFFFFull ? n : 0xFFFFFFull) << 40) | p0;
     return vocab_insert_s(keys, reps, mask, klo, khi, rep, status, bytes);
 }

@@ -528,3 +528,69 @@ def test_rccl_clique_failure_releases_peers(xchg, monkeypatch):
         with pytest.raises(tfidf_abi.TfidfError) as ei2:
             g.run_host(shards)     # the clique was aborted: unusable until reopened
         assert ei2.value.rc in (-11, -10)
+
+
+def _six_letter_words(n, rng):
+    from test_gpu_paths import fixed_words
+    return fixed_words(np.sort(rng.choice(26 ** 6, n, replace=False)), 6).view("S6").ravel().tolist()
+
+
+def _two_word_shards(words0, words1, rng, ndocs=300):
+    """rank 0 holds documents 100..399 over words0, rank 1 documents 400..699 over words1 (each
+    word at least once): every name of rank 0 orders before every name of rank 1, so the ranks'
+    texts concatenate to the single-rank output.  Returns the shards and the oracle's result."""
+    from helpers import docs_to_arrays
+    from test_gpu_paths import docs_covering
+    N = 2 * ndocs
+    shards, docs = [], []
+    for r, words in enumerate((words0, words1)):
+        mine = docs_covering(words, ndocs, rng)
+        d, o = docs_to_arrays(mine)
+        shards.append((d, o, np.arange(100 + r * ndocs, 100 + (r + 1) * ndocs, dtype=np.uint32), N))
+        docs += mine
+    d, o = docs_to_arrays(docs)
+    return shards, oracle_py.run(d, o, np.arange(100, 100 + N, dtype=np.uint32), N)
+
+
+@pytest.mark.parametrize("xchg", ["owner", "dense_table"])
+def test_group_long_terms_on_the_radix_vocabulary_path(xchg, monkeypatch):
+    """Both ranks hold more than SORT_TILE_MAXN = 131 072 terms, so each orders its vocabulary
+    by the radix sort and runs the long-term fix-up over the gathered radix order; both hold
+    terms of 16 bytes or more: one shared, several of their own, and runs tied on their first
+    16 bytes (one of them split over the ranks).  Rank-order text and arrays equal the
+    single-rank oracle's."""
+    monkeypatch.setenv("TFIDF_XCHG", xchg)
+    rng = np.random.default_rng(77)
+    pool = _six_letter_words(200_000, rng)
+    rng.shuffle(pool)
+    base = b"sixteen_byte_pre"
+    assert len(base) == 16
+    ties = [base, base + b"a", base + b"b", base + b"\x01", base + b"ab", base + b"z" * 22]
+    shared = b"a_long_term_shared_by_both_ranks"
+    long0 = [shared, ties[0], ties[1], ties[3], ties[5]] + [b"only_on_rank_zero_%04d" % i for i in range(50)]
+    long1 = [shared, ties[1], ties[2], ties[4]] + [b"only_on_rank_one_%04d" % i for i in range(50)]
+    shards, ora = _two_word_shards(pool[:135_000] + long0, pool[65_000:] + long1, rng)
+    texts, res, infos = _run_group(shards, 2)
+    assert all(i["nterms"] > 131072 for i in infos)
+    assert b"".join(texts) == ora["output_txt"]
+    assert_same_result(_concat(res), ora)
+    assert all(i["nterms_global"] == ora["nterms"] for i in infos)
+    assert bool(infos[0]["flags"] & tfidf_abi.RUN_XCHG_DENSE) == (xchg == "dense_table")
+
+
+@pytest.mark.parametrize("maxv", [131072, 131073])
+def test_group_exchange_form_chosen_by_largest_vocabulary(maxv, monkeypatch):
+    """TFIDF_XCHG unset: the dense all-reduce form up to 2^17 terms on the largest rank, the
+    hash-owner form from 2^17 + 1; both equal the single-rank oracle."""
+    monkeypatch.delenv("TFIDF_XCHG", raising=False)
+    rng = np.random.default_rng(maxv)
+    pool = _six_letter_words(maxv + 3000, rng)
+    rng.shuffle(pool)
+    shards, ora = _two_word_shards(pool[:maxv], pool[maxv - 2000:], rng)
+    texts, res, infos = _run_group(shards, 2)
+    assert [i["nterms"] for i in infos] == [maxv, 5000]
+    dense = [bool(i["flags"] & tfidf_abi.RUN_XCHG_DENSE) for i in infos]
+    assert dense == [maxv <= 131072] * 2
+    assert b"".join(texts) == ora["output_txt"]
+    assert_same_result(_concat(res), ora)
+    assert all(i["nterms_global"] == ora["nterms"] == maxv + 3000 for i in infos)

@@ -415,16 +415,19 @@ def test_dense_merge_long_documents(engine):
     check_vs_oracle(engine, d2, o2)
 
 
-def test_many_long_terms_sharing_prefixes(engine):
+@pytest.mark.parametrize("per_prefix", [30000, 50000])
+def test_many_long_terms_sharing_prefixes(engine, per_prefix):
     """~1e5 distinct long terms tied on their first 16 (and 32, 48, ...) bytes: URL-like
     runs, terms that are prefixes of others, a byte < TAB after a shared prefix, and a
     few terms sharing 200 bytes.  Their order (strcmp of "w\\t") comes from the iterated
-    segmented sort (vocab_long_fixup); against the oracle, bit-exact."""
+    segmented sort (vocab_long_fixup); against the oracle, bit-exact.  90 008 terms are
+    ordered by the tile sort; 150 008 take the radix sort of the first 8 bytes, and the
+    fix-up then runs over the gathered radix order (launch_gather_u128)."""
     rng = np.random.default_rng(21)
     alpha = np.frombuffer(b"abcdefghijklmnopqrstuvwxyz0123456789_/", dtype=np.uint8)
     words = set()
     for pre in (b"https://en.wikipedia.org/wiki/", b"/usr/local/lib/python3/site-packages/", b"x" * 40):
-        while len(words) < 30000 * (1 + [b"https://en.wikipedia.org/wiki/", b"/usr/local/lib/python3/site-packages/",
+        while len(words) < per_prefix * (1 + [b"https://en.wikipedia.org/wiki/", b"/usr/local/lib/python3/site-packages/",
                                           b"x" * 40].index(pre)):
             L = int(rng.integers(0, 12))
             words.add(pre + bytes(alpha[rng.integers(0, len(alpha), L)]))
@@ -441,6 +444,9 @@ def test_many_long_terms_sharing_prefixes(engine):
             docs.append(b" ".join(cur) + b"\n")
             cur = []
     check_vs_oracle(engine, *docs_to_arrays(docs))
+    nterms = engine.info()["nterms"]
+    assert nterms == 3 * per_prefix + len(extra)
+    assert (nterms > 131072) == (per_prefix == 50000)   # SORT_TILE_MAXN: the radix side
 
 
 @pytest.mark.parametrize("wgs", [None, "16"])
@@ -531,6 +537,37 @@ def test_term_of_16_mib_is_a_capacity_error(engine):
     big = np.full((16 << 20) + 7, ord("a"), dtype=np.uint8)
     data = np.concatenate([np.frombuffer(b"x y\n", dtype=np.uint8), big])
     off = np.array([0, 4, len(data)], dtype=np.uint64)
+    with pytest.raises(tfidf_abi.TfidfError) as ei:
+        engine.run_host(data, off)
+    assert ei.value.rc == -9
+    g = load_golden("g1_whitespace")
+    engine.run_host(g["data"], g["off"])
+    assert engine.fetch()["output_txt"] == g["output"]
+
+
+def _one_token_corpus(length):
+    """normal documents around one document that is a single token of `length` bytes"""
+    big = np.full(length, ord("a"), dtype=np.uint8)
+    head = np.frombuffer(b"x y\naaaa aaa b\n", dtype=np.uint8)
+    tail = np.frombuffer(b"\nb aaaa z\n", dtype=np.uint8)
+    data = np.concatenate([head, big, tail])
+    off = np.array([0, 4, len(head), len(head) + length + 1, len(data)], dtype=np.uint64)
+    return data, off
+
+
+def test_longest_legal_term_vs_oracle(engine):
+    """A token of 2^24 - 1 bytes, the largest length the vocabulary entry's 24 bits hold:
+    counted, ordered and emitted (its 16 MiB line included) as the oracle does."""
+    data, off = _one_token_corpus((1 << 24) - 1)
+    res = check_vs_oracle(engine, data, off)
+    assert max(len(t) for t in res["terms"]) == (1 << 24) - 1
+    assert res["npairs"] == 9
+
+
+def test_term_of_exactly_2_pow_24_bytes_is_a_capacity_error(engine):
+    """The first length that does not fit: TFIDF_E_CAPACITY, as for every longer token; the
+    engine then runs the longest legal one."""
+    data, off = _one_token_corpus(1 << 24)
     with pytest.raises(tfidf_abi.TfidfError) as ei:
         engine.run_host(data, off)
     assert ei.value.rc == -9
