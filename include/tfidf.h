@@ -271,6 +271,79 @@ int tfidf_write_output(const tfidf_result* r, const char* path);
  * one block pair for this shard, pairs in output order. */
 int tfidf_print_jobs(const tfidf_result* r);
 
+/* ---------------------------------------------------------------- query ----- */
+
+/* Batched top-k document retrieval over the resident result of the last run.  The reference
+ * ends at the sorted lines (TFIDF.c:245,273-282); ranking reads the scores it prints
+ * (TFIDF.c:202,243-244) where tfidf_run left them, without tfidf_fetch's copy of every pair.
+ *
+ * Query q is bytes[q_off[q], q_off[q + 1]) (host pointers), tokenised like a document
+ * (tfidf_corpus above; TFIDF.c:141-147,152): tokens are maximal runs of bytes not in
+ * {0x20,0x09..0x0D}, a term is the token's bytes up to its first NUL.  w(q,t) = the tokens
+ * of q whose term is t.  A term outside this shard's vocabulary contributes nothing; a term
+ * of >= 16 bytes matches a vocabulary term only when the bytes are equal (the 120-bit key
+ * alone does not decide: the rule of TFIDF_E_CAPACITY above and TFIDF.c:152,172's strcmp).
+ *   score(q,d)   = (..((+0.0 + fl(w1*s1)) + fl(w2*s2)) + ..) in IEEE binary64, round to
+ *                  nearest, every product rounded before its add (never fused), over the
+ *                  terms t1 < t2 < .. of q that occur in d in term-table order (the order of
+ *                  tfidf_result.pair_term inside a document), s = the run's pair_score
+ *   hits of q    = the documents holding >= 1 term of q (a score of 0.0 is a hit: df = N
+ *                  gives idf 0, TFIDF.c:243), ordered by score descending, then global
+ *                  document id ascending numerically (not the "docN@" strcmp order of the
+ *                  lines, TFIDF.c:273); the first k are returned. */
+#define TFIDF_QUERY_MAX_K 1024u
+#define TFIDF_QUERY_MAX_QUERIES 65536u
+typedef struct tfidf_queries {
+    const uint8_t*  bytes;
+    uint64_t        nbytes;
+    const uint64_t* q_off;       /* nqueries + 1 entries, non-decreasing, q_off[nqueries] <= nbytes */
+    uint32_t        nqueries;
+} tfidf_queries;
+/* Arrays are owned by the library and released by tfidf_hits_free(). */
+typedef struct tfidf_hits {
+    uint32_t  nqueries, k;
+    uint32_t* nhits;        /* per query, <= k */
+    uint64_t* nmatch;       /* per query: documents holding >= 1 query term (all hits, before the cut) */
+    uint32_t* nterms_found; /* per query: distinct query terms present in the vocabulary */
+    uint32_t* doc;          /* nqueries * k, row q at q * k: global doc ids ("docN", TFIDF.c:132) */
+    double*   score;        /* same layout */
+} tfidf_hits;
+/* Ranks this context's documents for every query of the batch.  TFIDF_E_STATE before a
+ * successful tfidf_run; TFIDF_E_INVAL for a NULL argument, k == 0, k > TFIDF_QUERY_MAX_K,
+ * nqueries > TFIDF_QUERY_MAX_QUERIES, a non-monotone q_off or q_off[nqueries] > nbytes.
+ * nqueries == 0 and empty queries are valid (nhits = nmatch = 0).  The run's result is not
+ * disturbed (tfidf_fetch / tfidf_format / tfidf_write_output_gpu give the same bytes after
+ * the call), and the run's corpus must still be valid, as for tfidf_format (long terms are
+ * compared with it).  With a communicator attached (tfidf_comm_init) the call is local, not
+ * collective: it ranks this shard's documents with the run's global-df scores
+ * (TFIDF.c:209-222).  The batch is scored in groups of queries, one pass over the pairs per
+ * group, whose per-(query, document) accumulators stay under TFIDF_QUERY_ACC_MB (read at
+ * tfidf_open, default 1024) MiB; the buffers belong to the context, so a repeated call
+ * allocates nothing (tfidf_alloc_stats). */
+int tfidf_query(tfidf_ctx* ctx, const tfidf_queries* queries, uint32_t k, tfidf_hits* out);
+void tfidf_hits_free(tfidf_hits* hits);
+/* The same over every shard of a group (tfidf_group_run; the gather + sort of
+ * TFIDF.c:253-273 for hits instead of lines): every rank ranks its shard on its own host
+ * thread, the host merges the ranks' rows by the same order (the shards partition the
+ * documents, so this is the exact top-k), nmatch sums over the ranks and nterms_found
+ * counts the distinct query terms found in at least one rank's vocabulary. */
+int tfidf_group_query(tfidf_group* g, const tfidf_queries* queries, uint32_t k, tfidf_hits* out);
+/* Counters of the last tfidf_query (the caller sets `size` = sizeof, as tfidf_run_info). */
+typedef struct tfidf_query_info {
+    uint64_t size;
+    uint32_t nqueries, k;
+    uint32_t nterms;          /* distinct terms of the batch */
+    uint32_t nterms_found;    /* ... present in the vocabulary */
+    uint32_t ngroups;         /* scoring passes over the pairs */
+    uint32_t group_queries;   /* queries per group the budget allowed */
+    uint64_t acc_bytes;       /* accumulator + candidate bytes of the largest group */
+    double   ms_lookup;       /* device times (HIP events), summed over the groups */
+    double   ms_score;
+    double   ms_topk;
+    double   ms_total;        /* host wall time of the whole call */
+} tfidf_query_info;
+int tfidf_last_query_info(const tfidf_ctx* ctx, tfidf_query_info* info);
+
 /* ---------------------------------------------------------------- ingest ---- */
 
 /* Reference input contract (TFIDF.c:98-110,130-147): N = number of entries of `dir`

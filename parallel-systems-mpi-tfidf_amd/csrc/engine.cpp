@@ -26,12 +26,14 @@
 #include <time.h>
 #include <unistd.h>
 
+#include <algorithm>
 #include <atomic>
 #include <chrono>
 #include <condition_variable>
 #include <mutex>
 #include <string>
 #include <thread>
+#include <unordered_map>
 #include <vector>
 
 #include "../../include/tfidf.h"
@@ -231,6 +233,14 @@ struct tfidf_ctx {
     const uint32_t* run_merged = nullptr;
     /* output text (emit.hip) */
     DevBuf t_key, t_len, doc_tbytes, doc_toff, text;
+    /* top-k retrieval (tfidf_query, query.hip): the batch's terms and their ranks, a group's
+     * term table, the (query, output position) accumulators and matched counts, the list of
+     * long documents, the top-k rounds' two candidate buffers, per-query counters */
+    DevBuf q_terms, q_rank, q_tab, q_acc, q_cnt, q_big, q_cand0, q_cand1, q_misc;
+    uint64_t query_acc_bytes = 1024ull << 20;   /* env TFIDF_QUERY_ACC_MB: accumulator budget of a query group */
+    hipEvent_t ev_q[3] = {};                    /* lookup / score / top-k bounds (created by the first query) */
+    uint32_t ncu = 0;
+    tfidf_query_info qinfo{};
 #define WR_NBUF 8
 #define WR_BUF (16ull << 20)
 #define WR_GROUPS 8
@@ -410,6 +420,11 @@ int tfidf_open(int device, tfidf_ctx** out) {
     ctx->xb_stage_max = kxb ? (uint32_t)atoi(kxb) : ~0u;
     const char* kds = getenv("TFIDF_DF_SPLIT");
     ctx->df_split = !(kds && !strcmp(kds, "0"));
+    const char* kq = getenv("TFIDF_QUERY_ACC_MB");
+    if (kq) {
+        const unsigned long long mb = strtoull(kq, nullptr, 0);
+        if (mb >= 1 && mb <= (1ull << 20)) ctx->query_acc_bytes = mb << 20;
+    }
     const char* kn = getenv("TFIDF_TEST_XNOMEM_RANK");
     ctx->xnomem_rank = kn ? atoi(kn) : -1;
     /* diagnostics: initial vocabulary capacity (power of two) and the loads it may reach
@@ -480,6 +495,11 @@ void tfidf_close(tfidf_ctx* ctx) {
         if (ctx->wr_fmt[i]) (void)hipEventDestroy(ctx->wr_fmt[i]);
     ctx->arena2_buf.release();
     ctx->df_scratch.release();
+    for (hipEvent_t e : ctx->ev_q)
+        if (e) (void)hipEventDestroy(e);
+    for (DevBuf* b : {&ctx->q_terms, &ctx->q_rank, &ctx->q_tab, &ctx->q_acc, &ctx->q_cnt, &ctx->q_big, &ctx->q_cand0,
+                      &ctx->q_cand1, &ctx->q_misc})
+        b->release();
     DevBuf* bufs[] = {&ctx->arena_buf, &ctx->in_bytes, &ctx->in_off, &ctx->in_ids, &ctx->syn_bytes, &ctx->syn_off,
                       &ctx->syn_ids, &ctx->syn_ntok, &ctx->syn_blkfirst, &ctx->syn_blkbytes, &ctx->syn_cdf,
                       &ctx->chunk_start, &ctx->chunk_doc, &ctx->vkeys, &ctx->vrep, &ctx->rec_slot, &ctx->rec_cnt,
@@ -2323,4 +2343,280 @@ extern "C" int tfidf_format_f64(tfidf_ctx* ctx, const double* vals, uint64_t n, 
     o.release();
     if (!rc && (st & ST_BOUNDS)) rc = TFIDF_E_INVAL;
     return rc;
+}
+
+/* ------------------------------------------------------------------- query ----
+ * Top-k retrieval over the resident result (query.hip).  The host tokenises the batch
+ * (fscanf("%s") tokens, terms cut at their first NUL: TFIDF.c:141-147,152), the device maps
+ * the batch's distinct terms to term ranks, and every group of queries takes one pass over
+ * the pairs and a few top-k rounds.  The vocabulary table is only read: no stage after K1
+ * writes vkeys or vrep (the vocabulary stage reads them into its own sort keys and writes
+ * rank_of_slot at the used slots; fetch and format read them again), and all three K1
+ * kernels insert from the pair-aligned home (vocab_insert's default, VS_HOME). */
+
+static inline bool query_is_ws(uint8_t c) { return c == 0x20u || (c >= 0x09u && c <= 0x0Du); }
+
+extern "C" void tfidf_hits_free(tfidf_hits* h) {
+    if (!h) return;
+    free(h->nhits); free(h->nmatch); free(h->nterms_found); free(h->doc); free(h->score);
+    memset(h, 0, sizeof(*h));
+}
+
+int tfidf_ctx_query(tfidf_ctx* ctx, const tfidf_queries* qs, uint32_t k, tfidf_hits* out, std::vector<uint8_t>* found_out,
+                    std::vector<uint64_t>* found_off_out) {
+    if (!ctx || !qs || !out) return TFIDF_E_INVAL;
+    if (k == 0 || k > TFIDF_QUERY_MAX_K || qs->nqueries > TFIDF_QUERY_MAX_QUERIES) return TFIDF_E_INVAL;
+    const uint32_t nq = qs->nqueries;
+    if (nq && !qs->q_off) return TFIDF_E_INVAL;
+    for (uint32_t q = 0; q < nq; ++q)
+        if (qs->q_off[q] > qs->q_off[q + 1]) return TFIDF_E_INVAL;
+    if (nq && (qs->q_off[nq] > qs->nbytes || (qs->q_off[nq] > qs->q_off[0] && !qs->bytes))) return TFIDF_E_INVAL;
+    if (!ctx->have_result) return TFIDF_E_STATE;
+    const auto wall0 = std::chrono::steady_clock::now();
+    HIPCHK(hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    for (hipEvent_t& e : ctx->ev_q)
+        if (!e) HIPCHK(hipEventCreate(&e));
+    if (!ctx->ncu) {
+        int n = 0;
+        if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, ctx->device) != hipSuccess || n <= 0) n = 256;
+        ctx->ncu = (uint32_t)n;
+    }
+    memset(out, 0, sizeof(*out));
+    out->nqueries = nq;
+    out->k = k;
+    out->nhits = (uint32_t*)calloc((size_t)nq + 1, 4);
+    out->nmatch = (uint64_t*)calloc((size_t)nq + 1, 8);
+    out->nterms_found = (uint32_t*)calloc((size_t)nq + 1, 4);
+    out->doc = (uint32_t*)calloc((size_t)nq * k + 1, 4);
+    out->score = (double*)calloc((size_t)nq * k + 1, 8);
+    struct HitsGuard {   /* an error return leaves *out zeroed */
+        tfidf_hits* h;
+        ~HitsGuard() { if (h) tfidf_hits_free(h); }
+    } guard{out};
+    if (!out->nhits || !out->nmatch || !out->nterms_found || !out->doc || !out->score) return TFIDF_E_NOMEM;
+
+    /* ---- tokens -> the batch's distinct terms, per query (term, weight) in first-occurrence order ---- */
+    std::unordered_map<std::string, uint32_t> term_id;
+    std::vector<const std::string*> terms;
+    std::vector<uint64_t> qt_off((size_t)nq + 1, 0);
+    std::vector<uint32_t> qt_term, qt_w;
+    for (uint32_t q = 0; q < nq; ++q) {
+        const uint8_t* b = qs->bytes;
+        const uint64_t e = qs->q_off[q + 1];
+        std::unordered_map<uint32_t, size_t> seen;
+        for (uint64_t i = qs->q_off[q]; i < e;) {
+            while (i < e && query_is_ws(b[i])) ++i;
+            if (i >= e) break;
+            const uint64_t t0 = i;
+            while (i < e && !query_is_ws(b[i])) ++i;
+            uint64_t tl = 0;
+            while (t0 + tl < i && b[t0 + tl] != 0) ++tl;   /* strcmp semantics: up to the first NUL */
+            auto ins = term_id.emplace(std::string((const char*)b + t0, (size_t)tl), (uint32_t)terms.size());
+            if (ins.second) terms.push_back(&ins.first->first);
+            auto at = seen.emplace(ins.first->second, qt_term.size());
+            if (at.second) { qt_term.push_back(ins.first->second); qt_w.push_back(1u); }
+            else if (qt_w[at.first->second] != 0xFFFFFFFFu) ++qt_w[at.first->second];
+        }
+        qt_off[q + 1] = qt_term.size();
+    }
+    const uint32_t nT = (uint32_t)terms.size();
+    tfidf_query_info qi{};
+    qi.nqueries = nq;
+    qi.k = k;
+    qi.nterms = nT;
+
+    /* ---- lookup: one lane per distinct term ---- */
+    std::vector<uint32_t> rank(nT, QUERY_NO_TERM);
+    std::vector<uint64_t> toff((size_t)nT + 1, 0);
+    std::string blob;
+    if (nT && ctx->V) {
+        for (uint32_t t = 0; t < nT; ++t) { toff[t] = blob.size(); blob += *terms[t]; }
+        toff[nT] = blob.size();
+        const size_t offb = ((size_t)nT + 1) * 8;
+        ENSURE(ctx->q_terms, offb + blob.size() + 16);
+        ENSURE(ctx->q_rank, (size_t)nT * 4 + 4);
+        HIPCHK(hipMemcpyAsync(ctx->q_terms.p, toff.data(), offb, hipMemcpyHostToDevice, s));
+        if (!blob.empty())
+            HIPCHK(hipMemcpyAsync(ctx->q_terms.as<uint8_t>() + offb, blob.data(), blob.size(), hipMemcpyHostToDevice, s));
+        QLookupArgs la{};
+        la.tbytes = ctx->q_terms.as<uint8_t>() + offb;
+        la.toff = ctx->q_terms.as<uint64_t>();
+        la.nterms = nT;
+        la.vkeys = ctx->vkeys.as<uint4>();
+        la.vrep = ctx->vrep.as<uint64_t>();
+        la.mask = ctx->vcap - 1;
+        la.home = ~1ull;
+        la.rank_of_slot = ctx->rank_of_slot.as<uint32_t>();
+        la.corpus = ctx->dev_bytes;
+        la.corpus_bytes = ctx->corpus.nbytes;
+        la.V = ctx->V;
+        la.rank_out = ctx->q_rank.as<uint32_t>();
+        HIPCHK(hipEventRecord(ctx->ev_q[0], s));
+        if (launch_query_lookup(la, s)) { HIPCHK(hipGetLastError()); return TFIDF_E_HIP; }
+        HIPCHK(hipEventRecord(ctx->ev_q[1], s));
+        HIPCHK(hipMemcpyAsync(rank.data(), ctx->q_rank.p, (size_t)nT * 4, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        float ms = 0;
+        (void)hipEventElapsedTime(&ms, ctx->ev_q[0], ctx->ev_q[1]);
+        qi.ms_lookup = ms;
+    }
+    for (uint32_t t = 0; t < nT; ++t) qi.nterms_found += rank[t] != QUERY_NO_TERM;
+    if (found_out) found_out->assign(qt_term.size(), 0);
+    if (found_off_out) *found_off_out = qt_off;
+    for (uint32_t q = 0; q < nq; ++q)
+        for (uint64_t x = qt_off[q]; x < qt_off[q + 1]; ++x)
+            if (rank[qt_term[x]] != QUERY_NO_TERM) {
+                ++out->nterms_found[q];
+                if (found_out) (*found_out)[x] = 1;
+            }
+
+    /* ---- query groups under the accumulator budget ---- */
+    const uint32_t N = ctx->ndocs;
+    const uint64_t nsl0 = ((uint64_t)N + QT_SLICE - 1) / QT_SLICE;
+    const uint64_t per_q = (uint64_t)N * 12 + 2 * (nsl0 * k * 12 + nsl0 * 4) + 8;
+    uint64_t G = ctx->query_acc_bytes / per_q;
+    G = G < 1 ? 1 : (G > QG_MAX ? QG_MAX : G);
+    if (G > nq) G = nq ? nq : 1;
+    qi.group_queries = (uint32_t)G;
+    qi.acc_bytes = G * per_q;
+    const uint64_t cand_el = G * nsl0 * k;   /* entries of one candidate buffer */
+    if (N && nq) {
+        ENSURE(ctx->q_acc, G * N * 8);
+        ENSURE(ctx->q_cnt, G * N * 4);
+        ENSURE(ctx->q_big, (size_t)N * 4 + 4);
+        ENSURE(ctx->q_cand0, cand_el * 12 + G * nsl0 * 4);
+        ENSURE(ctx->q_cand1, cand_el * 12 + G * nsl0 * 4);
+        ENSURE(ctx->q_misc, G * 8 + 16);
+    }
+    std::vector<uint64_t> h_s((size_t)G * k), h_nm(G);
+    std::vector<uint32_t> h_id((size_t)G * k), h_n(G);
+    struct Post { uint32_t rank, q, w; };
+    std::vector<Post> posts;
+    std::vector<uint32_t> tab;
+    for (uint32_t g0 = 0; N && g0 < nq; g0 += (uint32_t)G) {
+        const uint32_t gn = nq - g0 < G ? nq - g0 : (uint32_t)G;
+        posts.clear();
+        for (uint32_t q = 0; q < gn; ++q)
+            for (uint64_t x = qt_off[g0 + q]; x < qt_off[g0 + q + 1]; ++x)
+                if (rank[qt_term[x]] != QUERY_NO_TERM) posts.push_back(Post{rank[qt_term[x]], q, qt_w[x]});
+        if (posts.empty()) continue;   /* no term of the group is in the vocabulary: no hits */
+        if (posts.size() > 0x7FFFFFFFull) return TFIDF_E_CAPACITY;
+        ++qi.ngroups;
+        std::sort(posts.begin(), posts.end(), [](const Post& a, const Post& b) { return a.rank != b.rank ? a.rank < b.rank : a.q < b.q; });
+        /* the group's table: sorted distinct ranks, CSR offsets, postings' queries and weights */
+        uint32_t nG = 0;
+        for (size_t i = 0; i < posts.size(); ++i) nG += i == 0 || posts[i].rank != posts[i - 1].rank;
+        const uint32_t nP = (uint32_t)posts.size();
+        tab.assign((size_t)2 * nG + 1 + 2 * (size_t)nP, 0);
+        uint32_t* gterm = tab.data();
+        uint32_t* poff = gterm + nG;
+        uint32_t* pq = poff + nG + 1;
+        uint32_t* pw = pq + nP;
+        for (uint32_t i = 0, t = 0; i < nP; ++i) {
+            if (i == 0 || posts[i].rank != posts[i - 1].rank) { gterm[t] = posts[i].rank; poff[t] = i; ++t; }
+            pq[i] = posts[i].q;
+            pw[i] = posts[i].w;
+        }
+        poff[nG] = nP;
+        ENSURE(ctx->q_tab, tab.size() * 4 + 16);
+        HIPCHK(hipMemcpyAsync(ctx->q_tab.p, tab.data(), tab.size() * 4, hipMemcpyHostToDevice, s));
+        unsigned long long* d_nm = ctx->q_misc.as<unsigned long long>();
+        HIPCHK(hipMemsetAsync(d_nm, 0, (size_t)G * 8, s));
+        QScoreArgs sa{};
+        sa.out_off = ctx->out_off.as<uint64_t>();
+        sa.out_term = ctx->out_term.as<uint32_t>();
+        sa.out_score = ctx->out_score.as<double>();
+        sa.ndocs = N;
+        sa.npairs = ctx->npairs;
+        sa.gterm = ctx->q_tab.as<uint32_t>();
+        sa.ngterm = nG;
+        sa.post_off = sa.gterm + nG;
+        sa.post_q = sa.post_off + nG + 1;
+        sa.post_w = sa.post_q + nP;
+        sa.tab_words = tab.size() <= 0xFFFFFFFFull ? (uint32_t)tab.size() : 0u;
+        sa.nq = gn;
+        sa.acc = ctx->q_acc.as<double>();
+        sa.cnt = ctx->q_cnt.as<uint32_t>();
+        sa.big_list = ctx->q_big.as<uint32_t>();
+        sa.big_count = (uint32_t*)(d_nm + G);
+        HIPCHK(hipEventRecord(ctx->ev_q[0], s));
+        if (launch_query_score(sa, ctx->ncu, s)) { HIPCHK(hipGetLastError()); return TFIDF_E_HIP; }
+        HIPCHK(hipEventRecord(ctx->ev_q[1], s));
+        /* top-k rounds: the accumulators' slices, then the slices' lists until one is left */
+        DevBuf* cand[2] = {&ctx->q_cand0, &ctx->q_cand1};
+        auto cs = [&](int c) { return cand[c]->as<uint64_t>(); };
+        auto cid = [&](int c) { return (uint32_t*)(cs(c) + cand_el); };
+        auto cn = [&](int c) { return cid(c) + cand_el; };
+        int cur = 0;
+        QTopkArgs ta{};
+        ta.acc = sa.acc;
+        ta.cnt = sa.cnt;
+        ta.order = ctx->order;
+        ta.doc_ids = ctx->dev_ids;
+        ta.n_in = N;
+        ta.kk = k;
+        ta.out_s = cs(0);
+        ta.out_id = cid(0);
+        ta.out_n = cn(0);
+        ta.out_slices = (uint32_t)nsl0;
+        ta.nmatch = d_nm;
+        if (launch_query_topk(ta, gn, s)) { HIPCHK(hipGetLastError()); return TFIDF_E_HIP; }
+        uint64_t nsl = nsl0;
+        while (nsl > 1) {
+            QTopkArgs tb{};
+            tb.in_s = cs(cur);
+            tb.in_id = cid(cur);
+            tb.in_n = cn(cur);
+            tb.in_slices = (uint32_t)nsl;
+            tb.n_in = nsl * k;
+            tb.kk = k;
+            nsl = (tb.n_in + QT_SLICE - 1) / QT_SLICE;
+            cur ^= 1;
+            tb.out_s = cs(cur);
+            tb.out_id = cid(cur);
+            tb.out_n = cn(cur);
+            tb.out_slices = (uint32_t)nsl;
+            tb.nmatch = d_nm;
+            if (launch_query_topk(tb, gn, s)) { HIPCHK(hipGetLastError()); return TFIDF_E_HIP; }
+        }
+        HIPCHK(hipEventRecord(ctx->ev_q[2], s));
+        /* one slice per query is left: row q = entries [q * k, q * k + n[q]) */
+        HIPCHK(hipMemcpyAsync(h_s.data(), cs(cur), (size_t)gn * k * 8, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(h_id.data(), cid(cur), (size_t)gn * k * 4, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(h_n.data(), cn(cur), (size_t)gn * 4, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(h_nm.data(), d_nm, (size_t)gn * 8, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        float ms = 0;
+        (void)hipEventElapsedTime(&ms, ctx->ev_q[0], ctx->ev_q[1]);
+        qi.ms_score += ms;
+        (void)hipEventElapsedTime(&ms, ctx->ev_q[1], ctx->ev_q[2]);
+        qi.ms_topk += ms;
+        for (uint32_t q = 0; q < gn; ++q) {
+            const uint32_t n = h_n[q] < k ? h_n[q] : k;
+            out->nhits[g0 + q] = n;
+            out->nmatch[g0 + q] = h_nm[q];
+            for (uint32_t i = 0; i < n; ++i) {
+                out->doc[(size_t)(g0 + q) * k + i] = h_id[(size_t)q * k + i];
+                memcpy(&out->score[(size_t)(g0 + q) * k + i], &h_s[(size_t)q * k + i], 8);
+            }
+        }
+    }
+    qi.ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - wall0).count();
+    ctx->qinfo = qi;
+    guard.h = nullptr;
+    return TFIDF_OK;
+}
+
+extern "C" int tfidf_query(tfidf_ctx* ctx, const tfidf_queries* queries, uint32_t k, tfidf_hits* out) {
+    return tfidf_ctx_query(ctx, queries, k, out, nullptr, nullptr);
+}
+
+extern "C" int tfidf_last_query_info(const tfidf_ctx* ctx, tfidf_query_info* info) {
+    if (!ctx || !info || info->size < sizeof(uint64_t)) return TFIDF_E_INVAL;
+    const uint64_t n = info->size < sizeof(tfidf_query_info) ? info->size : sizeof(tfidf_query_info);
+    tfidf_query_info o = ctx->qinfo;
+    o.size = n;
+    memcpy(info, &o, (size_t)n);
+    return TFIDF_OK;
 }

@@ -579,6 +579,78 @@ int tfidf_group_write_output(tfidf_group* g, const char* path) {
     return TFIDF_OK;
 }
 
+/* Every rank ranks its own shard (tfidf_query is local to a context), one host thread per
+ * rank as in tfidf_group_run; the rows are merged here by (score descending, document id
+ * ascending).  The shards partition the documents, so a document of the global top-k is in
+ * its shard's top-k and the merge is exact. */
+int tfidf_group_query(tfidf_group* g, const tfidf_queries* queries, uint32_t k, tfidf_hits* out) {
+    if (!g || !queries || !out) return TFIDF_E_INVAL;
+    const int R = g->n;
+    std::vector<int> rc((size_t)R, TFIDF_OK);
+    std::vector<tfidf_hits> part((size_t)R);
+    std::vector<std::vector<uint8_t>> found((size_t)R);
+    std::vector<std::vector<uint64_t>> foff((size_t)R);
+    for (tfidf_hits& h : part) memset(&h, 0, sizeof(h));
+    {
+        std::vector<std::thread> th;
+        for (int r = 1; r < R; ++r)
+            th.emplace_back([&, r] { rc[r] = tfidf_ctx_query(g->ctx[r], queries, k, &part[r], &found[r], &foff[r]); });
+        rc[0] = tfidf_ctx_query(g->ctx[0], queries, k, &part[0], &found[0], &foff[0]);
+        for (auto& t : th) t.join();
+    }
+    int err = TFIDF_OK;
+    for (int r = 0; r < R && !err; ++r) err = rc[r];
+    const uint32_t nq = queries->nqueries;
+    tfidf_hits m;
+    memset(&m, 0, sizeof(m));
+    if (!err) {
+        m.nqueries = nq;
+        m.k = k;
+        m.nhits = (uint32_t*)calloc((size_t)nq + 1, 4);
+        m.nmatch = (uint64_t*)calloc((size_t)nq + 1, 8);
+        m.nterms_found = (uint32_t*)calloc((size_t)nq + 1, 4);
+        m.doc = (uint32_t*)calloc((size_t)nq * k + 1, 4);
+        m.score = (double*)calloc((size_t)nq * k + 1, 8);
+        if (!m.nhits || !m.nmatch || !m.nterms_found || !m.doc || !m.score) err = TFIDF_E_NOMEM;
+    }
+    for (uint32_t q = 0; q < nq && !err; ++q) {
+        for (uint64_t x = foff[0][q]; x < foff[0][q + 1]; ++x) {   /* the same term numbering on every rank */
+            bool any = false;
+            for (int r = 0; r < R; ++r) any = any || found[r][x];
+            m.nterms_found[q] += any;
+        }
+        std::vector<size_t> at((size_t)R, 0);   /* R-way merge of the ranks' ordered rows */
+        uint32_t n = 0;
+        for (int r = 0; r < R; ++r) m.nmatch[q] += part[r].nmatch[q];
+        while (n < k) {
+            int best = -1;
+            uint64_t bs = 0;
+            uint32_t bd = 0;
+            for (int r = 0; r < R; ++r) {
+                if (at[r] >= part[r].nhits[q]) continue;
+                uint64_t sb;
+                memcpy(&sb, &part[r].score[(size_t)q * k + at[r]], 8);   /* scores >= +0.0: the bits order like the values */
+                const uint32_t d = part[r].doc[(size_t)q * k + at[r]];
+                if (best < 0 || sb > bs || (sb == bs && d < bd)) { best = r; bs = sb; bd = d; }
+            }
+            if (best < 0) break;
+            m.doc[(size_t)q * k + n] = bd;
+            memcpy(&m.score[(size_t)q * k + n], &bs, 8);
+            ++at[best];
+            ++n;
+        }
+        m.nhits[q] = n;
+    }
+    for (tfidf_hits& h : part) tfidf_hits_free(&h);
+    if (err) {
+        tfidf_hits_free(&m);
+        memset(out, 0, sizeof(*out));
+        return err;
+    }
+    *out = m;
+    return TFIDF_OK;
+}
+
 void tfidf_group_close(tfidf_group* g) {
     if (!g) return;
     for (tfidf_ctx* c : g->ctx)

@@ -334,4 +334,70 @@ int launch_emit_write(const EmitLaunch& e, const uint64_t* doc_text, uint8_t* te
                       uint32_t d1 = 0xFFFFFFFFu);
 int launch_format_f64(const double* v, uint64_t n, uint8_t* out, uint32_t* status, hipStream_t s);
 
+/* ---- top-k retrieval over the resident result (query.hip, tfidf_query) ---- */
+#define QG_MAX        64u      /* queries per scoring pass: one accumulator per lane of the owner wave */
+#define QS_BIG        4096u    /* documents over this many pairs: a workgroup each (K5_MAX_PAIRS's cut) */
+#define QT_SLICE      4096u    /* candidates a top-k workgroup sorts in LDS (> TFIDF_QUERY_MAX_K) */
+#define QUERY_NO_TERM 0xFFFFFFFFu
+/* distinct query terms -> term ranks (QUERY_NO_TERM: not in this shard's vocabulary) */
+struct QLookupArgs {
+    const uint8_t* tbytes;       /* term i = tbytes[toff[i], toff[i + 1]), NUL-free */
+    const uint64_t* toff;
+    uint32_t nterms;
+    const uint4* vkeys;          /* the run's table, read only */
+    const uint64_t* vrep;
+    uint64_t mask;               /* capacity - 1 */
+    uint64_t home;               /* home alignment of the run's inserts (dev_vocab.h): ~1 pairs, ~3 quads */
+    const uint32_t* rank_of_slot;
+    const uint8_t* corpus;       /* long terms' bytes */
+    uint64_t corpus_bytes;
+    uint32_t V;
+    uint32_t* rank_out;
+};
+int launch_query_lookup(const QLookupArgs& a, hipStream_t s);
+/* one group of nq <= QG_MAX queries: gterm = the group's sorted distinct term ranks, term i's
+ * postings (query in the group, weight) at [post_off[i], post_off[i + 1]); acc / cnt are
+ * written for every (query, output position): [nq][ndocs] */
+struct QScoreArgs {
+    const uint64_t* out_off;
+    const uint32_t* out_term;
+    const double* out_score;
+    uint32_t ndocs;
+    uint64_t npairs;
+    const uint32_t* gterm;
+    uint32_t ngterm;
+    const uint32_t* post_off;
+    const uint32_t* post_q;
+    const uint32_t* post_w;
+    uint32_t tab_words;          /* words of the table when it is one block from gterm on (0: it is not) */
+    uint32_t nq;
+    double* acc;
+    uint32_t* cnt;
+    uint32_t* big_list;          /* [ndocs] scratch: output positions of documents over QS_BIG pairs */
+    uint32_t* big_count;
+};
+int launch_query_score(const QScoreArgs& a, uint32_t ncu, hipStream_t s);
+/* one top-k round: per (query, slice of QT_SLICE inputs) the best kk in order.  First round
+ * (acc != null): the inputs are the output positions, hits where cnt != 0, ids through
+ * order / doc_ids (null: index + 1), nmatch[q] += the slice's hits.  Later rounds: in_slices
+ * lists of kk (score bits, id) with in_n valid entries each.  out_*: [nq][out_slices][kk] */
+struct QTopkArgs {
+    const double* acc;
+    const uint32_t* cnt;
+    const uint32_t* order;
+    const uint32_t* doc_ids;
+    const uint64_t* in_s;
+    const uint32_t* in_id;
+    const uint32_t* in_n;
+    uint32_t in_slices;
+    uint64_t n_in;               /* inputs per query: ndocs, or in_slices * kk */
+    uint32_t kk;
+    uint64_t* out_s;
+    uint32_t* out_id;
+    uint32_t* out_n;
+    uint32_t out_slices;         /* ceil(n_in / QT_SLICE) */
+    unsigned long long* nmatch;
+};
+int launch_query_topk(const QTopkArgs& a, uint32_t nq, hipStream_t s);
+
 #endif

@@ -26,7 +26,11 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include <vector>
+
 struct tfidf_ctx;
+struct tfidf_queries;
+struct tfidf_hits;
 
 struct Xport {
     int rank = 0, nranks = 1;
@@ -55,6 +59,11 @@ struct Xport {
 int tfidf_ctx_attach_xport(tfidf_ctx* ctx, Xport* xp);
 int tfidf_ctx_device(const tfidf_ctx* ctx);
 hipStream_t tfidf_ctx_stream(const tfidf_ctx* ctx);
+/* engine.cpp: tfidf_query that also reports which query terms the shard's vocabulary holds:
+ * found[found_off[q] + i] for the i-th distinct term of query q in first-occurrence order
+ * (the same numbering on every rank: tfidf_group_query counts a term found by any rank once) */
+int tfidf_ctx_query(tfidf_ctx* ctx, const tfidf_queries* queries, uint32_t k, tfidf_hits* out,
+                    std::vector<uint8_t>* found, std::vector<uint64_t>* found_off);
 
 /* engine.cpp: hipMalloc counted in tfidf_run_info.device_allocs / device_alloc_bytes */
 hipError_t tfidf_dev_malloc(void** p, size_t bytes);

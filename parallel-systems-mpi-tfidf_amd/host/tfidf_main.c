@@ -18,6 +18,15 @@
  * more than N documents; their outputs are concatenated in shard order.  One shard
  * streams input/ straight into HBM (tfidf_ingest_dir_device).  The work runs on the GPU
  * through libtfidf_hip.so; there is no CPU path.
+ *
+ * Retrieval (beyond the reference, which ends at output.txt):
+ *   --query FILE  every line of FILE (split at '\n' only) is one query, tokenised like a
+ *                 document; after output.txt is written, the best documents of each query go
+ *                 to the hits file as "q<i>\tdoc<N>\t%.16f" lines (i 1-based, score
+ *                 descending, then document id ascending; a query without hits writes nothing);
+ *   --top K       hits per query (default 10, at most TFIDF_QUERY_MAX_K);
+ *   --hits FILE   the hits file (default hits.txt).
+ * With several shards the ranks' hits are merged (tfidf_group_query).
  */
 #include <dirent.h>
 #include <pthread.h>
@@ -53,6 +62,75 @@ static int debug_jobs(tfidf_ctx* ctx) {
     tfidf_print_jobs(&r);
     tfidf_result_free(&r);
     return TFIDF_OK;
+}
+
+/* ---------------------------------------------------------------- queries -- */
+
+static struct {
+    const char* file;   /* NULL: no retrieval, behaviour and bytes as without the option */
+    const char* hits;
+    uint32_t top;
+} g_query = {NULL, "hits.txt", 10};
+
+/* the query file's lines as one batch (tfidf_queries): q_off at the line starts */
+static int load_queries(uint8_t** bytes, uint64_t* nbytes, uint64_t** off, uint32_t* nq) {
+    FILE* f = fopen(g_query.file, "rb");
+    if (!f) return TFIDF_E_NOINPUT;
+    size_t cap = 1 << 16, n = 0;
+    uint8_t* b = (uint8_t*)malloc(cap);
+    for (;;) {
+        if (!b) { fclose(f); return TFIDF_E_NOMEM; }
+        const size_t got = fread(b + n, 1, cap - n, f);
+        n += got;
+        if (got == 0) break;
+        if (n == cap) { cap *= 2; b = (uint8_t*)realloc(b, cap); }
+    }
+    fclose(f);
+    size_t lines = 0;
+    for (size_t i = 0; i < n; ++i) lines += b[i] == '\n';
+    if (n && b[n - 1] != '\n') ++lines;   /* a last line without its newline */
+    if (lines > TFIDF_QUERY_MAX_QUERIES) { free(b); return TFIDF_E_INVAL; }
+    uint64_t* o = (uint64_t*)malloc((lines + 1) * sizeof(uint64_t));
+    if (!o) { free(b); return TFIDF_E_NOMEM; }
+    size_t q = 0;
+    o[0] = 0;
+    for (size_t i = 0; i < n; ++i)
+        if (b[i] == '\n') o[++q] = i + 1;   /* the newline stays in its query: whitespace */
+    if (q < lines) o[++q] = n;
+    *bytes = b;
+    *nbytes = n;
+    *off = o;
+    *nq = (uint32_t)lines;
+    return TFIDF_OK;
+}
+
+/* --query: ranks the resident result of ctx (one shard) or of every rank of g */
+static int run_queries(tfidf_ctx* ctx, tfidf_group* g) {
+    if (!g_query.file) return TFIDF_OK;
+    tfidf_queries qs;
+    uint64_t* off = NULL;
+    uint8_t* bytes = NULL;
+    memset(&qs, 0, sizeof(qs));
+    int rc = load_queries(&bytes, &qs.nbytes, &off, &qs.nqueries);
+    if (rc == TFIDF_E_NOINPUT) { printf("Error Opening File: %s\n", g_query.file); return TFIDF_OK; }
+    if (rc) return rc;
+    qs.bytes = bytes;
+    qs.q_off = off;
+    tfidf_hits h;
+    memset(&h, 0, sizeof(h));
+    rc = g ? tfidf_group_query(g, &qs, g_query.top, &h) : tfidf_query(ctx, &qs, g_query.top, &h);
+    if (!rc) {
+        FILE* f = fopen(g_query.hits, "w");
+        if (!f) printf("Error Opening File: %s\n", g_query.hits);
+        for (uint32_t q = 0; f && q < h.nqueries; ++q)
+            for (uint32_t i = 0; i < h.nhits[q]; ++i)
+                fprintf(f, "q%u\tdoc%u\t%.16f\n", q + 1, h.doc[(size_t)q * h.k + i], h.score[(size_t)q * h.k + i]);
+        if (f && fclose(f) != 0) rc = TFIDF_E_OUTPUT;
+    }
+    tfidf_hits_free(&h);
+    free(bytes);
+    free(off);
+    return rc;
 }
 
 /* ------------------------------------------------------------- one shard -- */
@@ -96,7 +174,9 @@ static int run_single(int device, const char* indir, const char* outpath, int de
                 ii.ms_total > 0 ? ii.nbytes / ii.ms_total / 1e6 : 0.0, ri.ms_total, (unsigned long long)ri.npairs,
                 out_ms, (unsigned long long)oi.text_bytes, oi.ms_prepare, oi.ms_d2h_busy, oi.ms_write, oi.writers);
     }
+    rc = run_queries(ctx, NULL);
     tfidf_close(ctx);
+    if (rc) return fail(rc);
     return 0;
 }
 
@@ -192,8 +272,10 @@ static int run_sharded(int ngpus, int nshards, const char* indir, const char* ou
                 plan.ndocs, (unsigned long long)bytes, nshards, ngpus, t_open - t0, t_ingest - t_open, t_run - t_ingest,
                 (unsigned long long)pairs, wall_ms() - t_run);
     }
+    rc = run_queries(NULL, g);
     tfidf_group_close(g);
     tfidf_plan_free(&plan);
+    if (rc) return fail(rc);
     free(dev);
     free(jobs);
     free(th);
@@ -213,9 +295,16 @@ int main(int argc, char** argv) {
         else if (!strcmp(argv[i], "--shards") && i + 1 < argc) nshards = atoi(argv[++i]);
         else if (!strcmp(argv[i], "--input") && i + 1 < argc) indir = argv[++i];
         else if (!strcmp(argv[i], "--output") && i + 1 < argc) outpath = argv[++i];
+        else if (!strcmp(argv[i], "--query") && i + 1 < argc) g_query.file = argv[++i];
+        else if (!strcmp(argv[i], "--hits") && i + 1 < argc) g_query.hits = argv[++i];
+        else if (!strcmp(argv[i], "--top") && i + 1 < argc) {
+            const long k = atol(argv[++i]);
+            if (k < 1 || k > (long)TFIDF_QUERY_MAX_K) { fprintf(stderr, "tfidf: --top takes 1..%u\n", TFIDF_QUERY_MAX_K); return 2; }
+            g_query.top = (uint32_t)k;
+        }
         else {
             fprintf(stderr, "usage: tfidf [--debug-jobs] [--stats] [--gpus N] [--shards K] [--device D] "
-                            "[--input DIR] [--output FILE]\n");
+                            "[--input DIR] [--output FILE] [--query FILE [--top K] [--hits FILE]]\n");
             return 2;
         }
     }

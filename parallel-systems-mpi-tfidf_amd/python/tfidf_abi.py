@@ -38,7 +38,11 @@ EXPORTS = [
     "tfidf_group_run", "tfidf_group_write_output", "tfidf_group_close", "tfidf_plan_dir", "tfidf_plan_free",
     "tfidf_ingest_shard_device", "tfidf_doc_name_order", "tfidf_shard_split", "tfidf_device_count",
     "tfidf_last_output_info", "tfidf_run_totals_get",
+    "tfidf_query", "tfidf_hits_free", "tfidf_group_query", "tfidf_last_query_info",
 ]
+QUERY_MAX_K = 1024  # TFIDF_QUERY_MAX_K
+E_INVAL = -1
+E_STATE = -10
 TFIDF_GROUP_LOCAL = 1
 E_PEER = -11
 
@@ -82,6 +86,27 @@ class OutputInfo(C.Structure):
     _fields_ = [
         ("size", C.c_uint64), ("text_bytes", C.c_uint64), ("writers", C.c_uint32), ("formatted", C.c_uint32),
         ("ms_prepare", C.c_double), ("ms_d2h_busy", C.c_double), ("ms_write", C.c_double), ("ms_total", C.c_double),
+    ]
+
+
+class Queries(C.Structure):
+    _fields_ = [("bytes", C.c_void_p), ("nbytes", C.c_uint64), ("q_off", C.c_void_p), ("nqueries", C.c_uint32)]
+
+
+class Hits(C.Structure):
+    _fields_ = [
+        ("nqueries", C.c_uint32), ("k", C.c_uint32), ("nhits", C.POINTER(C.c_uint32)),
+        ("nmatch", C.POINTER(C.c_uint64)), ("nterms_found", C.POINTER(C.c_uint32)),
+        ("doc", C.POINTER(C.c_uint32)), ("score", C.POINTER(C.c_double)),
+    ]
+
+
+class QueryInfo(C.Structure):
+    _fields_ = [
+        ("size", C.c_uint64), ("nqueries", C.c_uint32), ("k", C.c_uint32), ("nterms", C.c_uint32),
+        ("nterms_found", C.c_uint32), ("ngroups", C.c_uint32), ("group_queries", C.c_uint32),
+        ("acc_bytes", C.c_uint64), ("ms_lookup", C.c_double), ("ms_score", C.c_double), ("ms_topk", C.c_double),
+        ("ms_total", C.c_double),
     ]
 
 
@@ -152,6 +177,11 @@ def lib() -> C.CDLL:
                                                 C.POINTER(Corpus), C.POINTER(C.c_uint32), C.POINTER(IngestInfo)]
         L.tfidf_doc_name_order.argtypes = [C.c_uint32, C.c_void_p]
         L.tfidf_shard_split.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
+        L.tfidf_query.argtypes = [C.c_void_p, C.POINTER(Queries), C.c_uint32, C.POINTER(Hits)]
+        L.tfidf_group_query.argtypes = [C.c_void_p, C.POINTER(Queries), C.c_uint32, C.POINTER(Hits)]
+        L.tfidf_hits_free.argtypes = [C.POINTER(Hits)]
+        L.tfidf_hits_free.restype = None
+        L.tfidf_last_query_info.argtypes = [C.c_void_p, C.POINTER(QueryInfo)]
         if L.tfidf_abi_version() != ABI_VERSION:
             raise RuntimeError(f"{LIB_PATH}: ABI version {L.tfidf_abi_version()}, binding expects {ABI_VERSION} "
                                f"(stale build: rebuild with __graft_entry__.build())")
@@ -172,6 +202,35 @@ def _chk(rc: int, what: str) -> None:
 
 def _ptr(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
+
+
+def _query(fn, handle, queries, k: int, what: str) -> dict:
+    """One batch through tfidf_query / tfidf_group_query: queries are bytes objects."""
+    data = np.frombuffer(b"".join(queries), dtype=np.uint8)
+    off = np.zeros(len(queries) + 1, dtype=np.uint64)
+    if len(queries):
+        off[1:] = np.cumsum([len(q) for q in queries], dtype=np.uint64)
+    qs = Queries()
+    qs.bytes = data.ctypes.data if len(data) else None
+    qs.nbytes = len(data)
+    qs.q_off = off.ctypes.data
+    qs.nqueries = len(queries)
+    h = Hits()
+    _chk(fn(handle, C.byref(qs), k, C.byref(h)), what)
+    try:
+        nq = int(h.nqueries)
+
+        def arr(p, n, dt):
+            return np.ctypeslib.as_array(p, shape=(n,)).astype(dt, copy=True) if n else np.zeros(0, dtype=dt)
+
+        return {
+            "k": int(h.k), "nhits": arr(h.nhits, nq, np.uint32), "nmatch": arr(h.nmatch, nq, np.uint64),
+            "nterms_found": arr(h.nterms_found, nq, np.uint32),
+            "doc": arr(h.doc, nq * k, np.uint32).reshape(nq, k),
+            "score": arr(h.score, nq * k, np.float64).reshape(nq, k),
+        }
+    finally:
+        lib().tfidf_hits_free(C.byref(h))
 
 
 def synth_host(seed: int, V: int, mode: int, cdf, doc_ids, ntok):
@@ -329,6 +388,20 @@ class Engine:
         _chk(lib().tfidf_format_f64(self.h, v.ctypes.data, v.size, out.ctypes.data), "tfidf_format_f64")
         return [bytes(out[i * 32:(i + 1) * 32]).rstrip(b"\0") for i in range(v.size)]
 
+    def query(self, queries, k: int = 10) -> dict:
+        """Top-k documents of this shard for every query (tfidf_query).  queries: bytes
+        objects, tokenised like documents.  Returns numpy arrays nhits[nq], nmatch[nq],
+        nterms_found[nq], doc[nq, k] (global ids) and score[nq, k]; rows are valid up to
+        nhits."""
+        return _query(lib().tfidf_query, self.h, queries, k, "tfidf_query")
+
+    def query_info(self) -> dict:
+        """Counters and device times of the last query (tfidf_last_query_info)."""
+        q = QueryInfo()
+        q.size = C.sizeof(QueryInfo)
+        _chk(lib().tfidf_last_query_info(self.h, C.byref(q)), "tfidf_last_query_info")
+        return {k: getattr(q, k) for k, _ in QueryInfo._fields_ if k != "size"}
+
     @contextlib.contextmanager
     def fetched(self):
         """The last run's result as numpy views of the library's host arrays (tfidf_fetch
@@ -433,6 +506,10 @@ class Group:
 
     def write_output(self, path: str):
         _chk(lib().tfidf_group_write_output(self.h, path.encode()), "tfidf_group_write_output")
+
+    def query(self, queries, k: int = 10) -> dict:
+        """Top-k documents over all shards (tfidf_group_query); see Engine.query."""
+        return _query(lib().tfidf_group_query, self.h, queries, k, "tfidf_group_query")
 
 
 def plan_dir(path: str, nshards: int, threads: int = 0) -> dict:
