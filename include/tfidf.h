@@ -344,6 +344,70 @@ typedef struct tfidf_query_info {
 } tfidf_query_info;
 int tfidf_last_query_info(const tfidf_ctx* ctx, tfidf_query_info* info);
 
+/* ---------------------------------------------------------------- keywords -- */
+
+/* Per-document top-k keyword extraction over the resident result of the last run: the k
+ * best-scoring words of each document, read where tfidf_run left the scores.
+ *
+ * The keywords of document d are its pairs (TFIDF.c:202,243-245), one per distinct term of d.
+ *   order        score descending, then term ascending in term-table order: the strcmp order
+ *                of "word\t" (TFIDF.c:245,273), which is the order of tfidf_result.pair_term
+ *                inside a document, so it equals pair position ascending
+ *   cut          the first k pairs are returned
+ *   zero scores  a pair with score +0.0 (df = N, TFIDF.c:243) is a pair like any other and
+ *                sorts last
+ *   scores       the run's pair_score, bit for bit: no arithmetic
+ * Scores are >= +0.0 and finite, so their bit patterns order like the values, and a term
+ * occurs at most once in a document (TFIDF.c:154,163 count it): the order is total and the
+ * result unique.  Equal scores at the cut are the normal case (same count and df). */
+#define TFIDF_TERMS_MAX_K 1024u
+/* Arrays are owned by the library and released by tfidf_doc_terms_free(). */
+typedef struct tfidf_doc_terms {
+    uint32_t  ndocs, k;      /* rows, row stride */
+    uint32_t* doc;           /* per row: global document id */
+    uint32_t* pos;           /* per row: the document's output position (index into the "docN@" order); UINT32_MAX: not in this shard */
+    uint64_t* npairs;        /* per row: pairs of the document (all, before the cut) */
+    uint32_t* nterms;        /* per row: min(k, npairs) */
+    uint32_t* term;          /* ndocs * k, row r at r * k: term rank = tfidf_result.pair_term */
+    uint32_t* count;         /* wordCount (TFIDF.c:154,163) */
+    double*   score;
+    uint64_t* pair;          /* index of the pair in output order (tfidf_result.pair_*) */
+    uint64_t* word_off;      /* ndocs * k + 1: entry r * k + j is bytes [word_off[..], word_off[.. + 1]); unused entries empty */
+    uint8_t*  word_bytes;    /* the selected words' bytes, gathered on the device */
+} tfidf_doc_terms;
+/* doc_ids == NULL: ndocs is ignored; one row per document of this context in output order
+ * ("docN@" order), empty documents included.  doc_ids != NULL: one row per entry in the
+ * caller's order, duplicates allowed; an id this shard does not hold gives pos = UINT32_MAX
+ * and npairs = nterms = 0.  TFIDF_E_STATE before a successful tfidf_run; TFIDF_E_INVAL for a
+ * NULL ctx or out, k == 0 or k > TFIDF_TERMS_MAX_K.  The run's result is not disturbed, and the
+ * run's corpus must still be valid, as for tfidf_format (long terms' bytes are read from it).
+ * With a communicator attached the call is local to the context.  Rows are processed in
+ * batches whose device result buffers (32 bytes per entry; the gathered words come on top)
+ * stay under TFIDF_TERMS_MB (read at tfidf_open, default 256) MiB; the buffers belong to the
+ * context, so a repeated identical call allocates nothing (tfidf_alloc_stats). */
+int tfidf_top_terms(tfidf_ctx* ctx, const uint32_t* doc_ids, uint32_t ndocs, uint32_t k, tfidf_doc_terms* out);
+void tfidf_doc_terms_free(tfidf_doc_terms* t);
+/* The same over every shard of a group (tfidf_group_run).  NULL list: the ranks' rows in rank
+ * order, which is the global "docN@" order for the contiguous shards tfidf_group_run
+ * requires.  Id list: every rank looks the ids up on its own host thread and each row comes
+ * from the rank that holds the id; an id that no rank holds stays UINT32_MAX.  pos and pair
+ * count from the first rank's first document and pair (the concatenated output); term is the
+ * rank in the holding shard's own term table. */
+int tfidf_group_top_terms(tfidf_group* g, const uint32_t* doc_ids, uint32_t ndocs, uint32_t k, tfidf_doc_terms* out);
+/* Counters of the last tfidf_top_terms (the caller sets `size` = sizeof, as tfidf_query_info). */
+typedef struct tfidf_terms_info {
+    uint64_t size;
+    uint32_t ndocs, k;
+    uint32_t nbatches;        /* batches of rows */
+    uint32_t big_docs;        /* rows of documents over 4096 pairs (the workgroup kernel) */
+    uint64_t out_bytes;       /* bytes copied to the host */
+    double   ms_lookup;       /* device times (HIP events), summed over the batches */
+    double   ms_select;
+    double   ms_words;
+    double   ms_total;        /* host wall time of the whole call */
+} tfidf_terms_info;
+int tfidf_last_terms_info(const tfidf_ctx* ctx, tfidf_terms_info* info);
+
 /* ---------------------------------------------------------------- ingest ---- */
 
 /* Reference input contract (TFIDF.c:98-110,130-147): N = number of entries of `dir`

@@ -241,6 +241,15 @@ struct tfidf_ctx {
     hipEvent_t ev_q[3] = {};                    /* lookup / score / top-k bounds (created by the first query) */
     uint32_t ncu = 0;
     tfidf_query_info qinfo{};
+    /* per-document top-k terms (tfidf_top_terms, terms.hip): the requested ids and their output
+     * positions, a batch's per-row words (npairs, nterms, id), its k entries per row (score
+     * bits, pair, term, count, word length -> offset), the gathered words, the list of long
+     * documents */
+    DevBuf tm_ids, tm_rows, tm_score, tm_pair, tm_term, tm_cnt, tm_woff, tm_words, tm_big;
+    uint64_t terms_bytes = 256ull << 20;        /* env TFIDF_TERMS_MB: device result buffers of a batch of rows */
+    hipEvent_t ev_t[5] = {};                    /* lookup or select / scan / gather bounds (created by the first call) */
+    bool tmeta_valid = false;                   /* t_key / t_len hold this run's term metadata */
+    tfidf_terms_info tinfo{};
 #define WR_NBUF 8
 #define WR_BUF (16ull << 20)
 #define WR_GROUPS 8
@@ -425,6 +434,11 @@ int tfidf_open(int device, tfidf_ctx** out) {
         const unsigned long long mb = strtoull(kq, nullptr, 0);
         if (mb >= 1 && mb <= (1ull << 20)) ctx->query_acc_bytes = mb << 20;
     }
+    const char* kt = getenv("TFIDF_TERMS_MB");
+    if (kt) {
+        const unsigned long long mb = strtoull(kt, nullptr, 0);
+        if (mb >= 1 && mb <= (1ull << 20)) ctx->terms_bytes = mb << 20;
+    }
     const char* kn = getenv("TFIDF_TEST_XNOMEM_RANK");
     ctx->xnomem_rank = kn ? atoi(kn) : -1;
     /* diagnostics: initial vocabulary capacity (power of two) and the loads it may reach
@@ -499,6 +513,11 @@ void tfidf_close(tfidf_ctx* ctx) {
         if (e) (void)hipEventDestroy(e);
     for (DevBuf* b : {&ctx->q_terms, &ctx->q_rank, &ctx->q_tab, &ctx->q_acc, &ctx->q_cnt, &ctx->q_big, &ctx->q_cand0,
                       &ctx->q_cand1, &ctx->q_misc})
+        b->release();
+    for (hipEvent_t e : ctx->ev_t)
+        if (e) (void)hipEventDestroy(e);
+    for (DevBuf* b : {&ctx->tm_ids, &ctx->tm_rows, &ctx->tm_score, &ctx->tm_pair, &ctx->tm_term, &ctx->tm_cnt, &ctx->tm_woff,
+                      &ctx->tm_words, &ctx->tm_big})
         b->release();
     DevBuf* bufs[] = {&ctx->arena_buf, &ctx->in_bytes, &ctx->in_off, &ctx->in_ids, &ctx->syn_bytes, &ctx->syn_off,
                       &ctx->syn_ids, &ctx->syn_ntok, &ctx->syn_blkfirst, &ctx->syn_blkbytes, &ctx->syn_cdf,
@@ -1714,6 +1733,7 @@ extern "C" int tfidf_run(tfidf_ctx* ctx, const tfidf_corpus* in) {
     ctx->have_result = false;
     ctx->have_info = false;
     ctx->text_valid = false;
+    ctx->tmeta_valid = false;
     CorpusDev c{};
     const uint32_t* dev_ids = nullptr;
     uint64_t Nt = 0;
@@ -2086,6 +2106,7 @@ static int format_prepare(tfidf_ctx* ctx, EmitLaunch& e, uint64_t& total) {
     if (launch_term_meta(ctx->vkeys.as<uint4>(), ctx->vrep.as<uint64_t>(), ctx->slot_of_rank.as<uint32_t>(), V,
                          ctx->t_key.as<uint4>(), ctx->t_len.as<uint32_t>(), s))
         return TFIDF_E_HIP;
+    ctx->tmeta_valid = true;
     e = EmitLaunch{ctx->order, ctx->dev_ids, ctx->out_off.as<uint64_t>(), ctx->out_term.as<uint32_t>(),
                    ctx->out_score.as<double>(), ctx->t_key.as<uint4>(), ctx->t_len.as<uint32_t>(), ctx->dev_bytes, N,
                    status};
@@ -2616,6 +2637,199 @@ extern "C" int tfidf_last_query_info(const tfidf_ctx* ctx, tfidf_query_info* inf
     if (!ctx || !info || info->size < sizeof(uint64_t)) return TFIDF_E_INVAL;
     const uint64_t n = info->size < sizeof(tfidf_query_info) ? info->size : sizeof(tfidf_query_info);
     tfidf_query_info o = ctx->qinfo;
+    o.size = n;
+    memcpy(info, &o, (size_t)n);
+    return TFIDF_OK;
+}
+
+/* ---------------------------------------------------------------- keywords ----
+ * Per-document top-k terms over the resident result (terms.hip).  The rows (every output
+ * position, or the positions of the requested ids) are cut into batches whose device result
+ * buffers stay under the context's budget; a batch is one selection pass, a scan of the
+ * selected words' lengths and a gather of their bytes, copied straight into the caller's
+ * arrays.  Nothing of the run's result is written. */
+
+extern "C" void tfidf_doc_terms_free(tfidf_doc_terms* t) {
+    if (!t) return;
+    free(t->doc); free(t->pos); free(t->npairs); free(t->nterms); free(t->term); free(t->count);
+    free(t->score); free(t->pair); free(t->word_off); free(t->word_bytes);
+    memset(t, 0, sizeof(*t));
+}
+
+extern "C" int tfidf_top_terms(tfidf_ctx* ctx, const uint32_t* doc_ids, uint32_t ndocs, uint32_t k, tfidf_doc_terms* out) {
+    if (!ctx || !out) return TFIDF_E_INVAL;
+    if (k == 0 || k > TFIDF_TERMS_MAX_K) return TFIDF_E_INVAL;
+    if (!ctx->have_result) return TFIDF_E_STATE;
+    const auto wall0 = std::chrono::steady_clock::now();
+    HIPCHK(hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    for (hipEvent_t& e : ctx->ev_t)
+        if (!e) HIPCHK(hipEventCreate(&e));
+    if (!ctx->ncu) {
+        int n = 0;
+        if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, ctx->device) != hipSuccess || n <= 0) n = 256;
+        ctx->ncu = (uint32_t)n;
+    }
+    const uint32_t N = ctx->ndocs, V = ctx->V;
+    const uint32_t R = doc_ids ? ndocs : N;
+    const size_t RK = (size_t)R * k;
+    memset(out, 0, sizeof(*out));
+    out->ndocs = R;
+    out->k = k;
+    out->doc = (uint32_t*)calloc((size_t)R + 1, 4);
+    out->pos = (uint32_t*)calloc((size_t)R + 1, 4);
+    out->npairs = (uint64_t*)calloc((size_t)R + 1, 8);
+    out->nterms = (uint32_t*)calloc((size_t)R + 1, 4);
+    out->term = (uint32_t*)calloc(RK + 1, 4);
+    out->count = (uint32_t*)calloc(RK + 1, 4);
+    out->score = (double*)calloc(RK + 1, 8);
+    out->pair = (uint64_t*)calloc(RK + 1, 8);
+    out->word_off = (uint64_t*)calloc(RK + 1, 8);
+    out->word_bytes = (uint8_t*)calloc(1, 1);
+    struct TermsGuard {   /* an error return leaves *out zeroed */
+        tfidf_doc_terms* t;
+        ~TermsGuard() { if (t) tfidf_doc_terms_free(t); }
+    } guard{out};
+    if (!out->doc || !out->pos || !out->npairs || !out->nterms || !out->term || !out->count || !out->score ||
+        !out->pair || !out->word_off || !out->word_bytes)
+        return TFIDF_E_NOMEM;
+    tfidf_terms_info ti{};
+    ti.ndocs = R;
+    ti.k = k;
+    float ms = 0;
+
+    /* ---- the selected words' lengths and byte sources: the formatter's term metadata ---- */
+    if (V && !ctx->tmeta_valid) {
+        ENSURE(ctx->t_key, (size_t)V * 16 + 16);
+        ENSURE(ctx->t_len, (size_t)V * 4 + 4);
+        if (launch_term_meta(ctx->vkeys.as<uint4>(), ctx->vrep.as<uint64_t>(), ctx->slot_of_rank.as<uint32_t>(), V,
+                             ctx->t_key.as<uint4>(), ctx->t_len.as<uint32_t>(), s))
+            return TFIDF_E_HIP;
+        ctx->tmeta_valid = true;
+    }
+
+    /* ---- lookup: one lane per requested id ---- */
+    const uint32_t* d_pos = nullptr;
+    if (doc_ids && R) {
+        ENSURE(ctx->tm_ids, (size_t)R * 8 + 8);
+        uint32_t* d_ids = ctx->tm_ids.as<uint32_t>();
+        HIPCHK(hipMemcpyAsync(d_ids, doc_ids, (size_t)R * 4, hipMemcpyHostToDevice, s));
+        TLookupArgs la{d_ids, R, ctx->order, ctx->dev_ids, N, d_ids + R};
+        HIPCHK(hipEventRecord(ctx->ev_t[0], s));
+        if (launch_terms_lookup(la, s)) { HIPCHK(hipGetLastError()); return TFIDF_E_HIP; }
+        HIPCHK(hipEventRecord(ctx->ev_t[1], s));
+        HIPCHK(hipMemcpyAsync(out->pos, d_ids + R, (size_t)R * 4, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        (void)hipEventElapsedTime(&ms, ctx->ev_t[0], ctx->ev_t[1]);
+        ti.ms_lookup = ms;
+        d_pos = d_ids + R;
+        ti.out_bytes += (uint64_t)R * 4;
+    } else {
+        for (uint32_t r = 0; r < R; ++r) out->pos[r] = r;
+    }
+
+    /* ---- batches of rows under the budget: 32 bytes per entry, 20 per row ---- */
+    const uint64_t per_row = (uint64_t)k * 32 + 20;
+    uint64_t B = ctx->terms_bytes / per_row;
+    B = B < 1 ? 1 : B;
+    if (B > R) B = R;
+    const size_t BK = (size_t)B * k;
+    if (R) {
+        ENSURE(ctx->tm_rows, (size_t)B * 16 + 16);
+        ENSURE(ctx->tm_score, BK * 8 + 8);
+        ENSURE(ctx->tm_pair, BK * 8 + 8);
+        ENSURE(ctx->tm_term, BK * 4 + 4);
+        ENSURE(ctx->tm_cnt, BK * 4 + 4);
+        ENSURE(ctx->tm_woff, BK * 8 + 16);
+        ENSURE(ctx->tm_big, (size_t)B * 4 + 16);
+    }
+    std::vector<uint64_t> h_woff(BK + 1);
+    std::vector<uint32_t> h_doc(B);
+    uint64_t wbase = 0;
+    for (uint64_t r0 = 0; r0 < R; r0 += B) {
+        const uint32_t nb = (uint32_t)(R - r0 < B ? R - r0 : B);
+        const size_t nbk = (size_t)nb * k;
+        ++ti.nbatches;
+        TSelArgs sa{};
+        sa.out_off = ctx->out_off.as<uint64_t>();
+        sa.out_term = ctx->out_term.as<uint32_t>();
+        sa.out_cnt = ctx->out_cnt.as<uint32_t>();
+        sa.out_score = ctx->out_score.as<double>();
+        sa.order = ctx->order;
+        sa.doc_ids = ctx->dev_ids;
+        sa.tlen = ctx->t_len.as<uint32_t>();
+        sa.ndocs = N;
+        sa.nterms = V;
+        sa.npairs = ctx->npairs;
+        sa.pos = d_pos;
+        sa.row0 = (uint32_t)r0;
+        sa.nrows = nb;
+        sa.k = k;
+        sa.rnpairs = ctx->tm_rows.as<uint64_t>();
+        sa.rnterms = (uint32_t*)(sa.rnpairs + B);
+        sa.rdoc = sa.rnterms + B;
+        sa.score = ctx->tm_score.as<uint64_t>();
+        sa.pair = ctx->tm_pair.as<uint64_t>();
+        sa.term = ctx->tm_term.as<uint32_t>();
+        sa.cnt = ctx->tm_cnt.as<uint32_t>();
+        sa.wlen = ctx->tm_woff.as<uint64_t>();
+        sa.big_list = ctx->tm_big.as<uint32_t>();
+        sa.big_count = sa.big_list + B;
+        HIPCHK(hipEventRecord(ctx->ev_t[0], s));
+        if (launch_terms_select(sa, ctx->ncu, s)) { HIPCHK(hipGetLastError()); return TFIDF_E_HIP; }
+        HIPCHK(hipEventRecord(ctx->ev_t[1], s));
+        /* word lengths -> offsets inside the batch, in place; [nbk] = the batch's word bytes */
+        ctx->arena.used = 0;   /* as format_prepare: nothing of the result lives in the arena */
+        const int sc = scan_excl_u64(sa.wlen, sa.wlen, nbk, ctx->arena, s);
+        if (sc) { if (sc != -2) HIPCHK(hipGetLastError()); return sc == -2 ? TFIDF_E_NOMEM : TFIDF_E_HIP; }
+        HIPCHK(hipEventRecord(ctx->ev_t[2], s));
+        uint32_t nbig = 0;
+        HIPCHK(hipMemcpyAsync(h_woff.data(), sa.wlen, (nbk + 1) * 8, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(&nbig, sa.big_count, 4, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        const uint64_t wtotal = h_woff[nbk];
+        ENSURE(ctx->tm_words, wtotal + 16);
+        TWordArgs wa{sa.term, sa.wlen, nbk, ctx->t_key.as<uint4>(), V, ctx->dev_bytes, ctx->corpus.nbytes,
+                     ctx->tm_words.as<uint8_t>()};
+        HIPCHK(hipEventRecord(ctx->ev_t[3], s));
+        if (launch_terms_words(wa, s)) { HIPCHK(hipGetLastError()); return TFIDF_E_HIP; }
+        HIPCHK(hipEventRecord(ctx->ev_t[4], s));
+        uint8_t* wb = (uint8_t*)realloc(out->word_bytes, (size_t)(wbase + wtotal) + 1);
+        if (!wb) return TFIDF_E_NOMEM;
+        out->word_bytes = wb;
+        const size_t e0 = (size_t)r0 * k;
+        HIPCHK(hipMemcpyAsync(out->npairs + r0, sa.rnpairs, (size_t)nb * 8, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(out->nterms + r0, sa.rnterms, (size_t)nb * 4, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(h_doc.data(), sa.rdoc, (size_t)nb * 4, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(out->score + e0, sa.score, nbk * 8, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(out->pair + e0, sa.pair, nbk * 8, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(out->term + e0, sa.term, nbk * 4, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(out->count + e0, sa.cnt, nbk * 4, hipMemcpyDeviceToHost, s));
+        if (wtotal) HIPCHK(hipMemcpyAsync(wb + wbase, ctx->tm_words.p, wtotal, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        (void)hipEventElapsedTime(&ms, ctx->ev_t[0], ctx->ev_t[1]);
+        ti.ms_select += ms;
+        (void)hipEventElapsedTime(&ms, ctx->ev_t[1], ctx->ev_t[2]);
+        ti.ms_words += ms;
+        (void)hipEventElapsedTime(&ms, ctx->ev_t[3], ctx->ev_t[4]);
+        ti.ms_words += ms;
+        ti.big_docs += nbig < nb ? nbig : nb;
+        ti.out_bytes += (uint64_t)nb * 16 + nbk * 32 + wtotal;
+        for (uint32_t i = 0; i < nb; ++i) out->doc[r0 + i] = doc_ids ? doc_ids[r0 + i] : h_doc[i];
+        for (size_t i = 0; i < nbk; ++i) out->word_off[e0 + i] = wbase + h_woff[i];
+        wbase += wtotal;
+    }
+    out->word_off[RK] = wbase;
+    ti.ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - wall0).count();
+    ctx->tinfo = ti;
+    guard.t = nullptr;
+    return TFIDF_OK;
+}
+
+extern "C" int tfidf_last_terms_info(const tfidf_ctx* ctx, tfidf_terms_info* info) {
+    if (!ctx || !info || info->size < sizeof(uint64_t)) return TFIDF_E_INVAL;
+    const uint64_t n = info->size < sizeof(tfidf_terms_info) ? info->size : sizeof(tfidf_terms_info);
+    tfidf_terms_info o = ctx->tinfo;
     o.size = n;
     memcpy(info, &o, (size_t)n);
     return TFIDF_OK;

@@ -651,6 +651,118 @@ int tfidf_group_query(tfidf_group* g, const tfidf_queries* queries, uint32_t k, 
     return TFIDF_OK;
 }
 
+/* Every rank selects on its own host thread (tfidf_top_terms is local to a context).  NULL
+ * list: the ranks' rows are concatenated in rank order.  Id list: every rank looks up every
+ * id and row r is taken from the first rank that holds it.  pos and pair are moved by the
+ * documents and pairs of the ranks before the holder. */
+int tfidf_group_top_terms(tfidf_group* g, const uint32_t* doc_ids, uint32_t ndocs, uint32_t k, tfidf_doc_terms* out) {
+    if (!g || !out) return TFIDF_E_INVAL;
+    const int R = g->n;
+    std::vector<int> rc((size_t)R, TFIDF_OK);
+    std::vector<tfidf_doc_terms> part((size_t)R);
+    for (tfidf_doc_terms& p : part) memset(&p, 0, sizeof(p));
+    {
+        std::vector<std::thread> th;
+        for (int r = 1; r < R; ++r) th.emplace_back([&, r] { rc[r] = tfidf_top_terms(g->ctx[r], doc_ids, ndocs, k, &part[r]); });
+        rc[0] = tfidf_top_terms(g->ctx[0], doc_ids, ndocs, k, &part[0]);
+        for (auto& t : th) t.join();
+    }
+    int err = TFIDF_OK;
+    for (int r = 0; r < R && !err; ++r) err = rc[r];
+    /* where each rank's documents and pairs start in the concatenated output */
+    std::vector<uint64_t> doc0((size_t)R + 1, 0), pair0((size_t)R + 1, 0);
+    for (int r = 0; r < R && !err; ++r) {
+        tfidf_run_info ri;
+        memset(&ri, 0, sizeof(ri));
+        ri.size = sizeof(ri);
+        err = tfidf_last_run_info(g->ctx[r], &ri);
+        doc0[r + 1] = doc0[r] + ri.ndocs;
+        pair0[r + 1] = pair0[r] + ri.npairs;
+    }
+    /* (rank, row in the rank's part) of every output row; rank -1: no rank holds the id */
+    std::vector<int> src_rank;
+    std::vector<uint32_t> src_row;
+    if (!err) {
+        if (!doc_ids) {
+            for (int r = 0; r < R; ++r)
+                for (uint32_t i = 0; i < part[r].ndocs; ++i) { src_rank.push_back(r); src_row.push_back(i); }
+        } else {
+            for (uint32_t i = 0; i < ndocs; ++i) {
+                int h = -1;
+                for (int r = 0; r < R && h < 0; ++r)
+                    if (part[r].pos[i] != UINT32_MAX) h = r;
+                src_rank.push_back(h);
+                src_row.push_back(i);
+            }
+        }
+        if (src_rank.size() > 0xFFFFFFFFull) err = TFIDF_E_CAPACITY;
+    }
+    tfidf_doc_terms m;
+    memset(&m, 0, sizeof(m));
+    const size_t nr = src_rank.size(), nrk = nr * k;
+    uint64_t wtotal = 0;
+    if (!err) {
+        for (size_t i = 0; i < nr; ++i)
+            if (src_rank[i] >= 0) {
+                const tfidf_doc_terms& p = part[src_rank[i]];
+                const size_t e = (size_t)src_row[i] * k;
+                wtotal += p.word_off[e + k] - p.word_off[e];
+            }
+        m.ndocs = (uint32_t)nr;
+        m.k = k;
+        m.doc = (uint32_t*)calloc(nr + 1, 4);
+        m.pos = (uint32_t*)calloc(nr + 1, 4);
+        m.npairs = (uint64_t*)calloc(nr + 1, 8);
+        m.nterms = (uint32_t*)calloc(nr + 1, 4);
+        m.term = (uint32_t*)calloc(nrk + 1, 4);
+        m.count = (uint32_t*)calloc(nrk + 1, 4);
+        m.score = (double*)calloc(nrk + 1, 8);
+        m.pair = (uint64_t*)calloc(nrk + 1, 8);
+        m.word_off = (uint64_t*)calloc(nrk + 1, 8);
+        m.word_bytes = (uint8_t*)calloc((size_t)wtotal + 1, 1);
+        if (!m.doc || !m.pos || !m.npairs || !m.nterms || !m.term || !m.count || !m.score || !m.pair || !m.word_off ||
+            !m.word_bytes)
+            err = TFIDF_E_NOMEM;
+    }
+    uint64_t wat = 0;
+    for (size_t i = 0; i < nr && !err; ++i) {
+        const size_t o = i * k;
+        const int h = src_rank[i];
+        if (h < 0) {
+            m.doc[i] = doc_ids[i];
+            m.pos[i] = UINT32_MAX;
+            for (uint32_t j = 0; j < k; ++j) m.word_off[o + j] = wat;
+            continue;
+        }
+        const tfidf_doc_terms& p = part[h];
+        const uint32_t r = src_row[i];
+        const size_t e = (size_t)r * k;
+        m.doc[i] = p.doc[r];
+        m.pos[i] = (uint32_t)(doc0[h] + p.pos[r]);
+        m.npairs[i] = p.npairs[r];
+        m.nterms[i] = p.nterms[r];
+        memcpy(m.term + o, p.term + e, (size_t)k * 4);
+        memcpy(m.count + o, p.count + e, (size_t)k * 4);
+        memcpy(m.score + o, p.score + e, (size_t)k * 8);
+        for (uint32_t j = 0; j < k; ++j) {
+            m.pair[o + j] = j < p.nterms[r] ? pair0[h] + p.pair[e + j] : 0;
+            m.word_off[o + j] = wat + (p.word_off[e + j] - p.word_off[e]);
+        }
+        const uint64_t wn = p.word_off[e + k] - p.word_off[e];
+        if (wn) memcpy(m.word_bytes + wat, p.word_bytes + p.word_off[e], (size_t)wn);
+        wat += wn;
+    }
+    if (!err) m.word_off[nrk] = wat;
+    for (tfidf_doc_terms& p : part) tfidf_doc_terms_free(&p);
+    if (err) {
+        tfidf_doc_terms_free(&m);
+        memset(out, 0, sizeof(*out));
+        return err;
+    }
+    *out = m;
+    return TFIDF_OK;
+}
+
 void tfidf_group_close(tfidf_group* g) {
     if (!g) return;
     for (tfidf_ctx* c : g->ctx)

@@ -400,4 +400,60 @@ struct QTopkArgs {
 };
 int launch_query_topk(const QTopkArgs& a, uint32_t nq, hipStream_t s);
 
+/* ---- per-document top-k terms over the resident result (terms.hip, tfidf_top_terms) ---- */
+#define TERMS_NO_POS 0xFFFFFFFFu
+/* requested global document ids -> output positions (TERMS_NO_POS: not in this shard): a binary
+ * search of the id's document-name key (launch_doc_keys) over the output positions */
+struct TLookupArgs {
+    const uint32_t* ids;
+    uint32_t nids;
+    const uint32_t* order;       /* output position -> local document */
+    const uint32_t* doc_ids;     /* local document -> global id (null: index + 1) */
+    uint32_t ndocs;
+    uint32_t* pos;
+};
+int launch_terms_lookup(const TLookupArgs& a, hipStream_t s);
+/* one batch of rows: row i < nrows is the document at output position pos[row0 + i] (pos null:
+ * row0 + i).  Its k best pairs under (score descending, pair position ascending) go to
+ * score / pair / term / cnt / wlen at [i * k, i * k + rnterms[i]), the rest of the row is
+ * zeroed; wlen = the term's byte length (tlen of launch_term_meta) */
+struct TSelArgs {
+    const uint64_t* out_off;
+    const uint32_t* out_term;
+    const uint32_t* out_cnt;
+    const double* out_score;
+    const uint32_t* order;
+    const uint32_t* doc_ids;
+    const uint32_t* tlen;
+    uint32_t ndocs;
+    uint32_t nterms;             /* V */
+    uint64_t npairs;
+    const uint32_t* pos;
+    uint32_t row0, nrows, k;
+    uint32_t* rdoc;              /* per row: global id (0: no such document) */
+    uint64_t* rnpairs;
+    uint32_t* rnterms;
+    uint64_t* score;             /* the scores' bit patterns */
+    uint64_t* pair;
+    uint32_t* term;
+    uint32_t* cnt;
+    uint64_t* wlen;
+    uint32_t* big_list;          /* [nrows] scratch: rows of documents over QS_BIG pairs */
+    uint32_t* big_count;
+};
+int launch_terms_select(const TSelArgs& a, uint32_t ncu, hipStream_t s);
+/* the selected words' bytes: entry i is bytes [woff[i], woff[i + 1]) of `bytes` (short terms
+ * from their key, long terms from the corpus, as emit.hip's lines) */
+struct TWordArgs {
+    const uint32_t* term;
+    const uint64_t* woff;        /* n + 1 */
+    uint64_t n;
+    const uint4* tkey;
+    uint32_t nterms;
+    const uint8_t* corpus;
+    uint64_t corpus_bytes;
+    uint8_t* bytes;
+};
+int launch_terms_words(const TWordArgs& a, hipStream_t s);
+
 #endif

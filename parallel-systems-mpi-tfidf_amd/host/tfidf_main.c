@@ -27,6 +27,14 @@
  *   --top K       hits per query (default 10, at most TFIDF_QUERY_MAX_K);
  *   --hits FILE   the hits file (default hits.txt).
  * With several shards the ranks' hits are merged (tfidf_group_query).
+ *
+ * Keywords (the k best-scoring words of every document, tfidf_top_terms):
+ *   --keywords K          after output.txt (and after the hits file of --query), one line
+ *                         "doc<N>\t<word>\t%.16f" per returned word: documents in "docN@"
+ *                         order, a document's words by score descending, then in the order
+ *                         of its output.txt lines; K is 1..TFIDF_TERMS_MAX_K;
+ *   --keywords-file FILE  the keywords file (default keywords.txt).
+ * With several shards the ranks' rows are written in rank order (tfidf_group_top_terms).
  */
 #include <dirent.h>
 #include <pthread.h>
@@ -133,6 +141,34 @@ static int run_queries(tfidf_ctx* ctx, tfidf_group* g) {
     return rc;
 }
 
+/* --------------------------------------------------------------- keywords -- */
+
+static struct {
+    uint32_t k;         /* 0: no keywords, behaviour and bytes as without the option */
+    const char* file;
+} g_keywords = {0, "keywords.txt"};
+
+/* --keywords: the best words of every document of ctx (one shard) or of every rank of g */
+static int run_keywords(tfidf_ctx* ctx, tfidf_group* g) {
+    if (!g_keywords.k) return TFIDF_OK;
+    tfidf_doc_terms t;
+    memset(&t, 0, sizeof(t));
+    int rc = g ? tfidf_group_top_terms(g, NULL, 0, g_keywords.k, &t) : tfidf_top_terms(ctx, NULL, 0, g_keywords.k, &t);
+    if (rc) return rc;
+    FILE* f = fopen(g_keywords.file, "w");
+    if (!f) printf("Error Opening File: %s\n", g_keywords.file);
+    for (uint32_t r = 0; f && r < t.ndocs; ++r)
+        for (uint32_t j = 0; j < t.nterms[r]; ++j) {
+            const size_t e = (size_t)r * t.k + j;
+            fprintf(f, "doc%u\t", t.doc[r]);
+            fwrite(t.word_bytes + t.word_off[e], 1, (size_t)(t.word_off[e + 1] - t.word_off[e]), f);
+            fprintf(f, "\t%.16f\n", t.score[e]);
+        }
+    if (f && fclose(f) != 0) rc = TFIDF_E_OUTPUT;
+    tfidf_doc_terms_free(&t);
+    return rc;
+}
+
 /* ------------------------------------------------------------- one shard -- */
 
 static int run_single(int device, const char* indir, const char* outpath, int debug, int stats) {
@@ -175,6 +211,7 @@ static int run_single(int device, const char* indir, const char* outpath, int de
                 out_ms, (unsigned long long)oi.text_bytes, oi.ms_prepare, oi.ms_d2h_busy, oi.ms_write, oi.writers);
     }
     rc = run_queries(ctx, NULL);
+    if (!rc) rc = run_keywords(ctx, NULL);
     tfidf_close(ctx);
     if (rc) return fail(rc);
     return 0;
@@ -273,6 +310,7 @@ static int run_sharded(int ngpus, int nshards, const char* indir, const char* ou
                 (unsigned long long)pairs, wall_ms() - t_run);
     }
     rc = run_queries(NULL, g);
+    if (!rc) rc = run_keywords(NULL, g);
     tfidf_group_close(g);
     tfidf_plan_free(&plan);
     if (rc) return fail(rc);
@@ -302,9 +340,16 @@ int main(int argc, char** argv) {
             if (k < 1 || k > (long)TFIDF_QUERY_MAX_K) { fprintf(stderr, "tfidf: --top takes 1..%u\n", TFIDF_QUERY_MAX_K); return 2; }
             g_query.top = (uint32_t)k;
         }
+        else if (!strcmp(argv[i], "--keywords-file") && i + 1 < argc) g_keywords.file = argv[++i];
+        else if (!strcmp(argv[i], "--keywords") && i + 1 < argc) {
+            const long k = atol(argv[++i]);
+            if (k < 1 || k > (long)TFIDF_TERMS_MAX_K) { fprintf(stderr, "tfidf: --keywords takes 1..%u\n", TFIDF_TERMS_MAX_K); return 2; }
+            g_keywords.k = (uint32_t)k;
+        }
         else {
             fprintf(stderr, "usage: tfidf [--debug-jobs] [--stats] [--gpus N] [--shards K] [--device D] "
-                            "[--input DIR] [--output FILE] [--query FILE [--top K] [--hits FILE]]\n");
+                            "[--input DIR] [--output FILE] [--query FILE [--top K] [--hits FILE]] "
+                            "[--keywords K [--keywords-file FILE]]\n");
             return 2;
         }
     }

@@ -39,8 +39,11 @@ EXPORTS = [
     "tfidf_ingest_shard_device", "tfidf_doc_name_order", "tfidf_shard_split", "tfidf_device_count",
     "tfidf_last_output_info", "tfidf_run_totals_get",
     "tfidf_query", "tfidf_hits_free", "tfidf_group_query", "tfidf_last_query_info",
+    "tfidf_top_terms", "tfidf_doc_terms_free", "tfidf_group_top_terms", "tfidf_last_terms_info",
 ]
 QUERY_MAX_K = 1024  # TFIDF_QUERY_MAX_K
+TERMS_MAX_K = 1024  # TFIDF_TERMS_MAX_K
+NO_POS = 0xFFFFFFFF  # tfidf_doc_terms.pos of a document the shard does not hold
 E_INVAL = -1
 E_STATE = -10
 TFIDF_GROUP_LOCAL = 1
@@ -107,6 +110,23 @@ class QueryInfo(C.Structure):
         ("nterms_found", C.c_uint32), ("ngroups", C.c_uint32), ("group_queries", C.c_uint32),
         ("acc_bytes", C.c_uint64), ("ms_lookup", C.c_double), ("ms_score", C.c_double), ("ms_topk", C.c_double),
         ("ms_total", C.c_double),
+    ]
+
+
+class DocTerms(C.Structure):
+    _fields_ = [
+        ("ndocs", C.c_uint32), ("k", C.c_uint32), ("doc", C.POINTER(C.c_uint32)), ("pos", C.POINTER(C.c_uint32)),
+        ("npairs", C.POINTER(C.c_uint64)), ("nterms", C.POINTER(C.c_uint32)), ("term", C.POINTER(C.c_uint32)),
+        ("count", C.POINTER(C.c_uint32)), ("score", C.POINTER(C.c_double)), ("pair", C.POINTER(C.c_uint64)),
+        ("word_off", C.POINTER(C.c_uint64)), ("word_bytes", C.POINTER(C.c_uint8)),
+    ]
+
+
+class TermsInfo(C.Structure):
+    _fields_ = [
+        ("size", C.c_uint64), ("ndocs", C.c_uint32), ("k", C.c_uint32), ("nbatches", C.c_uint32),
+        ("big_docs", C.c_uint32), ("out_bytes", C.c_uint64), ("ms_lookup", C.c_double), ("ms_select", C.c_double),
+        ("ms_words", C.c_double), ("ms_total", C.c_double),
     ]
 
 
@@ -182,6 +202,11 @@ def lib() -> C.CDLL:
         L.tfidf_hits_free.argtypes = [C.POINTER(Hits)]
         L.tfidf_hits_free.restype = None
         L.tfidf_last_query_info.argtypes = [C.c_void_p, C.POINTER(QueryInfo)]
+        L.tfidf_top_terms.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(DocTerms)]
+        L.tfidf_group_top_terms.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(DocTerms)]
+        L.tfidf_doc_terms_free.argtypes = [C.POINTER(DocTerms)]
+        L.tfidf_doc_terms_free.restype = None
+        L.tfidf_last_terms_info.argtypes = [C.c_void_p, C.POINTER(TermsInfo)]
         if L.tfidf_abi_version() != ABI_VERSION:
             raise RuntimeError(f"{LIB_PATH}: ABI version {L.tfidf_abi_version()}, binding expects {ABI_VERSION} "
                                f"(stale build: rebuild with __graft_entry__.build())")
@@ -231,6 +256,37 @@ def _query(fn, handle, queries, k: int, what: str) -> dict:
         }
     finally:
         lib().tfidf_hits_free(C.byref(h))
+
+
+def _top_terms(fn, handle, k: int, docs, what: str, words: bool = True) -> dict:
+    """tfidf_top_terms / tfidf_group_top_terms: docs is None (every document in output order)
+    or a sequence of global document ids."""
+    ids = None if docs is None else np.ascontiguousarray(docs, dtype=np.uint32)
+    n = 0 if ids is None else len(ids)
+    if ids is not None and n == 0:
+        ids = np.zeros(1, dtype=np.uint32)   # an empty list is a list: the pointer must not be NULL
+    t = DocTerms()
+    _chk(fn(handle, None if ids is None else ids.ctypes.data_as(C.c_void_p), n, k, C.byref(t)), what)
+    try:
+        R = int(t.ndocs)
+
+        def arr(p, n, dt):
+            return np.ctypeslib.as_array(p, shape=(n,)).astype(dt, copy=True) if n else np.zeros(0, dtype=dt)
+
+        out = {
+            "k": int(t.k), "doc": arr(t.doc, R, np.uint32), "pos": arr(t.pos, R, np.uint32),
+            "npairs": arr(t.npairs, R, np.uint64), "nterms": arr(t.nterms, R, np.uint32),
+            "term": arr(t.term, R * k, np.uint32).reshape(R, k), "count": arr(t.count, R * k, np.uint32).reshape(R, k),
+            "score": arr(t.score, R * k, np.float64).reshape(R, k), "pair": arr(t.pair, R * k, np.uint64).reshape(R, k),
+        }
+        if words:
+            woff = arr(t.word_off, R * k + 1, np.uint64).tolist()
+            wb = bytes(arr(t.word_bytes, woff[-1], np.uint8))
+            nt = out["nterms"].tolist()
+            out["words"] = [[wb[woff[r * k + j]:woff[r * k + j + 1]] for j in range(nt[r])] for r in range(R)]
+        return out
+    finally:
+        lib().tfidf_doc_terms_free(C.byref(t))
 
 
 def synth_host(seed: int, V: int, mode: int, cdf, doc_ids, ntok):
@@ -402,6 +458,22 @@ class Engine:
         _chk(lib().tfidf_last_query_info(self.h, C.byref(q)), "tfidf_last_query_info")
         return {k: getattr(q, k) for k, _ in QueryInfo._fields_ if k != "size"}
 
+    def top_terms(self, k: int = 10, docs=None, words: bool = True) -> dict:
+        """The k best-scoring words of each document of this shard (tfidf_top_terms).  docs:
+        None for every document in output order, or global document ids (rows in that order;
+        an id the shard does not hold has pos == NO_POS).  Returns numpy arrays doc[rows],
+        pos[rows], npairs[rows], nterms[rows], term / count / score / pair [rows, k] (rows are
+        valid up to nterms) and words: per row the list of the words' bytes (words=False
+        leaves it out)."""
+        return _top_terms(lib().tfidf_top_terms, self.h, k, docs, "tfidf_top_terms", words)
+
+    def terms_info(self) -> dict:
+        """Counters and device times of the last top_terms (tfidf_last_terms_info)."""
+        t = TermsInfo()
+        t.size = C.sizeof(TermsInfo)
+        _chk(lib().tfidf_last_terms_info(self.h, C.byref(t)), "tfidf_last_terms_info")
+        return {k: getattr(t, k) for k, _ in TermsInfo._fields_ if k != "size"}
+
     @contextlib.contextmanager
     def fetched(self):
         """The last run's result as numpy views of the library's host arrays (tfidf_fetch
@@ -510,6 +582,11 @@ class Group:
     def query(self, queries, k: int = 10) -> dict:
         """Top-k documents over all shards (tfidf_group_query); see Engine.query."""
         return _query(lib().tfidf_group_query, self.h, queries, k, "tfidf_group_query")
+
+    def top_terms(self, k: int = 10, docs=None, words: bool = True) -> dict:
+        """The k best-scoring words of each document over all shards (tfidf_group_top_terms);
+        see Engine.top_terms.  term is the rank in the holding shard's term table."""
+        return _top_terms(lib().tfidf_group_top_terms, self.h, k, docs, "tfidf_group_top_terms", words)
 
 
 def plan_dir(path: str, nshards: int, threads: int = 0) -> dict:
