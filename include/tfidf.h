@@ -408,6 +408,82 @@ typedef struct tfidf_terms_info {
 } tfidf_terms_info;
 int tfidf_last_terms_info(const tfidf_ctx* ctx, tfidf_terms_info* info);
 
+/* ----------------------------------------------------------------- similar -- */
+
+/* Top-k similar-document search over the resident result of the last run: the nearest
+ * neighbours of a document under the cosine similarity of the TF-IDF vectors, read where
+ * tfidf_run left the scores.
+ *
+ * All arithmetic is IEEE binary64, round to nearest, and no product is fused into an add.
+ *   vector      document d's pairs (t, s(d,t)), s = the run's pair_score, terms in term-table
+ *               order, which is pair order
+ *   sq(d)       ((+0.0 + fl(s1*s1)) + fl(s2*s2)) + ... over d's pairs in pair order
+ *   norm(d)     sqrt(sq(d)), correctly rounded
+ *   dot(q,d)    ((+0.0 + fl(s(q,t1)*s(d,t1))) + fl(s(q,t2)*s(d,t2))) + ... over the terms q
+ *               and d share, in term-table order: the strcmp order of the words, the same in
+ *               every shard, so dot(q,d) and dot(d,q) have the same bits
+ *   sim(q,d)    fl(dot(q,d) / fl(norm(q)*norm(d))); +0.0 when that denominator is 0 (every
+ *               pair of q or of d has df = N, TFIDF.c:243)
+ *   neighbours  the documents other than q itself that share at least one term with q (a
+ *               similarity of +0.0 still counts)
+ *   order       sim descending, then global document id ascending numerically; the first k
+ *               are returned
+ * All values are >= +0.0 and finite, so their bit patterns order like the values (the argument
+ * of tfidf_query).  The result does not depend on grid, group size, budget or number of
+ * shards. */
+#define TFIDF_SIMILAR_MAX_K 1024u
+/* Arrays are owned by the library and released by tfidf_neighbors_free(). */
+typedef struct tfidf_neighbors {
+    uint32_t  ndocs, k;      /* rows, row stride */
+    uint32_t* doc;           /* per row: global document id */
+    uint32_t* pos;           /* per row: the document's output position; UINT32_MAX: not in this shard */
+    uint64_t* npairs;        /* per row: pairs of the document */
+    double*   norm;          /* per row: norm(d) */
+    uint64_t* nmatch;        /* per row: all neighbours, before the cut */
+    uint32_t* nnb;           /* per row: min(k, nmatch) */
+    uint32_t* nb_doc;        /* ndocs * k, row r at r * k: the neighbours' global document ids */
+    uint32_t* nb_shared;     /* terms the row's document and the neighbour share */
+    double*   nb_score;      /* sim */
+} tfidf_neighbors;
+/* The row rules are tfidf_top_terms's.  doc_ids == NULL: ndocs is ignored; one row per document
+ * of this context in output order (all pairs of documents: ceil(N / group) scans of the pairs).
+ * doc_ids != NULL: one row per entry in the caller's order, duplicates allowed; an id this
+ * shard does not hold gives pos = UINT32_MAX and an empty row.  An empty document has no
+ * neighbours.  TFIDF_E_STATE before a successful tfidf_run; TFIDF_E_INVAL for a NULL ctx or out,
+ * k == 0 or k > TFIDF_SIMILAR_MAX_K.  The run's result is not disturbed.  With a communicator
+ * attached the call is local to the context: it searches this shard's documents.  The norms
+ * are computed by the first call after a run and kept until the next tfidf_run (16 bytes per
+ * document).  The rows are scored in groups of up to 64, one scan of the pairs per group,
+ * whose dense per-(row, document) accumulators and top-k candidates stay under
+ * TFIDF_QUERY_ACC_MB (they are tfidf_query's buffers); all buffers belong to the context, so a
+ * repeated identical call allocates nothing (tfidf_alloc_stats). */
+int tfidf_similar(tfidf_ctx* ctx, const uint32_t* doc_ids, uint32_t ndocs, uint32_t k, tfidf_neighbors* out);
+void tfidf_neighbors_free(tfidf_neighbors* n);
+/* The same over every shard of a group (tfidf_group_run): the exact global top-k, bit-identical
+ * to a single-shard run of the same corpus.  The rank that holds a row's document exports its
+ * vector as (word bytes, score) and its norm; every rank resolves the words in its own
+ * vocabulary, scores its shard and the host merges the ranks' rows by the same order (the
+ * shards partition the documents).  nmatch sums over the ranks; pos counts from the first
+ * rank's first document.  The vectors of the rows pass through host memory: the all-documents
+ * form moves every pair's word and score once per rank. */
+int tfidf_group_similar(tfidf_group* g, const uint32_t* doc_ids, uint32_t ndocs, uint32_t k, tfidf_neighbors* out);
+/* Counters of the last tfidf_similar (the caller sets `size` = sizeof, as tfidf_query_info). */
+typedef struct tfidf_similar_info {
+    uint64_t size;
+    uint32_t rows, k;
+    uint32_t ngroups;         /* scans of the pairs */
+    uint32_t group_rows;      /* rows per group the budget allowed */
+    uint64_t acc_bytes;       /* accumulator + candidate bytes of the largest group */
+    uint32_t big_docs;        /* documents over 4096 pairs (the workgroup kernel), per scan */
+    uint32_t reserved;
+    double   ms_norms;        /* device times (HIP events), summed over the groups; 0 when cached */
+    double   ms_table;
+    double   ms_score;
+    double   ms_topk;
+    double   ms_total;        /* host wall time of the whole call */
+} tfidf_similar_info;
+int tfidf_last_similar_info(const tfidf_ctx* ctx, tfidf_similar_info* info);
+
 /* ---------------------------------------------------------------- ingest ---- */
 
 /* Reference input contract (TFIDF.c:98-110,130-147): N = number of entries of `dir`

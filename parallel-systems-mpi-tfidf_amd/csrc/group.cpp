@@ -763,6 +763,145 @@ int tfidf_group_top_terms(tfidf_group* g, const uint32_t* doc_ids, uint32_t ndoc
     return TFIDF_OK;
 }
 
+/* The rank that holds a row's document exports its vector as (word bytes, score) and its norm
+ * (tfidf_ctx_similar_export, every rank on its own host thread); the rows are put together
+ * here (NULL list: the ranks' rows in rank order; id list: each row from the first rank that
+ * holds the id, an id nobody holds stays empty); every rank then searches its shard for all
+ * rows (tfidf_ctx_similar_ext) and the ranks' rows are merged by (sim descending, document id
+ * ascending).  The words sort the same in every shard, so a rank adds a row's shared terms in
+ * the order a single shard would, and the shards partition the documents: the merged top-k is
+ * the single-shard result bit for bit. */
+int tfidf_group_similar(tfidf_group* g, const uint32_t* doc_ids, uint32_t ndocs, uint32_t k, tfidf_neighbors* out) {
+    if (!g || !out) return TFIDF_E_INVAL;
+    if (k == 0 || k > TFIDF_SIMILAR_MAX_K) return TFIDF_E_INVAL;
+    const int R = g->n;
+    std::vector<int> rc((size_t)R, TFIDF_OK);
+    std::vector<SimExport> ex((size_t)R);
+    {
+        std::vector<std::thread> th;
+        for (int r = 1; r < R; ++r) th.emplace_back([&, r] { rc[r] = tfidf_ctx_similar_export(g->ctx[r], doc_ids, ndocs, &ex[r]); });
+        rc[0] = tfidf_ctx_similar_export(g->ctx[0], doc_ids, ndocs, &ex[0]);
+        for (auto& t : th) t.join();
+    }
+    int err = TFIDF_OK;
+    for (int r = 0; r < R && !err; ++r) err = rc[r];
+    std::vector<uint64_t> doc0((size_t)R + 1, 0);
+    for (int r = 0; r < R && !err; ++r) {
+        tfidf_run_info ri;
+        memset(&ri, 0, sizeof(ri));
+        ri.size = sizeof(ri);
+        err = tfidf_last_run_info(g->ctx[r], &ri);
+        doc0[r + 1] = doc0[r] + ri.ndocs;
+    }
+    /* (rank, row in the rank's export) of every row; rank -1: no rank holds the id */
+    std::vector<int> src_rank;
+    std::vector<uint32_t> src_row;
+    if (!err) {
+        if (!doc_ids) {
+            for (int r = 0; r < R; ++r)
+                for (size_t i = 0; i + 1 < ex[r].voff.size(); ++i) { src_rank.push_back(r); src_row.push_back((uint32_t)i); }
+        } else {
+            for (uint32_t i = 0; i < ndocs; ++i) {
+                int h = -1;
+                for (int r = 0; r < R && h < 0; ++r)
+                    if (ex[r].pos[i] != UINT32_MAX) h = r;
+                src_rank.push_back(h);
+                src_row.push_back(i);
+            }
+        }
+        if (src_rank.size() > 0xFFFFFFFFull) err = TFIDF_E_CAPACITY;
+    }
+    const size_t nr = src_rank.size();
+    SimExport all;
+    tfidf_neighbors m;
+    memset(&m, 0, sizeof(m));
+    if (!err) {
+        all.id.assign(nr + 1, 0);
+        all.norm.assign(nr + 1, 0.0);
+        all.voff.assign(nr + 1, 0);
+        all.woff.assign(1, 0);
+        for (size_t i = 0; i < nr; ++i) {
+            const int h = src_rank[i];
+            all.id[i] = h < 0 ? doc_ids[i] : ex[h].id[src_row[i]];
+            uint64_t np = 0;
+            if (h >= 0) {
+                const SimExport& e = ex[h];
+                const uint32_t x = src_row[i];
+                all.norm[i] = e.norm[x];
+                np = e.voff[x + 1] - e.voff[x];
+                const uint64_t w0 = e.woff[e.voff[x]], wat = all.wbytes.size();
+                for (uint64_t p = e.voff[x]; p < e.voff[x + 1]; ++p) {
+                    all.score.push_back(e.score[p]);
+                    all.woff.push_back(wat + (e.woff[p + 1] - w0));
+                }
+                all.wbytes.insert(all.wbytes.end(), e.wbytes.begin() + (size_t)w0, e.wbytes.begin() + (size_t)e.woff[e.voff[x + 1]]);
+            }
+            all.voff[i + 1] = all.voff[i] + np;
+        }
+    }
+    std::vector<tfidf_neighbors> part((size_t)R);
+    for (tfidf_neighbors& p : part) memset(&p, 0, sizeof(p));
+    if (!err) {
+        std::vector<std::thread> th;
+        for (int r = 1; r < R; ++r) th.emplace_back([&, r] { rc[r] = tfidf_ctx_similar_ext(g->ctx[r], &all, k, &part[r]); });
+        rc[0] = tfidf_ctx_similar_ext(g->ctx[0], &all, k, &part[0]);
+        for (auto& t : th) t.join();
+        for (int r = 0; r < R && !err; ++r) err = rc[r];
+    }
+    if (!err) {
+        m.ndocs = (uint32_t)nr;
+        m.k = k;
+        m.doc = (uint32_t*)calloc(nr + 1, 4);
+        m.pos = (uint32_t*)calloc(nr + 1, 4);
+        m.npairs = (uint64_t*)calloc(nr + 1, 8);
+        m.norm = (double*)calloc(nr + 1, 8);
+        m.nmatch = (uint64_t*)calloc(nr + 1, 8);
+        m.nnb = (uint32_t*)calloc(nr + 1, 4);
+        m.nb_doc = (uint32_t*)calloc(nr * k + 1, 4);
+        m.nb_shared = (uint32_t*)calloc(nr * k + 1, 4);
+        m.nb_score = (double*)calloc(nr * k + 1, 8);
+        if (!m.doc || !m.pos || !m.npairs || !m.norm || !m.nmatch || !m.nnb || !m.nb_doc || !m.nb_shared || !m.nb_score)
+            err = TFIDF_E_NOMEM;
+    }
+    for (size_t i = 0; i < nr && !err; ++i) {
+        const int h = src_rank[i];
+        m.doc[i] = all.id[i];
+        m.pos[i] = h < 0 ? UINT32_MAX : (uint32_t)(doc0[h] + ex[h].pos[src_row[i]]);
+        m.npairs[i] = all.voff[i + 1] - all.voff[i];
+        m.norm[i] = all.norm[i];
+        std::vector<size_t> at((size_t)R, 0);   /* R-way merge of the ranks' ordered rows */
+        uint32_t n = 0;
+        for (int r = 0; r < R; ++r) m.nmatch[i] += part[r].nmatch[i];
+        while (n < k) {
+            int best = -1;
+            uint64_t bs = 0;
+            uint32_t bd = 0;
+            for (int r = 0; r < R; ++r) {
+                if (at[r] >= part[r].nnb[i]) continue;
+                uint64_t sb;
+                memcpy(&sb, &part[r].nb_score[i * k + at[r]], 8);   /* sims >= +0.0: the bits order like the values */
+                const uint32_t d = part[r].nb_doc[i * k + at[r]];
+                if (best < 0 || sb > bs || (sb == bs && d < bd)) { best = r; bs = sb; bd = d; }
+            }
+            if (best < 0) break;
+            m.nb_doc[i * k + n] = bd;
+            m.nb_shared[i * k + n] = part[best].nb_shared[i * k + at[best]];
+            memcpy(&m.nb_score[i * k + n], &bs, 8);
+            ++at[best];
+            ++n;
+        }
+        m.nnb[i] = n;
+    }
+    for (tfidf_neighbors& p : part) tfidf_neighbors_free(&p);
+    if (err) {
+        tfidf_neighbors_free(&m);
+        memset(out, 0, sizeof(*out));
+        return err;
+    }
+    *out = m;
+    return TFIDF_OK;
+}
+
 void tfidf_group_close(tfidf_group* g) {
     if (!g) return;
     for (tfidf_ctx* c : g->ctx)

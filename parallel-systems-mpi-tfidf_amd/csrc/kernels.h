@@ -456,4 +456,96 @@ struct TWordArgs {
 };
 int launch_terms_words(const TWordArgs& a, hipStream_t s);
 
+/* ---- top-k similar documents over the resident result (similar.hip, tfidf_similar) ---- */
+#define SG_MAX 64u   /* rows per scoring pass: one accumulator per lane of the owner wave (= QG_MAX) */
+/* sq[j] = the sequential sum of the squared scores of the document at output position j,
+ * norm[j] = its correctly rounded square root */
+int launch_sim_norms(const uint64_t* out_off, const double* out_score, uint32_t ndocs, uint64_t npairs, double* sq,
+                     double* norm, hipStream_t s);
+/* the rows of a call: row i is the document at output position pos[i] (pos null: i; no such
+ * position: an empty row with norm 0 and id 0) */
+struct SimRowArgs {
+    const uint64_t* out_off;
+    const uint32_t* order;
+    const uint32_t* doc_ids;
+    const double* sq;
+    const double* norm;
+    uint32_t ndocs;
+    uint64_t npairs;
+    const uint32_t* pos;
+    uint32_t nrows;
+    uint64_t* rb;                /* per row: its vector is entries [rb, re) of the pair arrays */
+    uint64_t* re;
+    double* rnorm;
+    double* rsq;
+    uint32_t* rpos;
+    uint32_t* rid;
+};
+int launch_sim_rows(const SimRowArgs& a, hipStream_t s);
+/* one group's term -> postings table over the shard's term ranks: row r < nrows <= SG_MAX holds
+ * the entries [rb[r], re[r]) of (term, score); entries whose term is >= V (a word this shard's
+ * vocabulary does not hold) are skipped.  mark sets bit r of mask[t] (V words, zeroed by the
+ * caller) for every term t of row r and writes cnt[t] = popcount(mask[t]); after post_off = the
+ * exclusive scan of cnt, fill writes row r's weight for t to
+ * post_w[post_off[t] + popcount(mask[t] below bit r)] */
+struct SimTabArgs {
+    const uint32_t* term;
+    const double* score;
+    const uint64_t* rb;
+    const uint64_t* re;
+    uint64_t nentries;           /* bound of term / score */
+    uint32_t nrows;
+    uint32_t V;
+    uint64_t* mask;
+    uint32_t* cnt;
+    const uint32_t* post_off;
+    double* post_w;
+    uint32_t post_cap;
+};
+int launch_sim_mark(const SimTabArgs& a, hipStream_t s);
+int launch_sim_fill(const SimTabArgs& a, hipStream_t s);
+/* one scan of the pairs for a group of nq <= SG_MAX rows: sim(row, document) and the number of
+ * shared terms for every (row, output position), [nq][ndocs], the layout of QScoreArgs.  The
+ * position rpos[row] (the row's own document) gets count 0. */
+struct SimScoreArgs {
+    const uint64_t* out_off;
+    const uint32_t* out_term;
+    const double* out_score;
+    uint32_t ndocs;
+    uint64_t npairs;
+    uint32_t V;
+    const uint64_t* mask;        /* V: the rows holding the term */
+    const uint32_t* post_off;    /* V + 1 */
+    const double* post_w;
+    uint32_t post_cap;
+    uint32_t nq;
+    const double* rnorm;         /* the group's rows */
+    const uint32_t* rpos;
+    const double* dnorm;         /* by output position */
+    double* acc;
+    uint32_t* cnt;
+    uint32_t* big_list;          /* [ndocs] scratch: output positions of documents over QS_BIG pairs */
+    uint32_t* big_count;
+};
+int launch_sim_score(const SimScoreArgs& a, uint32_t ncu, hipStream_t s);
+/* shared[e] = cnt[row][pos[e]] for the n_of_row[row] first entries of row = e / k, else 0 */
+int launch_sim_shared(const uint32_t* cnt, const uint32_t* pos, const uint32_t* n_of_row, uint32_t nrows, uint32_t k,
+                      uint32_t ndocs, uint32_t* shared, hipStream_t s);
+/* a group of rows' vectors made contiguous: row r's entries [rb[r], re[r]) of the pair arrays
+ * go to [eoff[r], ...) of term / score, wlen = the terms' byte lengths */
+struct SimExportArgs {
+    const uint32_t* out_term;
+    const double* out_score;
+    const uint32_t* tlen;
+    uint32_t V;
+    const uint64_t* rb;
+    const uint64_t* re;
+    const uint64_t* eoff;
+    uint32_t nrows;
+    uint32_t* term;
+    double* score;
+    uint64_t* wlen;
+};
+int launch_sim_export(const SimExportArgs& a, hipStream_t s);
+
 #endif

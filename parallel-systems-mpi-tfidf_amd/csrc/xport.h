@@ -65,6 +65,21 @@ hipStream_t tfidf_ctx_stream(const tfidf_ctx* ctx);
 int tfidf_ctx_query(tfidf_ctx* ctx, const tfidf_queries* queries, uint32_t k, tfidf_hits* out,
                     std::vector<uint8_t>* found, std::vector<uint64_t>* found_off);
 
+/* engine.cpp: the two halves of tfidf_group_similar on one shard.  Export: the rows' documents
+ * as this shard holds them (pos UINT32_MAX: it does not; the row is empty): row i's vector is
+ * entries [voff[i], voff[i + 1]) of (word, score), word x = wbytes[woff[x], woff[x + 1]), in
+ * term-table order.  Search: this shard's neighbours of rows given that way (id, norm, voff,
+ * woff, wbytes, score): the words are resolved in the shard's own vocabulary, the row's own
+ * document is found by its id; fills nmatch, nnb and nb_* of `out` (rows in the given order). */
+struct SimExport {
+    std::vector<uint32_t> id, pos;
+    std::vector<uint64_t> npairs, voff, woff;
+    std::vector<double> norm, score;
+    std::vector<uint8_t> wbytes;
+};
+int tfidf_ctx_similar_export(tfidf_ctx* ctx, const uint32_t* doc_ids, uint32_t ndocs, SimExport* e);
+int tfidf_ctx_similar_ext(tfidf_ctx* ctx, const SimExport* rows, uint32_t k, tfidf_neighbors* out);
+
 /* engine.cpp: hipMalloc counted in tfidf_run_info.device_allocs / device_alloc_bytes */
 hipError_t tfidf_dev_malloc(void** p, size_t bytes);
 

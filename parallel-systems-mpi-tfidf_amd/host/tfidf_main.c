@@ -35,6 +35,18 @@
  *                         of its output.txt lines; K is 1..TFIDF_TERMS_MAX_K;
  *   --keywords-file FILE  the keywords file (default keywords.txt).
  * With several shards the ranks' rows are written in rank order (tfidf_group_top_terms).
+ *
+ * Similar documents (nearest neighbours under the cosine similarity of the TF-IDF vectors,
+ * tfidf_similar):
+ *   --similar K           after output.txt (and the files of --query and --keywords), one line
+ *                         "doc<N>\tdoc<M>\t%.16f" per returned neighbour: documents in "docN@"
+ *                         order, a document's neighbours by similarity descending, then document
+ *                         id ascending; K is 1..TFIDF_SIMILAR_MAX_K.  Every document is a row:
+ *                         ceil(N / group) scans of the scored pairs, group <= 64;
+ *   --similar-docs FILE   rows for the document ids of FILE only (one id per line), in FILE's
+ *                         order;
+ *   --similar-file FILE   the neighbours file (default similar.txt).
+ * With several shards the result is the single-shard one (tfidf_group_similar).
  */
 #include <dirent.h>
 #include <pthread.h>
@@ -169,6 +181,49 @@ static int run_keywords(tfidf_ctx* ctx, tfidf_group* g) {
     return rc;
 }
 
+/* ---------------------------------------------------------------- similar -- */
+
+static struct {
+    uint32_t k;         /* 0: no search, behaviour and bytes as without the option */
+    const char* docs;   /* NULL: every document */
+    const char* file;
+} g_similar = {0, NULL, "similar.txt"};
+
+/* --similar: the nearest neighbours of the documents of ctx (one shard) or of every rank of g */
+static int run_similar(tfidf_ctx* ctx, tfidf_group* g) {
+    if (!g_similar.k) return TFIDF_OK;
+    uint32_t* ids = NULL;
+    uint32_t nids = 0;
+    if (g_similar.docs) {
+        FILE* f = fopen(g_similar.docs, "r");
+        if (!f) { printf("Error Opening File: %s\n", g_similar.docs); return TFIDF_OK; }
+        size_t cap = 1024;
+        ids = (uint32_t*)malloc(cap * sizeof(uint32_t));
+        unsigned long long v;
+        while (ids && fscanf(f, "%llu", &v) == 1) {
+            if (nids == cap) { cap *= 2; ids = (uint32_t*)realloc(ids, cap * sizeof(uint32_t)); }
+            if (ids) ids[nids++] = v > 0xFFFFFFFFull ? 0u : (uint32_t)v;   /* no document has id 0 */
+        }
+        fclose(f);
+        if (!ids) return TFIDF_E_NOMEM;
+    }
+    tfidf_neighbors n;
+    memset(&n, 0, sizeof(n));
+    int rc = g ? tfidf_group_similar(g, ids, nids, g_similar.k, &n) : tfidf_similar(ctx, ids, nids, g_similar.k, &n);
+    free(ids);
+    if (rc) return rc;
+    FILE* f = fopen(g_similar.file, "w");
+    if (!f) printf("Error Opening File: %s\n", g_similar.file);
+    for (uint32_t r = 0; f && r < n.ndocs; ++r)
+        for (uint32_t j = 0; j < n.nnb[r]; ++j) {
+            const size_t e = (size_t)r * n.k + j;
+            fprintf(f, "doc%u\tdoc%u\t%.16f\n", n.doc[r], n.nb_doc[e], n.nb_score[e]);
+        }
+    if (f && fclose(f) != 0) rc = TFIDF_E_OUTPUT;
+    tfidf_neighbors_free(&n);
+    return rc;
+}
+
 /* ------------------------------------------------------------- one shard -- */
 
 static int run_single(int device, const char* indir, const char* outpath, int debug, int stats) {
@@ -212,6 +267,7 @@ static int run_single(int device, const char* indir, const char* outpath, int de
     }
     rc = run_queries(ctx, NULL);
     if (!rc) rc = run_keywords(ctx, NULL);
+    if (!rc) rc = run_similar(ctx, NULL);
     tfidf_close(ctx);
     if (rc) return fail(rc);
     return 0;
@@ -311,6 +367,7 @@ static int run_sharded(int ngpus, int nshards, const char* indir, const char* ou
     }
     rc = run_queries(NULL, g);
     if (!rc) rc = run_keywords(NULL, g);
+    if (!rc) rc = run_similar(NULL, g);
     tfidf_group_close(g);
     tfidf_plan_free(&plan);
     if (rc) return fail(rc);
@@ -346,10 +403,20 @@ int main(int argc, char** argv) {
             if (k < 1 || k > (long)TFIDF_TERMS_MAX_K) { fprintf(stderr, "tfidf: --keywords takes 1..%u\n", TFIDF_TERMS_MAX_K); return 2; }
             g_keywords.k = (uint32_t)k;
         }
+        else if (!strcmp(argv[i], "--similar-docs") && i + 1 < argc) g_similar.docs = argv[++i];
+        else if (!strcmp(argv[i], "--similar-file") && i + 1 < argc) g_similar.file = argv[++i];
+        else if (!strcmp(argv[i], "--similar") && i + 1 < argc) {
+            const long k = atol(argv[++i]);
+            if (k < 1 || k > (long)TFIDF_SIMILAR_MAX_K) { fprintf(stderr, "tfidf: --similar takes 1..%u\n", TFIDF_SIMILAR_MAX_K); return 2; }
+            g_similar.k = (uint32_t)k;
+        }
         else {
             fprintf(stderr, "usage: tfidf [--debug-jobs] [--stats] [--gpus N] [--shards K] [--device D] "
                             "[--input DIR] [--output FILE] [--query FILE [--top K] [--hits FILE]] "
-                            "[--keywords K [--keywords-file FILE]]\n");
+                            "[--keywords K [--keywords-file FILE]] "
+                            "[--similar K [--similar-docs FILE] [--similar-file FILE]]\n"
+                            "  --similar K without --similar-docs searches for every document: "
+                            "ceil(N / group) scans of the scored pairs, group <= 64\n");
             return 2;
         }
     }

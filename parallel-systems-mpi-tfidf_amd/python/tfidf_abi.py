@@ -40,9 +40,11 @@ EXPORTS = [
     "tfidf_last_output_info", "tfidf_run_totals_get",
     "tfidf_query", "tfidf_hits_free", "tfidf_group_query", "tfidf_last_query_info",
     "tfidf_top_terms", "tfidf_doc_terms_free", "tfidf_group_top_terms", "tfidf_last_terms_info",
+    "tfidf_similar", "tfidf_neighbors_free", "tfidf_group_similar", "tfidf_last_similar_info",
 ]
 QUERY_MAX_K = 1024  # TFIDF_QUERY_MAX_K
 TERMS_MAX_K = 1024  # TFIDF_TERMS_MAX_K
+SIMILAR_MAX_K = 1024  # TFIDF_SIMILAR_MAX_K
 NO_POS = 0xFFFFFFFF  # tfidf_doc_terms.pos of a document the shard does not hold
 E_INVAL = -1
 E_STATE = -10
@@ -130,6 +132,24 @@ class TermsInfo(C.Structure):
     ]
 
 
+class Neighbors(C.Structure):
+    _fields_ = [
+        ("ndocs", C.c_uint32), ("k", C.c_uint32), ("doc", C.POINTER(C.c_uint32)), ("pos", C.POINTER(C.c_uint32)),
+        ("npairs", C.POINTER(C.c_uint64)), ("norm", C.POINTER(C.c_double)), ("nmatch", C.POINTER(C.c_uint64)),
+        ("nnb", C.POINTER(C.c_uint32)), ("nb_doc", C.POINTER(C.c_uint32)), ("nb_shared", C.POINTER(C.c_uint32)),
+        ("nb_score", C.POINTER(C.c_double)),
+    ]
+
+
+class SimilarInfo(C.Structure):
+    _fields_ = [
+        ("size", C.c_uint64), ("rows", C.c_uint32), ("k", C.c_uint32), ("ngroups", C.c_uint32),
+        ("group_rows", C.c_uint32), ("acc_bytes", C.c_uint64), ("big_docs", C.c_uint32), ("reserved", C.c_uint32),
+        ("ms_norms", C.c_double), ("ms_table", C.c_double), ("ms_score", C.c_double), ("ms_topk", C.c_double),
+        ("ms_total", C.c_double),
+    ]
+
+
 class DirPlan(C.Structure):
     _fields_ = [
         ("ndocs", C.c_uint32), ("nshards", C.c_uint32), ("doc_ids", C.POINTER(C.c_uint32)),
@@ -207,6 +227,11 @@ def lib() -> C.CDLL:
         L.tfidf_doc_terms_free.argtypes = [C.POINTER(DocTerms)]
         L.tfidf_doc_terms_free.restype = None
         L.tfidf_last_terms_info.argtypes = [C.c_void_p, C.POINTER(TermsInfo)]
+        L.tfidf_similar.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(Neighbors)]
+        L.tfidf_group_similar.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(Neighbors)]
+        L.tfidf_neighbors_free.argtypes = [C.POINTER(Neighbors)]
+        L.tfidf_neighbors_free.restype = None
+        L.tfidf_last_similar_info.argtypes = [C.c_void_p, C.POINTER(SimilarInfo)]
         if L.tfidf_abi_version() != ABI_VERSION:
             raise RuntimeError(f"{LIB_PATH}: ABI version {L.tfidf_abi_version()}, binding expects {ABI_VERSION} "
                                f"(stale build: rebuild with __graft_entry__.build())")
@@ -287,6 +312,33 @@ def _top_terms(fn, handle, k: int, docs, what: str, words: bool = True) -> dict:
         return out
     finally:
         lib().tfidf_doc_terms_free(C.byref(t))
+
+
+def _similar(fn, handle, k: int, docs, what: str) -> dict:
+    """tfidf_similar / tfidf_group_similar: docs is None (every document in output order) or a
+    sequence of global document ids."""
+    ids = None if docs is None else np.ascontiguousarray(docs, dtype=np.uint32)
+    n = 0 if ids is None else len(ids)
+    if ids is not None and n == 0:
+        ids = np.zeros(1, dtype=np.uint32)   # an empty list is a list: the pointer must not be NULL
+    t = Neighbors()
+    _chk(fn(handle, None if ids is None else ids.ctypes.data_as(C.c_void_p), n, k, C.byref(t)), what)
+    try:
+        R = int(t.ndocs)
+
+        def arr(p, n, dt):
+            return np.ctypeslib.as_array(p, shape=(n,)).astype(dt, copy=True) if n else np.zeros(0, dtype=dt)
+
+        return {
+            "k": int(t.k), "doc": arr(t.doc, R, np.uint32), "pos": arr(t.pos, R, np.uint32),
+            "npairs": arr(t.npairs, R, np.uint64), "norm": arr(t.norm, R, np.float64),
+            "nmatch": arr(t.nmatch, R, np.uint64), "nnb": arr(t.nnb, R, np.uint32),
+            "nb_doc": arr(t.nb_doc, R * k, np.uint32).reshape(R, k),
+            "nb_shared": arr(t.nb_shared, R * k, np.uint32).reshape(R, k),
+            "nb_score": arr(t.nb_score, R * k, np.float64).reshape(R, k),
+        }
+    finally:
+        lib().tfidf_neighbors_free(C.byref(t))
 
 
 def synth_host(seed: int, V: int, mode: int, cdf, doc_ids, ntok):
@@ -474,6 +526,22 @@ class Engine:
         _chk(lib().tfidf_last_terms_info(self.h, C.byref(t)), "tfidf_last_terms_info")
         return {k: getattr(t, k) for k, _ in TermsInfo._fields_ if k != "size"}
 
+    def similar(self, k: int = 10, docs=None) -> dict:
+        """The k nearest neighbours of each document of this shard under the cosine similarity
+        of the TF-IDF vectors (tfidf_similar).  docs: None for every document in output order
+        (ceil(N / group) scans of the pairs), or global document ids (rows in that order; an id
+        the shard does not hold has pos == NO_POS).  Returns numpy arrays doc[rows], pos[rows],
+        npairs[rows], norm[rows], nmatch[rows], nnb[rows] and nb_doc / nb_shared / nb_score
+        [rows, k] (rows are valid up to nnb)."""
+        return _similar(lib().tfidf_similar, self.h, k, docs, "tfidf_similar")
+
+    def similar_info(self) -> dict:
+        """Counters and device times of the last similar (tfidf_last_similar_info)."""
+        t = SimilarInfo()
+        t.size = C.sizeof(SimilarInfo)
+        _chk(lib().tfidf_last_similar_info(self.h, C.byref(t)), "tfidf_last_similar_info")
+        return {k: getattr(t, k) for k, _ in SimilarInfo._fields_ if k not in ("size", "reserved")}
+
     @contextlib.contextmanager
     def fetched(self):
         """The last run's result as numpy views of the library's host arrays (tfidf_fetch
@@ -587,6 +655,11 @@ class Group:
         """The k best-scoring words of each document over all shards (tfidf_group_top_terms);
         see Engine.top_terms.  term is the rank in the holding shard's term table."""
         return _top_terms(lib().tfidf_group_top_terms, self.h, k, docs, "tfidf_group_top_terms", words)
+
+    def similar(self, k: int = 10, docs=None) -> dict:
+        """The k nearest neighbours of each document over all shards (tfidf_group_similar): the
+        single-shard result bit for bit; see Engine.similar."""
+        return _similar(lib().tfidf_group_similar, self.h, k, docs, "tfidf_group_similar")
 
 
 def plan_dir(path: str, nshards: int, threads: int = 0) -> dict:
