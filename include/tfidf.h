@@ -344,6 +344,83 @@ typedef struct tfidf_query_info {
 } tfidf_query_info;
 int tfidf_last_query_info(const tfidf_ctx* ctx, tfidf_query_info* info);
 
+/* ---------------------------------------------------------------- BM25 ------ */
+
+/* tfidf_query with Okapi BM25 as the ranking function, over the same resident result: term
+ * frequency saturates (k1), length normalisation is soft (b), and a word of every document
+ * still counts.  Queries are tokenised exactly as for tfidf_query (tokens, terms cut at their
+ * first NUL, terms of >= 16 bytes matched by their bytes); w(q,t) = the tokens of q whose
+ * term is t.
+ *
+ * All arithmetic is IEEE binary64, round to nearest; every operation below rounds on its own
+ * (fl() marks each rounding; no product is fused into an add).
+ *   N          the run's ndocs_total; df(t) the run's global df (tfidf_result.term_df)
+ *   idf(t)     log( fl(1.0 + fl( fl((double)(N - df) + 0.5) / fl((double)df + 0.5) )) ), the
+ *              host's libm log, once per distinct found term of the batch (the Lucene form:
+ *              always > 0, so a df = N word counts, unlike tfidf_query)
+ *   W(q,t)     fl( (double)w(q,t) * idf(t) )
+ *   avgdl      params.avgdl when it is > 0; when it is 0, fl( (double)L / (double)n ) with L the
+ *              u64 sum of docSize over this context's documents and n the number of documents
+ *              the context holds (L = 0: there are no pairs and every row is empty)
+ *   K(d)       fl( k1 * fl( fl(1.0 - b) + fl( b * fl( (double)docSize(d) / avgdl ) ) ) )
+ *   sat(d,t)   fl( fl( (double)c * fl(k1 + 1.0) ) / fl( (double)c + K(d) ) ), c = the pair's
+ *              wordCount (tfidf_result.pair_count; c >= 1, so the divisor is >= 1)
+ *   score(q,d) ((+0.0 + fl(W1 * sat1)) + fl(W2 * sat2)) + .. over the terms of q that occur in
+ *              d, in pair order (term-table order, the order of tfidf_result.pair_term)
+ *   hits of q  the documents holding >= 1 term of q, ordered by score descending, then global
+ *              document id ascending numerically; the first k are returned.
+ * All scores are >= +0.0 and finite.  The result does not depend on grid, group size, budget
+ * or number of shards.
+ *
+ * Parameters: k1 >= 0, 0 <= b <= 1, avgdl >= 0, all finite; anything else, NaN included, is
+ * TFIDF_E_INVAL.  So that no intermediate can become inf/inf or 0*inf (K(d) may overflow to +inf:
+ * sat is then +0.0 and the score stays finite), k1 above TFIDF_BM25_MAX_K1 and an avgdl in
+ * (0, TFIDF_BM25_MIN_AVGDL) are TFIDF_E_INVAL too.  `size` is set by the caller to
+ * sizeof(tfidf_bm25_params); a smaller one is TFIDF_E_INVAL.  A NULL params pointer means
+ * the defaults k1 = 1.2, b = 0.75, avgdl = 0. */
+#define TFIDF_BM25_DEFAULT_K1 1.2
+#define TFIDF_BM25_DEFAULT_B  0.75
+#define TFIDF_BM25_MAX_K1     0x1p+900
+#define TFIDF_BM25_MIN_AVGDL  0x1p-900
+typedef struct tfidf_bm25_params {
+    uint64_t size;
+    double   k1, b, avgdl;
+} tfidf_bm25_params;
+/* Errors, state rules and buffers are tfidf_query's: TFIDF_E_STATE before a successful
+ * tfidf_run; TFIDF_E_INVAL for a NULL ctx / queries / out, k == 0, k > TFIDF_QUERY_MAX_K, a bad
+ * batch or bad parameters; the run's result is not disturbed; the run's corpus must still be
+ * valid (long terms); with a communicator attached the call is local to this shard.  The
+ * accumulators and candidate lists are tfidf_query's own buffers under TFIDF_QUERY_ACC_MB, so
+ * a repeated call allocates nothing and tfidf_query after it returns its own bits.  L is
+ * summed once per run.  The rows are freed with tfidf_hits_free. */
+int tfidf_query_bm25(tfidf_ctx* ctx, const tfidf_queries* queries, uint32_t k, const tfidf_bm25_params* params,
+                     tfidf_hits* out);
+/* The same over every shard of a group, merged like tfidf_group_query.  With avgdl = 0 the
+ * host sums L and n over the ranks (exact integers, one division) and hands every rank the
+ * same avgdl; global df and N are shared by the run, so the merged result is bit-identical to
+ * a single-shard run of the same corpus.  A multi-process caller that attached its own
+ * communicator (tfidf_comm_init) has no group: its tfidf_query_bm25 calls are local, avgdl = 0
+ * would be each shard's own average, so it passes the corpus-wide avgdl itself. */
+int tfidf_group_query_bm25(tfidf_group* g, const tfidf_queries* queries, uint32_t k, const tfidf_bm25_params* params,
+                           tfidf_hits* out);
+/* Counters of the last tfidf_query_bm25: tfidf_query_info's fields and the avgdl used (the
+ * caller sets `size` = sizeof). */
+typedef struct tfidf_bm25_info {
+    uint64_t size;
+    uint32_t nqueries, k;
+    uint32_t nterms;
+    uint32_t nterms_found;
+    uint32_t ngroups;
+    uint32_t group_queries;
+    uint64_t acc_bytes;
+    double   ms_lookup;       /* includes the gather of the found terms' df */
+    double   ms_score;
+    double   ms_topk;
+    double   ms_total;
+    double   avgdl;           /* the value the scores were computed with (0: L = 0, no pairs) */
+} tfidf_bm25_info;
+int tfidf_last_bm25_info(const tfidf_ctx* ctx, tfidf_bm25_info* info);
+
 /* ---------------------------------------------------------------- keywords -- */
 
 /* Per-document top-k keyword extraction over the resident result of the last run: the k

@@ -16,6 +16,7 @@
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
 
+#include <float.h>
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -241,6 +242,11 @@ struct tfidf_ctx {
     hipEvent_t ev_q[3] = {};                    /* lookup / score / top-k bounds (created by the first query) */
     uint32_t ncu = 0;
     tfidf_query_info qinfo{};
+    /* BM25 ranking (tfidf_query_bm25, bm25.hip): tfidf_query's buffers; L = the sum of doc_size
+     * over this context's documents, kept until the next run */
+    uint64_t bm25_L = 0;
+    bool bm25_L_valid = false;
+    tfidf_bm25_info binfo{};
     /* per-document top-k terms (tfidf_top_terms, terms.hip): the requested ids and their output
      * positions, a batch's per-row words (npairs, nterms, id), its k entries per row (score
      * bits, pair, term, count, word length -> offset), the gathered words, the list of long
@@ -1752,6 +1758,7 @@ extern "C" int tfidf_run(tfidf_ctx* ctx, const tfidf_corpus* in) {
     ctx->text_valid = false;
     ctx->tmeta_valid = false;
     ctx->norm_valid = false;
+    ctx->bm25_L_valid = false;
     CorpusDev c{};
     const uint32_t* dev_ids = nullptr;
     uint64_t Nt = 0;
@@ -2401,8 +2408,44 @@ extern "C" void tfidf_hits_free(tfidf_hits* h) {
     memset(h, 0, sizeof(*h));
 }
 
+/* the exact sum of doc_size over the context's documents (BM25's default avgdl): a host sum
+ * over one copy, kept until the next run */
+int tfidf_ctx_bm25_lengths(tfidf_ctx* ctx, uint64_t* L, uint64_t* n) {
+    if (!ctx || !L || !n) return TFIDF_E_INVAL;
+    if (!ctx->have_result) return TFIDF_E_STATE;
+    if (!ctx->bm25_L_valid) {
+        HIPCHK(hipSetDevice(ctx->device));
+        std::vector<uint32_t> dsz(ctx->ndocs);
+        if (ctx->ndocs) {
+            HIPCHK(hipMemcpyAsync(dsz.data(), ctx->doc_size.p, (size_t)ctx->ndocs * 4, hipMemcpyDeviceToHost, ctx->stream));
+            HIPCHK(hipStreamSynchronize(ctx->stream));
+        }
+        uint64_t sum = 0;
+        for (uint32_t v : dsz) sum += v;
+        ctx->bm25_L = sum;
+        ctx->bm25_L_valid = true;
+    }
+    *L = ctx->bm25_L;
+    *n = ctx->ndocs;
+    return TFIDF_OK;
+}
+
+int tfidf_bm25_params_check(const tfidf_bm25_params* p, Bm25Call* out) {
+    Bm25Call c{TFIDF_BM25_DEFAULT_K1, TFIDF_BM25_DEFAULT_B, 0.0};
+    if (p) {
+        if (p->size < sizeof(tfidf_bm25_params)) return TFIDF_E_INVAL;
+        c = Bm25Call{p->k1, p->b, p->avgdl};
+    }
+    /* written so that a NaN fails every test */
+    if (!(c.k1 >= 0.0 && c.k1 <= TFIDF_BM25_MAX_K1)) return TFIDF_E_INVAL;
+    if (!(c.b >= 0.0 && c.b <= 1.0)) return TFIDF_E_INVAL;
+    if (!(c.avgdl == 0.0 || (c.avgdl >= TFIDF_BM25_MIN_AVGDL && c.avgdl <= DBL_MAX))) return TFIDF_E_INVAL;
+    *out = c;
+    return TFIDF_OK;
+}
+
 int tfidf_ctx_query(tfidf_ctx* ctx, const tfidf_queries* qs, uint32_t k, tfidf_hits* out, std::vector<uint8_t>* found_out,
-                    std::vector<uint64_t>* found_off_out) {
+                    std::vector<uint64_t>* found_off_out, const Bm25Call* bm) {
     if (!ctx || !qs || !out) return TFIDF_E_INVAL;
     if (k == 0 || k > TFIDF_QUERY_MAX_K || qs->nqueries > TFIDF_QUERY_MAX_QUERIES) return TFIDF_E_INVAL;
     const uint32_t nq = qs->nqueries;
@@ -2414,6 +2457,16 @@ int tfidf_ctx_query(tfidf_ctx* ctx, const tfidf_queries* qs, uint32_t k, tfidf_h
     const auto wall0 = std::chrono::steady_clock::now();
     HIPCHK(hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
+    double avgdl = 0.0;   /* BM25: 0 = no document has a token, every row is empty */
+    if (bm) {
+        avgdl = bm->avgdl;
+        if (!(avgdl > 0.0)) {
+            uint64_t L = 0, n = 0;
+            const int rc = tfidf_ctx_bm25_lengths(ctx, &L, &n);
+            if (rc) return rc;
+            avgdl = L ? (double)L / (double)n : 0.0;
+        }
+    }
     for (hipEvent_t& e : ctx->ev_q)
         if (!e) HIPCHK(hipEventCreate(&e));
     if (!ctx->ncu) {
@@ -2466,7 +2519,7 @@ int tfidf_ctx_query(tfidf_ctx* ctx, const tfidf_queries* qs, uint32_t k, tfidf_h
     qi.nterms = nT;
 
     /* ---- lookup: one lane per distinct term ---- */
-    std::vector<uint32_t> rank(nT, QUERY_NO_TERM);
+    std::vector<uint32_t> rank(nT, QUERY_NO_TERM), df_found(bm ? nT : 0, 0u);
     std::vector<uint64_t> toff((size_t)nT + 1, 0);
     std::string blob;
     if (nT && ctx->V) {
@@ -2474,7 +2527,7 @@ int tfidf_ctx_query(tfidf_ctx* ctx, const tfidf_queries* qs, uint32_t k, tfidf_h
         toff[nT] = blob.size();
         const size_t offb = ((size_t)nT + 1) * 8;
         ENSURE(ctx->q_terms, offb + blob.size() + 16);
-        ENSURE(ctx->q_rank, (size_t)nT * 4 + 4);
+        ENSURE(ctx->q_rank, (size_t)nT * (bm ? 8 : 4) + 4);   /* BM25: the found terms' df behind the ranks */
         HIPCHK(hipMemcpyAsync(ctx->q_terms.p, toff.data(), offb, hipMemcpyHostToDevice, s));
         if (!blob.empty())
             HIPCHK(hipMemcpyAsync(ctx->q_terms.as<uint8_t>() + offb, blob.data(), blob.size(), hipMemcpyHostToDevice, s));
@@ -2493,8 +2546,13 @@ int tfidf_ctx_query(tfidf_ctx* ctx, const tfidf_queries* qs, uint32_t k, tfidf_h
         la.rank_out = ctx->q_rank.as<uint32_t>();
         HIPCHK(hipEventRecord(ctx->ev_q[0], s));
         if (launch_query_lookup(la, s)) { HIPCHK(hipGetLastError()); return TFIDF_E_HIP; }
+        if (bm && launch_bm25_df(la.rank_out, nT, df_of_run(ctx), ctx->V, la.rank_out + nT, s)) {
+            HIPCHK(hipGetLastError());
+            return TFIDF_E_HIP;
+        }
         HIPCHK(hipEventRecord(ctx->ev_q[1], s));
         HIPCHK(hipMemcpyAsync(rank.data(), ctx->q_rank.p, (size_t)nT * 4, hipMemcpyDeviceToHost, s));
+        if (bm) HIPCHK(hipMemcpyAsync(df_found.data(), la.rank_out + nT, (size_t)nT * 4, hipMemcpyDeviceToHost, s));
         HIPCHK(hipStreamSynchronize(s));
         float ms = 0;
         (void)hipEventElapsedTime(&ms, ctx->ev_q[0], ctx->ev_q[1]);
@@ -2510,8 +2568,22 @@ int tfidf_ctx_query(tfidf_ctx* ctx, const tfidf_queries* qs, uint32_t k, tfidf_h
                 if (found_out) (*found_out)[x] = 1;
             }
 
+    /* ---- BM25: idf per distinct found term, the host's libm log (one operation per line) ---- */
+    std::vector<double> idf(bm ? nT : 0, 0.0);
+    for (uint32_t t = 0; bm && t < nT; ++t) {
+        if (rank[t] == QUERY_NO_TERM) continue;
+        const uint64_t Nt = ctx->ndocs_total, df = df_found[t] < Nt ? df_found[t] : Nt;
+        const double num = (double)(Nt - df) + 0.5;
+        const double den = (double)df + 0.5;
+        const double ratio = num / den;
+        const double arg = 1.0 + ratio;
+        idf[t] = log(arg);
+    }
+
     /* ---- query groups under the accumulator budget ---- */
-    const uint32_t N = ctx->ndocs;
+    /* BM25 with avgdl 0 (L = 0: no document of the context has a token, so there are no pairs):
+     * N = 0 turns every group below off and the rows stay empty, as the header defines */
+    const uint32_t N = bm && !(avgdl > 0.0) ? 0u : ctx->ndocs;
     const uint64_t nsl0 = ((uint64_t)N + QT_SLICE - 1) / QT_SLICE;
     const uint64_t per_q = (uint64_t)N * 12 + 2 * (nsl0 * k * 12 + nsl0 * 4) + 8;
     uint64_t G = ctx->query_acc_bytes / per_q;
@@ -2530,7 +2602,7 @@ int tfidf_ctx_query(tfidf_ctx* ctx, const tfidf_queries* qs, uint32_t k, tfidf_h
     }
     std::vector<uint64_t> h_s((size_t)G * k), h_nm(G);
     std::vector<uint32_t> h_id((size_t)G * k), h_n(G);
-    struct Post { uint32_t rank, q, w; };
+    struct Post { uint32_t rank, q, w, term; };
     std::vector<Post> posts;
     std::vector<uint32_t> tab;
     for (uint32_t g0 = 0; N && g0 < nq; g0 += (uint32_t)G) {
@@ -2538,7 +2610,7 @@ int tfidf_ctx_query(tfidf_ctx* ctx, const tfidf_queries* qs, uint32_t k, tfidf_h
         posts.clear();
         for (uint32_t q = 0; q < gn; ++q)
             for (uint64_t x = qt_off[g0 + q]; x < qt_off[g0 + q + 1]; ++x)
-                if (rank[qt_term[x]] != QUERY_NO_TERM) posts.push_back(Post{rank[qt_term[x]], q, qt_w[x]});
+                if (rank[qt_term[x]] != QUERY_NO_TERM) posts.push_back(Post{rank[qt_term[x]], q, qt_w[x], qt_term[x]});
         if (posts.empty()) continue;   /* no term of the group is in the vocabulary: no hits */
         if (posts.size() > 0x7FFFFFFFull) return TFIDF_E_CAPACITY;
         ++qi.ngroups;
@@ -2547,15 +2619,22 @@ int tfidf_ctx_query(tfidf_ctx* ctx, const tfidf_queries* qs, uint32_t k, tfidf_h
         uint32_t nG = 0;
         for (size_t i = 0; i < posts.size(); ++i) nG += i == 0 || posts[i].rank != posts[i - 1].rank;
         const uint32_t nP = (uint32_t)posts.size();
-        tab.assign((size_t)2 * nG + 1 + 2 * (size_t)nP, 0);
+        /* BM25: the weights are binary64 W(q,t) = fl(w * idf), at the next even word */
+        const size_t w_at = (size_t)2 * nG + 1 + nP + (bm ? (nP + 1) & 1u : 0u);
+        tab.assign(w_at + (bm ? 2 : 1) * (size_t)nP, 0);
         uint32_t* gterm = tab.data();
         uint32_t* poff = gterm + nG;
         uint32_t* pq = poff + nG + 1;
-        uint32_t* pw = pq + nP;
+        uint32_t* pw = gterm + w_at;
         for (uint32_t i = 0, t = 0; i < nP; ++i) {
             if (i == 0 || posts[i].rank != posts[i - 1].rank) { gterm[t] = posts[i].rank; poff[t] = i; ++t; }
             pq[i] = posts[i].q;
-            pw[i] = posts[i].w;
+            if (bm) {
+                const double W = (double)posts[i].w * idf[posts[i].term];
+                memcpy(pw + 2 * (size_t)i, &W, 8);
+            } else {
+                pw[i] = posts[i].w;
+            }
         }
         poff[nG] = nP;
         ENSURE(ctx->q_tab, tab.size() * 4 + 16);
@@ -2572,7 +2651,7 @@ int tfidf_ctx_query(tfidf_ctx* ctx, const tfidf_queries* qs, uint32_t k, tfidf_h
         sa.ngterm = nG;
         sa.post_off = sa.gterm + nG;
         sa.post_q = sa.post_off + nG + 1;
-        sa.post_w = sa.post_q + nP;
+        sa.post_w = sa.gterm + w_at;
         sa.tab_words = tab.size() <= 0xFFFFFFFFull ? (uint32_t)tab.size() : 0u;
         sa.nq = gn;
         sa.acc = ctx->q_acc.as<double>();
@@ -2580,7 +2659,36 @@ int tfidf_ctx_query(tfidf_ctx* ctx, const tfidf_queries* qs, uint32_t k, tfidf_h
         sa.big_list = ctx->q_big.as<uint32_t>();
         sa.big_count = (uint32_t*)(d_nm + G);
         HIPCHK(hipEventRecord(ctx->ev_q[0], s));
-        if (launch_query_score(sa, ctx->ncu, s)) { HIPCHK(hipGetLastError()); return TFIDF_E_HIP; }
+        if (bm) {
+            BScoreArgs ba{};
+            ba.out_off = sa.out_off;
+            ba.out_term = sa.out_term;
+            ba.out_cnt = ctx->out_cnt.as<uint32_t>();
+            ba.order = ctx->order;
+            ba.doc_size = ctx->doc_size.as<uint32_t>();
+            ba.ndocs = N;
+            ba.npairs = sa.npairs;
+            ba.gterm = sa.gterm;
+            ba.ngterm = nG;
+            ba.post_off = sa.post_off;
+            ba.post_q = sa.post_q;
+            ba.post_w = (const double*)(sa.gterm + w_at);
+            ba.tab_words = sa.tab_words;
+            ba.nq = gn;
+            ba.k1 = bm->k1;
+            ba.b = bm->b;
+            ba.avgdl = avgdl;
+            ba.k1_plus_1 = bm->k1 + 1.0;
+            ba.one_minus_b = 1.0 - bm->b;
+            ba.acc = sa.acc;
+            ba.cnt = sa.cnt;
+            ba.big_list = sa.big_list;
+            ba.big_count = sa.big_count;
+            if (launch_bm25_score(ba, ctx->ncu, s)) { HIPCHK(hipGetLastError()); return TFIDF_E_HIP; }
+        } else if (launch_query_score(sa, ctx->ncu, s)) {
+            HIPCHK(hipGetLastError());
+            return TFIDF_E_HIP;
+        }
         HIPCHK(hipEventRecord(ctx->ev_q[1], s));
         /* top-k rounds: the accumulators' slices, then the slices' lists until one is left */
         DevBuf* cand[2] = {&ctx->q_cand0, &ctx->q_cand1};
@@ -2642,13 +2750,40 @@ int tfidf_ctx_query(tfidf_ctx* ctx, const tfidf_queries* qs, uint32_t k, tfidf_h
         }
     }
     qi.ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - wall0).count();
-    ctx->qinfo = qi;
+    if (bm) {
+        tfidf_bm25_info bi{};
+        bi.nqueries = qi.nqueries; bi.k = qi.k; bi.nterms = qi.nterms; bi.nterms_found = qi.nterms_found;
+        bi.ngroups = qi.ngroups; bi.group_queries = qi.group_queries; bi.acc_bytes = qi.acc_bytes;
+        bi.ms_lookup = qi.ms_lookup; bi.ms_score = qi.ms_score; bi.ms_topk = qi.ms_topk; bi.ms_total = qi.ms_total;
+        bi.avgdl = avgdl;
+        ctx->binfo = bi;
+    } else {
+        ctx->qinfo = qi;
+    }
     guard.h = nullptr;
     return TFIDF_OK;
 }
 
 extern "C" int tfidf_query(tfidf_ctx* ctx, const tfidf_queries* queries, uint32_t k, tfidf_hits* out) {
     return tfidf_ctx_query(ctx, queries, k, out, nullptr, nullptr);
+}
+
+extern "C" int tfidf_query_bm25(tfidf_ctx* ctx, const tfidf_queries* queries, uint32_t k, const tfidf_bm25_params* params,
+                                tfidf_hits* out) {
+    if (!ctx || !queries || !out) return TFIDF_E_INVAL;
+    Bm25Call bm{};
+    const int rc = tfidf_bm25_params_check(params, &bm);
+    if (rc) return rc;
+    return tfidf_ctx_query(ctx, queries, k, out, nullptr, nullptr, &bm);
+}
+
+extern "C" int tfidf_last_bm25_info(const tfidf_ctx* ctx, tfidf_bm25_info* info) {
+    if (!ctx || !info || info->size < sizeof(uint64_t)) return TFIDF_E_INVAL;
+    const uint64_t n = info->size < sizeof(tfidf_bm25_info) ? info->size : sizeof(tfidf_bm25_info);
+    tfidf_bm25_info o = ctx->binfo;
+    o.size = n;
+    memcpy(info, &o, (size_t)n);
+    return TFIDF_OK;
 }
 
 extern "C" int tfidf_last_query_info(const tfidf_ctx* ctx, tfidf_query_info* info) {

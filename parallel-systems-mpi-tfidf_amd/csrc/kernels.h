@@ -400,6 +400,37 @@ struct QTopkArgs {
 };
 int launch_query_topk(const QTopkArgs& a, uint32_t nq, hipStream_t s);
 
+/* ---- BM25 scoring over the resident result (bm25.hip, tfidf_query_bm25) ---- */
+/* out[i] = df[rank[i]] (0 where rank[i] is QUERY_NO_TERM): the found terms' global df */
+int launch_bm25_df(const uint32_t* rank, uint32_t n, const uint32_t* df, uint32_t V, uint32_t* out, hipStream_t s);
+/* one group of nq <= QG_MAX queries, as QScoreArgs, with binary64 weights W(q,t): the table is
+ * one block from gterm on (gterm, post_off, post_q as u32 words, then post_w at an even word).
+ * A match reads out_cnt; the document's normaliser comes from doc_size through order. */
+struct BScoreArgs {
+    const uint64_t* out_off;
+    const uint32_t* out_term;
+    const uint32_t* out_cnt;
+    const uint32_t* order;       /* output position -> document index */
+    const uint32_t* doc_size;    /* by document index */
+    uint32_t ndocs;
+    uint64_t npairs;
+    const uint32_t* gterm;
+    uint32_t ngterm;
+    const uint32_t* post_off;
+    const uint32_t* post_q;
+    const double* post_w;
+    uint32_t tab_words;          /* u32 words of the whole block (0: do not stage it) */
+    uint32_t nq;
+    double k1, b, avgdl;         /* avgdl > 0 */
+    double k1_plus_1;            /* fl(k1 + 1.0) */
+    double one_minus_b;          /* fl(1.0 - b) */
+    double* acc;
+    uint32_t* cnt;
+    uint32_t* big_list;          /* [ndocs] scratch: output positions of documents over QS_BIG pairs */
+    uint32_t* big_count;
+};
+int launch_bm25_score(const BScoreArgs& a, uint32_t ncu, hipStream_t s);
+
 /* ---- per-document top-k terms over the resident result (terms.hip, tfidf_top_terms) ---- */
 #define TERMS_NO_POS 0xFFFFFFFFu
 /* requested global document ids -> output positions (TERMS_NO_POS: not in this shard): a binary

@@ -62,8 +62,19 @@ hipStream_t tfidf_ctx_stream(const tfidf_ctx* ctx);
 /* engine.cpp: tfidf_query that also reports which query terms the shard's vocabulary holds:
  * found[found_off[q] + i] for the i-th distinct term of query q in first-occurrence order
  * (the same numbering on every rank: tfidf_group_query counts a term found by any rank once) */
+struct Bm25Call;
 int tfidf_ctx_query(tfidf_ctx* ctx, const tfidf_queries* queries, uint32_t k, tfidf_hits* out,
-                    std::vector<uint8_t>* found, std::vector<uint64_t>* found_off);
+                    std::vector<uint8_t>* found, std::vector<uint64_t>* found_off, const Bm25Call* bm = nullptr);
+/* engine.cpp: tfidf_query_bm25 is tfidf_ctx_query with validated parameters (bm non-null: the
+ * scoring pass is bm25.hip's, the counters go to tfidf_last_bm25_info).  avgdl 0: this
+ * context's own average */
+struct Bm25Call {
+    double k1, b, avgdl;
+};
+/* TFIDF_E_INVAL unless params (NULL: the defaults) are as include/tfidf.h requires */
+int tfidf_bm25_params_check(const tfidf_bm25_params* params, Bm25Call* out);
+/* L = the exact sum of docSize over the context's documents, n = the documents it holds */
+int tfidf_ctx_bm25_lengths(tfidf_ctx* ctx, uint64_t* L, uint64_t* n);
 
 /* engine.cpp: the two halves of tfidf_group_similar on one shard.  Export: the rows' documents
  * as this shard holds them (pos UINT32_MAX: it does not; the row is empty): row i's vector is

@@ -25,8 +25,14 @@
  *                 to the hits file as "q<i>\tdoc<N>\t%.16f" lines (i 1-based, score
  *                 descending, then document id ascending; a query without hits writes nothing);
  *   --top K       hits per query (default 10, at most TFIDF_QUERY_MAX_K);
- *   --hits FILE   the hits file (default hits.txt).
- * With several shards the ranks' hits are merged (tfidf_group_query).
+ *   --hits FILE   the hits file (default hits.txt);
+ *   --bm25        rank by Okapi BM25 (tfidf_query_bm25) instead of the summed TF-IDF scores:
+ *                 the same hits file and line format, the scores are BM25's;
+ *   --bm25-k1 X   its term-frequency saturation (default 1.2, X >= 0);
+ *   --bm25-b Y    its length normalisation (default 0.75, 0 <= Y <= 1); the average document
+ *                 length is the corpus's own.  Either parameter implies --bm25; any of the
+ *                 three without --query is a usage error (exit 2).
+ * With several shards the ranks' hits are merged (tfidf_group_query / tfidf_group_query_bm25).
  *
  * Keywords (the k best-scoring words of every document, tfidf_top_terms):
  *   --keywords K          after output.txt (and after the hits file of --query), one line
@@ -90,7 +96,9 @@ static struct {
     const char* file;   /* NULL: no retrieval, behaviour and bytes as without the option */
     const char* hits;
     uint32_t top;
-} g_query = {NULL, "hits.txt", 10};
+    int bm25;           /* 0: the summed TF-IDF scores, bytes as without the option */
+    double k1, b;
+} g_query = {NULL, "hits.txt", 10, 0, TFIDF_BM25_DEFAULT_K1, TFIDF_BM25_DEFAULT_B};
 
 /* the query file's lines as one batch (tfidf_queries): q_off at the line starts */
 static int load_queries(uint8_t** bytes, uint64_t* nbytes, uint64_t** off, uint32_t* nq) {
@@ -138,7 +146,16 @@ static int run_queries(tfidf_ctx* ctx, tfidf_group* g) {
     qs.q_off = off;
     tfidf_hits h;
     memset(&h, 0, sizeof(h));
-    rc = g ? tfidf_group_query(g, &qs, g_query.top, &h) : tfidf_query(ctx, &qs, g_query.top, &h);
+    if (g_query.bm25) {
+        tfidf_bm25_params bp;
+        memset(&bp, 0, sizeof(bp));
+        bp.size = sizeof(bp);
+        bp.k1 = g_query.k1;
+        bp.b = g_query.b;
+        rc = g ? tfidf_group_query_bm25(g, &qs, g_query.top, &bp, &h) : tfidf_query_bm25(ctx, &qs, g_query.top, &bp, &h);
+    } else {
+        rc = g ? tfidf_group_query(g, &qs, g_query.top, &h) : tfidf_query(ctx, &qs, g_query.top, &h);
+    }
     if (!rc) {
         FILE* f = fopen(g_query.hits, "w");
         if (!f) printf("Error Opening File: %s\n", g_query.hits);
@@ -397,6 +414,18 @@ int main(int argc, char** argv) {
             if (k < 1 || k > (long)TFIDF_QUERY_MAX_K) { fprintf(stderr, "tfidf: --top takes 1..%u\n", TFIDF_QUERY_MAX_K); return 2; }
             g_query.top = (uint32_t)k;
         }
+        else if (!strcmp(argv[i], "--bm25")) g_query.bm25 = 1;
+        else if ((!strcmp(argv[i], "--bm25-k1") || !strcmp(argv[i], "--bm25-b")) && i + 1 < argc) {
+            const int is_b = !strcmp(argv[i], "--bm25-b");
+            char* end = NULL;
+            const double v = strtod(argv[++i], &end);
+            if (end == argv[i] || *end || !(v >= 0.0) || !(is_b ? v <= 1.0 : v <= TFIDF_BM25_MAX_K1)) {
+                fprintf(stderr, "tfidf: --bm25-k1 takes a number >= 0, --bm25-b one in 0..1\n");
+                return 2;
+            }
+            if (is_b) g_query.b = v; else g_query.k1 = v;
+            g_query.bm25 = 1;   /* a BM25 parameter asks for BM25 */
+        }
         else if (!strcmp(argv[i], "--keywords-file") && i + 1 < argc) g_keywords.file = argv[++i];
         else if (!strcmp(argv[i], "--keywords") && i + 1 < argc) {
             const long k = atol(argv[++i]);
@@ -412,13 +441,17 @@ int main(int argc, char** argv) {
         }
         else {
             fprintf(stderr, "usage: tfidf [--debug-jobs] [--stats] [--gpus N] [--shards K] [--device D] "
-                            "[--input DIR] [--output FILE] [--query FILE [--top K] [--hits FILE]] "
+                            "[--input DIR] [--output FILE] [--query FILE [--top K] [--hits FILE] [--bm25 [--bm25-k1 X] [--bm25-b Y]]] "
                             "[--keywords K [--keywords-file FILE]] "
                             "[--similar K [--similar-docs FILE] [--similar-file FILE]]\n"
                             "  --similar K without --similar-docs searches for every document: "
                             "ceil(N / group) scans of the scored pairs, group <= 64\n");
             return 2;
         }
+    }
+    if (g_query.bm25 && !g_query.file) {   /* nothing to rank: say so instead of ignoring the switch */
+        fprintf(stderr, "tfidf: --bm25, --bm25-k1 and --bm25-b need --query FILE\n");
+        return 2;
     }
     /* TFIDF.c:100-103 before anything touches the GPU */
     DIR* d = opendir(indir);

@@ -41,6 +41,7 @@ EXPORTS = [
     "tfidf_query", "tfidf_hits_free", "tfidf_group_query", "tfidf_last_query_info",
     "tfidf_top_terms", "tfidf_doc_terms_free", "tfidf_group_top_terms", "tfidf_last_terms_info",
     "tfidf_similar", "tfidf_neighbors_free", "tfidf_group_similar", "tfidf_last_similar_info",
+    "tfidf_query_bm25", "tfidf_group_query_bm25", "tfidf_last_bm25_info",
 ]
 QUERY_MAX_K = 1024  # TFIDF_QUERY_MAX_K
 TERMS_MAX_K = 1024  # TFIDF_TERMS_MAX_K
@@ -113,6 +114,14 @@ class QueryInfo(C.Structure):
         ("acc_bytes", C.c_uint64), ("ms_lookup", C.c_double), ("ms_score", C.c_double), ("ms_topk", C.c_double),
         ("ms_total", C.c_double),
     ]
+
+
+class Bm25Params(C.Structure):
+    _fields_ = [("size", C.c_uint64), ("k1", C.c_double), ("b", C.c_double), ("avgdl", C.c_double)]
+
+
+class Bm25Info(C.Structure):
+    _fields_ = QueryInfo._fields_ + [("avgdl", C.c_double)]
 
 
 class DocTerms(C.Structure):
@@ -222,6 +231,10 @@ def lib() -> C.CDLL:
         L.tfidf_hits_free.argtypes = [C.POINTER(Hits)]
         L.tfidf_hits_free.restype = None
         L.tfidf_last_query_info.argtypes = [C.c_void_p, C.POINTER(QueryInfo)]
+        L.tfidf_query_bm25.argtypes = [C.c_void_p, C.POINTER(Queries), C.c_uint32, C.POINTER(Bm25Params), C.POINTER(Hits)]
+        L.tfidf_group_query_bm25.argtypes = [C.c_void_p, C.POINTER(Queries), C.c_uint32, C.POINTER(Bm25Params),
+                                             C.POINTER(Hits)]
+        L.tfidf_last_bm25_info.argtypes = [C.c_void_p, C.POINTER(Bm25Info)]
         L.tfidf_top_terms.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(DocTerms)]
         L.tfidf_group_top_terms.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(DocTerms)]
         L.tfidf_doc_terms_free.argtypes = [C.POINTER(DocTerms)]
@@ -254,8 +267,9 @@ def _ptr(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
-def _query(fn, handle, queries, k: int, what: str) -> dict:
-    """One batch through tfidf_query / tfidf_group_query: queries are bytes objects."""
+def _query(fn, handle, queries, k: int, what: str, params=None) -> dict:
+    """One batch through tfidf_query / tfidf_group_query (or, with params, their BM25 forms):
+    queries are bytes objects."""
     data = np.frombuffer(b"".join(queries), dtype=np.uint8)
     off = np.zeros(len(queries) + 1, dtype=np.uint64)
     if len(queries):
@@ -266,7 +280,10 @@ def _query(fn, handle, queries, k: int, what: str) -> dict:
     qs.q_off = off.ctypes.data
     qs.nqueries = len(queries)
     h = Hits()
-    _chk(fn(handle, C.byref(qs), k, C.byref(h)), what)
+    if params is None:
+        _chk(fn(handle, C.byref(qs), k, C.byref(h)), what)
+    else:
+        _chk(fn(handle, C.byref(qs), k, C.byref(params), C.byref(h)), what)
     try:
         nq = int(h.nqueries)
 
@@ -281,6 +298,13 @@ def _query(fn, handle, queries, k: int, what: str) -> dict:
         }
     finally:
         lib().tfidf_hits_free(C.byref(h))
+
+
+def _bm25_params(k1: float, b: float, avgdl: float) -> Bm25Params:
+    p = Bm25Params()
+    p.size = C.sizeof(Bm25Params)
+    p.k1, p.b, p.avgdl = k1, b, avgdl
+    return p
 
 
 def _top_terms(fn, handle, k: int, docs, what: str, words: bool = True) -> dict:
@@ -510,6 +534,20 @@ class Engine:
         _chk(lib().tfidf_last_query_info(self.h, C.byref(q)), "tfidf_last_query_info")
         return {k: getattr(q, k) for k, _ in QueryInfo._fields_ if k != "size"}
 
+    def query_bm25(self, queries, k: int = 10, k1: float = 1.2, b: float = 0.75, avgdl: float = 0.0) -> dict:
+        """Engine.query ranked by Okapi BM25 (tfidf_query_bm25); avgdl 0: this shard's own
+        average document length.  The same dict, plus the avgdl used."""
+        res = _query(lib().tfidf_query_bm25, self.h, queries, k, "tfidf_query_bm25", _bm25_params(k1, b, avgdl))
+        res["avgdl"] = self.bm25_info()["avgdl"]
+        return res
+
+    def bm25_info(self) -> dict:
+        """Counters and device times of the last query_bm25 (tfidf_last_bm25_info)."""
+        q = Bm25Info()
+        q.size = C.sizeof(Bm25Info)
+        _chk(lib().tfidf_last_bm25_info(self.h, C.byref(q)), "tfidf_last_bm25_info")
+        return {k: getattr(q, k) for k, _ in Bm25Info._fields_ if k != "size"}
+
     def top_terms(self, k: int = 10, docs=None, words: bool = True) -> dict:
         """The k best-scoring words of each document of this shard (tfidf_top_terms).  docs:
         None for every document in output order, or global document ids (rows in that order;
@@ -650,6 +688,14 @@ class Group:
     def query(self, queries, k: int = 10) -> dict:
         """Top-k documents over all shards (tfidf_group_query); see Engine.query."""
         return _query(lib().tfidf_group_query, self.h, queries, k, "tfidf_group_query")
+
+    def query_bm25(self, queries, k: int = 10, k1: float = 1.2, b: float = 0.75, avgdl: float = 0.0) -> dict:
+        """BM25 ranking over all shards (tfidf_group_query_bm25); avgdl 0: the average over
+        every shard's documents.  See Engine.query_bm25."""
+        res = _query(lib().tfidf_group_query_bm25, self.h, queries, k, "tfidf_group_query_bm25",
+                     _bm25_params(k1, b, avgdl))
+        res["avgdl"] = self.ranks[0].bm25_info()["avgdl"]   # every rank scored with the same value
+        return res
 
     def top_terms(self, k: int = 10, docs=None, words: bool = True) -> dict:
         """The k best-scoring words of each document over all shards (tfidf_group_top_terms);
