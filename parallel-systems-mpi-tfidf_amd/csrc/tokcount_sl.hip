@@ -17,9 +17,12 @@
  *   - every position is a signed 32-bit offset from the chunk base b0 = chunk_start & ~15;
  *   - the vocabulary pair: terms are inserted from an even home slot (dev_vocab.h), so the
  *     two slots a round loads never wrap;
- *   - a round is a straight line for the common case (both vocabulary slots compared, the
- *     LDS bucket read, one CAS and one add per lane whatever the outcome: branching on the
- *     outcome measured 0.16 ms slower on c2); a claim lost to another lane of the same
+ *   - a round is a straight line for the common case (both vocabulary slots compared, one
+ *     CAS at the key's preferred LDS slot and one add per lane whatever the outcome:
+ *     branching on the outcome measured 0.16 ms slower on c2); keys whose preferred slot
+ *     holds another key (18.6 % of c2's tokens) gather on a per-wave LDS stack and are
+ *     counted 64 at a time by the full form (lds_count_full: the bucket read, eight compares,
+ *     one CAS and one add; c2 K1 1.52 -> 1.45 ms).  There a claim lost to another lane of the same
  *     round (1.4 per round on c2: 64 lanes over 448 buckets) retries inline at the next
  *     slots, and a full home bucket is probed once more inline at the next bucket (c2 K1
  *     1.96 -> 1.76 ms: the out-of-line call had run in 69 % of the rounds); the rest
@@ -40,7 +43,8 @@
  * round is counted.  At the group end the table is flushed as coalesced records (complete
  * documents) or partial records (documents split across chunks, merged by finalize.hip).
  *
- * LDS: 28 KiB table + ~10 KiB walk/document state -> four workgroups (16 waves) per CU.
+ * LDS: 28 KiB table + ~10 KiB walk/document state + 2 KiB of deferred keys -> four
+ * workgroups (16 waves) per CU.
  * Requires a 16-byte aligned corpus base and a vocabulary of <= 2^22 slots.
  */
 #include "dev_common.h"
@@ -91,6 +95,7 @@ constexpr uint32_t LEN_LONG = 31u;
 constexpr uint32_t SLOT_BITS = 25;      /* vocabulary slots < 2^25 (K1_SL_MAX_CAP; the LDS key's document
                                            field shrinks as the slot field grows: gcap below) */
 constexpr int PMAX = 16;
+constexpr uint32_t PQ = 128;            /* deferred keys a wave holds at most: < 64 after a drain + one round's 64 */
 #ifdef SL_STAMPS
 constexpr int SL_NPH = 12;              /* diagnostic phases (SL_STAMPS) */
 #endif                /* LDS buckets probed before a key becomes a partial record */
@@ -125,6 +130,8 @@ struct SlShared {
     unsigned long long rec_base, part_base;
     unsigned long long next_chunk;      /* persistent form: the workgroup's next chunk (claimed ahead) */
     uint32_t step_next;                 /* the group's next unclaimed step */
+    uint32_t pq[NWAVE][PQ];             /* a wave's deferred keys (lds_count) */
+    uint32_t wcl[NWAVE];                /* each wave's claims of the group, as last published (claims_over) */
 };
 
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
@@ -552,13 +559,39 @@ __device__ __forceinline__ void sl_flush_few(SlShared& S, const K1Out* o, uint32
 #define SL_STC
 #define SL_STC_ARG
 #endif
-__device__ __forceinline__ void lds_count(SlShared& S, const K1Out* o, uint32_t key, uint32_t& wclaims, uint32_t gd0,
-                                          uint32_t sb SL_STC_ARG) {
+/* Overflow mode.  A wave below its share of the claim budget (WAVE_CLAIMS) claims freely; one
+ * past it goes on while the group as a whole is inside the budget, by the counts every wave
+ * publishes after each round.  (A per-wave limit alone put a group into overflow mode when
+ * one wave had taken a step more than the others: its documents then leave as partial
+ * records and are merged for nothing.)  A published count lags its wave by one round's claims
+ * at most (64), and a wave claims at most 64 after a test, so the table holds fewer than
+ * NWAVE * WAVE_CLAIMS + NWAVE * 64 keys: the bound the per-wave limit gave. */
+template <bool FAST> __device__ __forceinline__ bool claims_over(SlShared& S, uint32_t wclaims) {
+    if (wclaims < WAVE_CLAIMS) return false;   /* wave-uniform */
+    if (!FAST) return true;                    /* the full count alone (lds_count): the per-wave limit */
+    const uint32_t w = threadIdx.x >> 6;
+    uint32_t sum = wclaims;
+#pragma unroll
+    for (uint32_t k = 0; k < (uint32_t)NWAVE; ++k)
+        sum += k == w ? 0u : __hip_atomic_load(&S.wcl[k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    return sum >= (uint32_t)NWAVE * WAVE_CLAIMS;
+}
+__device__ __forceinline__ void claims_publish(SlShared& S, uint32_t wclaims) {
+    __hip_atomic_store(&S.wcl[threadIdx.x >> 6], wclaims, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+}
+
+/* The full count of 64 keys: the drain of the keys lds_count deferred (below), behind its
+ * wave-uniform test.  Inline: as an out-of-line function every call saved and restored the
+ * live scalars (c2 K1 1.47-1.52 ms against 1.42-1.45 inline, profiles/k1_fastcount_ab.txt).
+ * Returns the wave's claims. */
+template <bool FAST>
+__device__ __forceinline__ uint32_t lds_count_full(SlShared& S, const K1Out* o, uint32_t key, uint32_t wclaims, uint32_t gd0,
+                                                uint32_t sb SL_STC_ARG) {
     /* The LDS count, straight-line: ONE bucket read (two ds_read_b128), then one CAS
      * and one add per lane whatever the case — a match CASes its own key over itself,
      * a new key claims a free slot (CAS from 0), every other lane CASes against a
      * value no slot holds (0x7FFFFFFF: keys carry bit 31) and adds 0 */
-    const bool over = wclaims >= WAVE_CLAIMS;
+    const bool over = claims_over<FAST>(S, wclaims);
     const uint32_t b = bkt_hash(key);
     const BktK kk = bkt_read(S.TK, b);
     /* the key's slot: at most one slot matches, so its index bits are ORs of the lane masks
@@ -646,7 +679,79 @@ __device__ __forceinline__ void lds_count(SlShared& S, const K1Out* o, uint32_t 
     if (__ballot(slow) != 0ull) {
         if (slow) claims = bkt_slow(S.TK, S.TC, S.dpart, o, key, b, over, gd0, sb);
     }
-    wclaims += (uint32_t)__popcll(__ballot(claims != 0u));
+    return wclaims + (uint32_t)__popcll(__ballot(claims != 0u));
+}
+
+__device__ __forceinline__ void pq_fence() {   /* a wave's own LDS stores before its loads of them */
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+/* The common round: ONE CAS at the key's preferred slot (bkt_hash, bkt_pref) and one add, no
+ * bucket read.  That slot is the first of every walk for the key and slots are never emptied
+ * during a group, so the CAS (compare 0, store the key) settles two of three cases:
+ *   - it returns the key: the key's slot (no other slot can hold it) — a hit;
+ *   - it returns 0: the key was nowhere in the table (a walker placing it earlier would have
+ *     taken this slot, empty ever since) and now sits where every later walk looks first;
+ *   - it returns another key: the key is displaced.  A foreign preferred slot stays foreign,
+ *     so such a key is deferred every time, on every wave, and only lds_count_full ever
+ *     places it: the lane pushes it on the wave's LDS stack, and a full 64 of them are
+ *     counted by lds_count_full in one round (counting commutes within a group).
+ * Same-key lanes of one round: the first CAS claims, the others get the key back and hit.
+ * A fast claim racing a drain walker's CAS on the same empty slot makes one of them lose: the
+ * walker retries at its next slot as after any lost claim, the fast lane defers.
+ * Empty lanes and overflow mode compare against a value no slot holds (0x7FFFFFFF): they
+ * never store, but a key already in its preferred slot still hits.
+ * Claim budget: `over` is tested before every round, this one or a drain, and a round claims
+ * at most 64 slots, so the table stays below TB - 2 * NT - 64 + NWAVE * 64 <= TB - NT keys
+ * (claims_over): inside the margin WAVE_CLAIMS leaves. */
+template <bool FAST>
+__device__ __forceinline__ void lds_count(SlShared& S, const K1Out* o, uint32_t key, uint32_t& wclaims, uint32_t& npend,
+                                          uint32_t* pq, uint32_t gd0, uint32_t sb SL_STC_ARG) {
+    if (!FAST) {   /* high-cardinality tables (launch_tokcount_sl): every round by the full count */
+        wclaims = lds_count_full<false>(S, o, key, wclaims, gd0, sb SL_STC);
+        return;
+    }
+    static_assert(NWAVE * 64 <= NT + 64, "claim overshoot inside WAVE_CLAIMS' margin");
+    const bool over = claims_over<FAST>(S, wclaims);
+    const uint32_t idx = bkt_slot(bkt_hash(key), bkt_pref(key));
+    const uint32_t old = atomicCAS(&S.TK[idx], (key != 0u && !over) ? 0u : 0x7FFFFFFFu, key);
+    const bool ok = key != 0u && (old == key || (!over && old == 0u));
+    atomicAdd(&S.TC[idx], ok ? 1u : 0u);
+    const uint64_t cm = __ballot(ok && old == 0u);
+    const bool slow = key != 0u && !ok;
+    wclaims += (uint32_t)__popcll(cm);
+    const uint64_t sm = __ballot(slow);
+#ifdef SL_STAMPS
+    ++st_cnt[8];
+    st_cnt[9] += (uint32_t)__popcll(__ballot(ok && old != 0u));
+    st_cnt[10] += (uint32_t)__popcll(cm);
+    st_cnt[11] += (uint32_t)__popcll(sm);
+#endif
+    if (sm != 0ull) {
+        if (slow) pq[npend + __builtin_amdgcn_mbcnt_hi((uint32_t)(sm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)sm, 0u))] = key;
+        npend += (uint32_t)__popcll(sm);   /* < 64 + 64 = PQ */
+        if (npend >= 64u) {
+            pq_fence();
+            npend -= 64u;
+            claims_publish(S, wclaims);
+            wclaims = lds_count_full<true>(S, o, pq[npend + (threadIdx.x & 63u)], wclaims, gd0, sb SL_STC);
+        }
+    }
+    claims_publish(S, wclaims);
+}
+/* the group's last deferred keys (fewer than 64: one partial round, padded with key 0) */
+template <bool FAST>
+__device__ __forceinline__ void lds_drain(SlShared& S, const K1Out* o, uint32_t& wclaims, uint32_t& npend, uint32_t* pq,
+                                          uint32_t gd0, uint32_t sb SL_STC_ARG) {
+    while (npend) {
+        pq_fence();
+        const uint32_t m = npend < 64u ? npend : 64u, l = threadIdx.x & 63u;
+        npend -= m;
+        wclaims = lds_count_full<FAST>(S, o, l < m ? pq[npend + l] : 0u, wclaims, gd0, sb SL_STC);
+        claims_publish(S, wclaims);
+    }
 }
 
 __device__ __forceinline__ uint32_t perm_sel(uint32_t n, uint32_t k) {
@@ -673,6 +778,7 @@ struct Round {
 
 }  // namespace
 
+template <bool FAST>
 __global__ __launch_bounds__(NT, WG_PER_CU * NT / 256) void k_tokcount_sl(CorpusDev c, const uint64_t* __restrict__ chunk_start,
                                                                const uint32_t* __restrict__ chunk_doc, uint64_t c0,
                                                                uint64_t c1, VocabDev v, const K1Out* __restrict__ o,
@@ -690,10 +796,11 @@ __global__ __launch_bounds__(NT, WG_PER_CU * NT / 256) void k_tokcount_sl(Corpus
      * allocation and its barriers, 11 a round finish's wait for its loads) */
     unsigned long long st_acc[SL_NPH] = {};
     unsigned long long st_t = __builtin_amdgcn_s_memtime(), st_chunks = 0;
-    unsigned long long st_cnt[8] = {};   /* rounds with a slow lane, slow lanes, lost claims, rounds
-                                            still slow after the inline retries, rounds; lanes
-                                            still slow by cause (lost every retry, bucket full,
-                                            overflow mode) */
+    unsigned long long st_cnt[12] = {};  /* drain rounds (lds_count_full): with a slow lane, slow lanes,
+                                            lost claims, still slow after the inline retries, their
+                                            number; lanes still slow by cause (lost every retry, bucket
+                                            full, overflow mode); lds_count: rounds, hits, claims,
+                                            deferred keys */
 #define SL_STAMP(k)                                                         \
     do {                                                                    \
         const unsigned long long t_ = __builtin_amdgcn_s_memtime();         \
@@ -766,6 +873,7 @@ __global__ __launch_bounds__(NT, WG_PER_CU * NT / 256) void k_tokcount_sl(Corpus
         }
         if (tid < GCAP) { S.dsz[tid] = 0; S.dpart[tid] = 0; }
         if (tid == 0) S.step_next = NWAVE;
+        if (tid < NWAVE) S.wcl[tid] = 0;
         lds_barrier();
         if ((uint32_t)tid < ng) S.dfull[tid] = S.gdoc[tid] >= cs_rel && S.gdoc[tid + 1] <= span;
         const int32_t g0 = __builtin_amdgcn_readfirstlane(S.gdoc[0]);
@@ -787,6 +895,8 @@ __global__ __launch_bounds__(NT, WG_PER_CU * NT / 256) void k_tokcount_sl(Corpus
         acc = pend;
         uint32_t fill = 0;             /* wave-uniform: built lanes of acc */
         uint32_t wclaims = 0;          /* this wave's LDS table claims (wave-uniform) */
+        uint32_t npend = 0;            /* this wave's deferred keys in pq (wave-uniform) */
+        uint32_t* const pq = S.pq[wid];
 
         /* pend takes acc's token and issues its vocabulary loads (two rounds whose roles swap
          * instead, to save the copy, made the compiler select between them through scratch) */
@@ -845,7 +955,7 @@ __global__ __launch_bounds__(NT, WG_PER_CU * NT / 256) void k_tokcount_sl(Corpus
             wclaims += (uint32_t)__popcll(__ballot(key == 0x12345u));
             return;
 #endif
-            lds_count(S, o, key, wclaims, gd0, sb SL_STC);
+            lds_count<FAST>(S, o, key, wclaims, npend, pq, gd0, sb SL_STC);
         };
         /* one lane's token into the round being built: its key from the staged bytes */
         auto build = [&](Round& a, uint32_t e, int32_t sbp) {
@@ -1005,6 +1115,7 @@ __global__ __launch_bounds__(NT, WG_PER_CU * NT / 256) void k_tokcount_sl(Corpus
         SL_STAMP(3);
         if (fill) turn();   /* the group's last, partial round */
         finish(pend);   /* drain */
+        lds_drain<FAST>(S, o, wclaims, npend, pq, gd0, sb SL_STC);   /* before the flush's first barrier */
 #ifdef SL_STAMPS
         SL_STAMP(5);
         lds_barrier();   /* (the flush's first barrier, made explicit to time the wait) */
@@ -1041,7 +1152,7 @@ __global__ __launch_bounds__(NT, WG_PER_CU * NT / 256) void k_tokcount_sl(Corpus
         for (int k = 0; k < SL_NPH; ++k) atomicAdd(&o->stamps[k], st_acc[k]);
         atomicAdd(&o->stamps[SL_NPH], st_chunks);
         atomicAdd(&o->stamps[SL_NPH + 1], 1ull);
-        for (int k = 0; k < 8; ++k) atomicAdd(&o->stamps[SL_NPH + 2 + k], st_cnt[k]);
+        for (int k = 0; k < 12; ++k) atomicAdd(&o->stamps[SL_NPH + 2 + k], st_cnt[k]);
     }
 #endif
 }
@@ -1063,6 +1174,14 @@ int launch_tokcount_sl(const CorpusDev& c, const uint64_t* chunk_start, const ui
     }
     const uint64_t wgs = (uint64_t)ncu * WG_PER_CU;
     const uint64_t grid = (c1 - c0) < wgs ? (c1 - c0) : wgs;
-    k_tokcount_sl<<<(unsigned)grid, NT, 0, s>>>(c, chunk_start, chunk_doc, c0, c1, v, o_dev, sbits, gcap);
+    /* Past K1_ST_MAX_CAP slots nearly every token is a new pair and every group runs into
+     * overflow mode: the preferred-slot count has few hits to settle there, and the keys still
+     * deferred when the budget is crossed turn earlier documents into partial records (c4:
+     * 6.8 M -> 8.9 M, merge 3.0 -> 3.2 ms, 76.8 -> 75.8 GB/s, profiles/k1_fastcount_ab.txt), so
+     * such tables keep the full count in every round */
+    if (v.mask + 1 > K1_ST_MAX_CAP)
+        k_tokcount_sl<false><<<(unsigned)grid, NT, 0, s>>>(c, chunk_start, chunk_doc, c0, c1, v, o_dev, sbits, gcap);
+    else
+        k_tokcount_sl<true><<<(unsigned)grid, NT, 0, s>>>(c, chunk_start, chunk_doc, c0, c1, v, o_dev, sbits, gcap);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }

@@ -30,9 +30,15 @@ tot = sum(v[:NPH])
 print(cfg, "K1 ms", round(info["ms_tokcount"], 4), "waves", waves, "chunk visits/wave", round(v[NPH] / waves, 1))
 for k, nm in enumerate(names):
     print("  %-12s %10.0f cycles/wave  %5.1f %%" % (nm, v[k] / waves, 100.0 * v[k] / max(tot, 1)))
-cnt = v[NPH + 2:NPH + 10]
-if len(cnt) == 8 and cnt[4]:
-    print("  rounds %d (per wave %.0f): with a slow lane %.1f %%, slow lanes/round %.2f, lost claims/round %.2f,"
+cnt = v[NPH + 2:NPH + 14]
+if len(cnt) == 12 and cnt[8]:
+    keys = cnt[9] + cnt[10] + cnt[11]
+    print("  lds_count rounds %d (per wave %.0f): keys %d, hits %.1f %%, claims %.1f %%, deferred %.1f %% (%.1f per round);"
+          " drain rounds (lds_count_full) %d, one per %.1f rounds" %
+          (cnt[8], cnt[8] / waves, keys, 100.0 * cnt[9] / max(keys, 1), 100.0 * cnt[10] / max(keys, 1),
+           100.0 * cnt[11] / max(keys, 1), cnt[11] / cnt[8], cnt[4], cnt[8] / max(cnt[4], 1)))
+if len(cnt) == 12 and cnt[4]:
+    print("  drain rounds %d (per wave %.0f): with a slow lane %.1f %%, slow lanes/round %.2f, lost claims/round %.2f,"
           " still slow after the inline retry %.1f %% (SL_RETRY builds)" %
           (cnt[4], cnt[4] / waves, 100.0 * cnt[0] / cnt[4], cnt[1] / cnt[4], cnt[2] / cnt[4], 100.0 * cnt[3] / cnt[4]))
     print("  lanes still slow per round: lost every retry %.3f, bucket full %.3f, overflow mode %.3f" %

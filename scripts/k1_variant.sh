@@ -10,7 +10,7 @@ B=$(basename $SRC .hip)
 mkdir -p $P/build/v_$N
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wall -I/opt/rocm/include -I$P/csrc $D -c $SRC -o $P/build/v_$N/$B.o
 O=""
-for f in prims tokcount tokcount_vs tokcount_sl finalize emit engine group ingest host_io; do
+for f in prims tokcount tokcount_vs tokcount_sl finalize emit query bm25 terms similar engine group ingest host_io; do
   if [ $f = $B ]; then O="$O $P/build/v_$N/$B.o"; else O="$O $P/build/$f.o"; fi
 done
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -o $P/lib/libtfidf_hip_$N.so $O -L/opt/rocm/lib -lrccl -lm -Wl,-rpath,/opt/rocm/lib
