@@ -53,7 +53,14 @@ enum tfidf_status {
  * (TFIDF.c:130-147): document i (0-based, local) is bytes[doc_off[i], doc_off[i+1]).
  * Document boundaries are token boundaries.  Tokens follow fscanf("%s") in the C
  * locale: maximal runs of bytes not in {0x20,0x09..0x0D}; a term is the token's bytes
- * up to its first NUL (strcmp semantics, TFIDF.c:152,172). */
+ * up to its first NUL (strcmp semantics, TFIDF.c:152,172).
+ * The documents are a window of the buffer: doc_off[0] may be greater than 0 and
+ * doc_off[ndocs] less than nbytes.  Bytes outside [doc_off[0], doc_off[ndocs]) belong
+ * to no document and never join a token, whatever they hold (several shards may pass
+ * the same bytes / nbytes with doc_off pointing into one shared offsets array).
+ * A device `bytes` pointer (TFIDF_CORPUS_DEVICE) of any alignment is accepted; one
+ * that is not 16-byte aligned is tokenised by the general kernel (TFIDF_RUN_K1_VS
+ * clear in tfidf_run_info.flags), the result is the same. */
 typedef struct tfidf_corpus {
     const uint8_t*  bytes;
     uint64_t        nbytes;

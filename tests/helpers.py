@@ -1,6 +1,8 @@
 """Shared test helpers: golden fixture loading and result comparison."""
 from __future__ import annotations
 
+import contextlib
+import ctypes as C
 import json
 import os
 
@@ -169,3 +171,148 @@ def check_full_properties(r: dict, ntokens: int, threads: int = 8, chunk: int = 
         x = bytes(tb[int(toff[i]):int(toff[i + 1])]) + b"\t"
         y = bytes(tb[int(toff[i + 1]):int(toff[i + 2])]) + b"\t"
         assert x < y, (i, x, y)
+
+
+# ---- corpus windows: doc_off[0] > 0, doc_off[ndocs] < nbytes, caller-owned device buffers ----
+
+_PAD = b"Qq "
+
+
+def pad_before(n: int) -> bytes:
+    """n padding bytes in front of a window: whole words "Qq" separated by blanks, the last
+    byte (the one just before the window) a letter"""
+    return (_PAD * (n // 3 + 2))[:-1][-n:] if n else b""
+
+
+def pad_after(n: int) -> bytes:
+    """n padding bytes behind a window: the first byte (the one at the window's end) a letter"""
+    return (_PAD * (n // 3 + 2))[:n]
+
+
+def windowed(docs, lead: int, trail: int):
+    """The packed documents between `lead` and `trail` bytes that belong to no document
+    (include/tfidf.h: doc_off[0] > 0, doc_off[ndocs] < nbytes).  The padding holds words of
+    its own, and a letter touches the window on both sides: a token extended over a boundary
+    and a byte counted outside the window both change the result."""
+    data, off = docs_to_arrays(docs)
+    buf = pad_before(lead) + data.tobytes() + pad_after(trail)
+    return np.frombuffer(buf, dtype=np.uint8).copy(), off + np.uint64(lead)
+
+
+_hip = None
+
+
+def hip():
+    """the HIP runtime through ctypes (test plumbing: allocation and copies only)"""
+    global _hip
+    if _hip is None:
+        h = C.CDLL("libamdhip64.so")
+        h.hipMalloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
+        h.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
+        h.hipFree.argtypes = [C.c_void_p]
+        _hip = h
+    return _hip
+
+
+def _to_device(host: np.ndarray) -> int:
+    p = C.c_void_p()
+    assert hip().hipMalloc(C.byref(p), max(host.nbytes, 16)) == 0
+    if host.nbytes:
+        assert hip().hipMemcpy(p, host.ctypes.data, host.nbytes, 1) == 0
+    return p.value
+
+
+@contextlib.contextmanager
+def device_corpus(data, off, ids=None, n_total: int = 0, shift: int = 0):
+    """A tfidf_abi.Corpus with flags = TFIDF_CORPUS_DEVICE in buffers of the caller's own.
+    The bytes lie in an allocation of whole 4 KiB pages with at least 256 bytes of padding
+    words (pad_before / pad_after) on both sides, the corpus base at the allocation's start
+    + 256 + shift: a kernel that reads past an edge of the corpus stays inside the allocation
+    and gives a wrong result.  doc_off and doc_ids are device arrays.  Everything stays
+    allocated until the context exits (text(), fetch(), top_terms and query read long terms
+    from the corpus bytes)."""
+    import tfidf_abi
+    assert 0 <= shift < 16
+    data = np.ascontiguousarray(data, dtype=np.uint8)
+    off = np.ascontiguousarray(off, dtype=np.uint64)
+    ids = None if ids is None else np.ascontiguousarray(ids, dtype=np.uint32)
+    front = 256 + shift
+    total = (front + len(data) + 256 + 4095) & ~4095
+    image = np.frombuffer(pad_before(front) + data.tobytes() + pad_after(total - front - len(data)), dtype=np.uint8)
+    ptrs = []
+    try:
+        ptrs.append(_to_device(image))
+        assert ptrs[0] % 16 == 0
+        ptrs.append(_to_device(off))
+        if ids is not None:
+            ptrs.append(_to_device(ids))
+        assert hip().hipDeviceSynchronize() == 0
+        c = tfidf_abi.Corpus()
+        c.bytes = ptrs[0] + front
+        c.nbytes = len(data)
+        c.doc_off = ptrs[1]
+        c.doc_ids = None if ids is None else ptrs[2]
+        c.ndocs = len(off) - 1
+        c.flags = tfidf_abi.TFIDF_CORPUS_DEVICE
+        c.ndocs_total = n_total
+        yield c
+    finally:
+        hip().hipDeviceSynchronize()
+        for p in ptrs:
+            hip().hipFree(p)
+
+
+# The four tokenize+count (K1) kernel instances and the environment that selects each
+# (read by tfidf_open, so every instance has an Engine of its own).
+K1_INSTANCES = {
+    "sl_fast": {},                              # k_tokcount_sl<true>: the default
+    "sl_full": {"TFIDF_VCAP": "8388608"},       # k_tokcount_sl<false>: past 2^22 vocabulary slots
+    "vs": {"TFIDF_K1": "vs"},                   # k_tokcount_vs: what runs past 2^25 slots
+    "general": {"TFIDF_K1": "general"},         # k_tokcount: what an unaligned corpus base gets
+}
+_K1_ENV = ("TFIDF_K1", "TFIDF_VCAP", "TFIDF_VLOAD", "TFIDF_VLOAD_BIG", "TFIDF_SL_MAXCAP")
+
+
+@contextlib.contextmanager
+def k1_engine(instance: str):
+    """an Engine opened under the instance's environment; the environment is restored as soon
+    as the engine is open"""
+    import tfidf_abi
+    saved = {k: os.environ.pop(k, None) for k in _K1_ENV}
+    os.environ.update(K1_INSTANCES[instance])
+    try:
+        e = tfidf_abi.Engine(0)
+    finally:
+        for k in _K1_ENV:
+            os.environ.pop(k, None)
+            if saved[k] is not None:
+                os.environ[k] = saved[k]
+    try:
+        yield e
+    finally:
+        e.close()
+
+
+def assert_k1_instance(info: dict, instance: str):
+    """the last run (Engine.info()) took the kernel instance it is named for"""
+    import tfidf_abi
+    f, cap = info["flags"], info["vocab_capacity"]
+    if instance == "sl_fast":
+        assert f & tfidf_abi.RUN_K1_SL and cap <= 1 << 22, (f, cap)
+    elif instance == "sl_full":
+        assert f & tfidf_abi.RUN_K1_SL and cap == 1 << 23, (f, cap)
+    elif instance == "vs":
+        assert (f & 3) == 2 and not f & tfidf_abi.RUN_K1_SL, f
+    else:
+        assert instance == "general" and (f & 3) == 0, f
+
+
+def k1_fixture(instances):
+    """a module-scoped fixture over K1 instances: (instance name, its Engine)"""
+    import pytest
+
+    @pytest.fixture(scope="module", params=list(instances))
+    def k1(request):
+        with k1_engine(request.param) as e:
+            yield request.param, e
+    return k1

@@ -76,17 +76,30 @@ def test_overflow_mode_with_deferred_keys(engine):
     assert res["npairs"] == 3400
 
 
-def test_hot_key_from_all_waves(engine):
-    """One term is every second token of a 20 KB document, between 500 distinct others: all
-    four waves count it at one slot."""
+def hot_key_corpus():
+    """(data, off, tokens of the document)"""
     rng = np.random.default_rng(5)
     words = _distinct_words(501, rng, 3, 6)
     hot, others = words[250], words[:250] + words[251:]
     toks = []
     while sum(len(t) + 1 for t in toks) < 20000:
         toks += [hot, others[int(rng.integers(0, 500))]]
-    res = check_vs_oracle(engine, *docs_to_arrays([b" ".join(toks) + b"\n"]))
-    assert int(np.max(res["count"])) == len(toks) // 2
+    return docs_to_arrays([b" ".join(toks) + b"\n"]) + (len(toks),)
+
+
+def test_hot_key_from_all_waves(engine):
+    """One term is every second token of a 20 KB document, between 500 distinct others: all
+    four waves count it at one slot."""
+    data, off, ntoks = hot_key_corpus()
+    res = check_vs_oracle(engine, data, off)
+    assert int(np.max(res["count"])) == ntoks // 2
+
+
+def many_documents_corpus(ndocs):
+    rng = np.random.default_rng(ndocs)
+    pool = _distinct_words(200, rng, 1, 2)
+    docs = [b" ".join(pool[i] for i in rng.integers(0, 200, int(rng.integers(28, 33)))) + b"\n" for _ in range(ndocs)]
+    return docs_to_arrays(docs)
 
 
 @pytest.mark.parametrize("ndocs", [9, 255, 256, 257, 600])
@@ -95,10 +108,7 @@ def test_many_documents_per_group(engine, ndocs):
     document): up to 257 documents are one 24 KiB chunk (the general flush, one group of GCAP
     = 256 documents and one over it), 600 are three chunks of more than GCAP documents each
     (several groups per chunk: the stack's per-group reset)."""
-    rng = np.random.default_rng(ndocs)
-    pool = _distinct_words(200, rng, 1, 2)
-    docs = [b" ".join(pool[i] for i in rng.integers(0, 200, int(rng.integers(28, 33)))) + b"\n" for _ in range(ndocs)]
-    check_vs_oracle(engine, *docs_to_arrays(docs))
+    check_vs_oracle(engine, *many_documents_corpus(ndocs))
 
 
 def test_displaced_keys_wider_slot_field(monkeypatch):

@@ -50,26 +50,38 @@ def test_synthetic_configs_vs_oracle(engine, cfg, scale):
     assert res["npairs"] > 0
 
 
+def document_boundaries_corpus():
+    return docs_to_arrays([b"ab", b"cd", b"ab", b"", b"ab cd"])
+
+
 def test_document_boundaries_split_tokens(engine):
-    data, off = docs_to_arrays([b"ab", b"cd", b"ab", b"", b"ab cd"])
+    data, off = document_boundaries_corpus()
     res = check_vs_oracle(engine, data, off)
     assert res["output_txt"].count(b"\n") == 5
 
 
+def blank_docs_corpus():
+    return docs_to_arrays([b"", b"  \n\t", b"\r\n", b"x"])
+
+
 def test_empty_corpus_and_blank_docs(engine):
-    data, off = docs_to_arrays([b"", b"  \n\t", b"\r\n", b"x"])
+    data, off = blank_docs_corpus()
     res = check_vs_oracle(engine, data, off)
     assert res["npairs"] == 1
 
 
-def test_nul_and_control_bytes(engine):
+def nul_and_control_bytes_corpus():
     docs = [b"ab\x00cd ab \x00zz \x01\x02 a\x01 a\x7f a\xff\xfe",
             b"\x00 \x00\x00 ab\x00 ab\x00\x00x",
             b"a\x08 a\x09a a\x0ea"]
-    check_vs_oracle(engine, *docs_to_arrays(docs))
+    return docs_to_arrays(docs)
 
 
-def test_long_tokens_and_shared_prefixes(engine):
+def test_nul_and_control_bytes(engine):
+    check_vs_oracle(engine, *nul_and_control_bytes_corpus())
+
+
+def long_tokens_corpus():
     rng = np.random.default_rng(7)
     base = b"abcdefghijklmnop"  # 16 bytes
     words = [base, base + b"q", base + b"\x01", base + b"qr" * 40, b"x" * 15, b"x" * 16, b"x" * 17,
@@ -79,10 +91,14 @@ def test_long_tokens_and_shared_prefixes(engine):
     for i in range(6):
         pick = rng.choice(len(words), size=12)
         docs.append(b" ".join(words[j] for j in pick) + b"\n")
-    check_vs_oracle(engine, *docs_to_arrays(docs))
+    return docs_to_arrays(docs)
 
 
-def test_tokens_across_windows_and_chunks(engine):
+def test_long_tokens_and_shared_prefixes(engine):
+    check_vs_oracle(engine, *long_tokens_corpus())
+
+
+def windows_and_chunks_corpus():
     # one big document (> BIG_DOC, split across chunks) whose tokens straddle the 4 KiB
     # windows and chunk boundaries (24 KiB for tokcount_sl, 12 KiB for the other K1
     # kernels) at every offset
@@ -96,7 +112,11 @@ def test_tokens_across_windows_and_chunks(engine):
         parts.append(w + sep)
         n += L + len(sep)
     docs = [b"".join(parts), b"aa bb", b"".join(parts[:5000])]
-    check_vs_oracle(engine, *docs_to_arrays(docs))
+    return docs_to_arrays(docs)
+
+
+def test_tokens_across_windows_and_chunks(engine):
+    check_vs_oracle(engine, *windows_and_chunks_corpus())
 
 
 def test_many_tiny_documents(engine):
@@ -247,14 +267,18 @@ def _distinct_words(n, rng, lo=2, hi=12):
     return sorted(words)
 
 
-def test_doc_with_more_pairs_than_lds_table(engine):
-    """One ~60 KB document (a single chunk) with ~7000 distinct terms: the open document
-    overflows the LDS table (partial flushes) and exceeds K5's in-LDS sort size."""
+def more_pairs_than_lds_table_corpus():
     rng = np.random.default_rng(11)
     words = _distinct_words(7000, rng)
     toks = [words[i] for i in rng.permutation(len(words))] + [words[i] for i in rng.integers(0, 300, 1500)]
     docs = [b"x y z\n", b" ".join(toks)[:63000] + b"\n", b"x q\n"]
-    check_vs_oracle(engine, *docs_to_arrays(docs))
+    return docs_to_arrays(docs)
+
+
+def test_doc_with_more_pairs_than_lds_table(engine):
+    """One ~60 KB document (a single chunk) with ~7000 distinct terms: the open document
+    overflows the LDS table (partial flushes) and exceeds K5's in-LDS sort size."""
+    check_vs_oracle(engine, *more_pairs_than_lds_table_corpus())
 
 
 @pytest.mark.parametrize("V", [65535, 65536, 65537])
@@ -276,33 +300,45 @@ def test_df_histogram_vocabulary_boundary(engine, V):
     assert int(np.max(res["df"])) == len(docs)
 
 
-def test_complete_doc_over_k5_limit(engine):
-    """~2500 distinct terms in a 25 KB document: complete inside one chunk but larger than
-    K5's in-LDS sort, so it is routed through the partial merge."""
+def complete_doc_over_k5_limit_corpus():
     rng = np.random.default_rng(12)
     words = _distinct_words(2500, rng, 3, 8)
     docs = [b" ".join(words[i] for i in rng.permutation(len(words))) + b"\n", b"a b\n"]
-    check_vs_oracle(engine, *docs_to_arrays(docs))
+    return docs_to_arrays(docs)
+
+
+def test_complete_doc_over_k5_limit(engine):
+    """~2500 distinct terms in a 25 KB document: complete inside one chunk but larger than
+    K5's in-LDS sort, so it is routed through the partial merge."""
+    check_vs_oracle(engine, *complete_doc_over_k5_limit_corpus())
+
+
+def tiny_docs_without_separators_corpus():
+    rng = np.random.default_rng(13)
+    pool = [b"a", b"b", b"ab", b"ba", b"abc", b" ", b"", b"c\t", b"\nd", b"ee ee"]
+    docs = [pool[i] for i in rng.integers(0, len(pool), 5000)]
+    return docs_to_arrays(docs)
 
 
 def test_many_tiny_docs_without_separators(engine):
     """Thousands of 0-6 byte documents, most with no trailing whitespace: document starts
     are token boundaries, more documents per chunk than one LDS document group."""
-    rng = np.random.default_rng(13)
-    pool = [b"a", b"b", b"ab", b"ba", b"abc", b" ", b"", b"c\t", b"\nd", b"ee ee"]
-    docs = [pool[i] for i in rng.integers(0, len(pool), 5000)]
-    check_vs_oracle(engine, *docs_to_arrays(docs))
+    check_vs_oracle(engine, *tiny_docs_without_separators_corpus())
 
 
-def test_big_docs_split_across_chunks(engine):
-    """Documents far above BIG_DOC are split across work units mid-token; their partial
-    counts are merged."""
+def big_docs_split_corpus():
     rng = np.random.default_rng(14)
     words = _distinct_words(3000, rng, 1, 20)
     z = rng.zipf(1.3, 60000) % len(words)
     big = b" ".join(words[i] for i in z)
     docs = [big, b"tail words here", big[:200000], b"", big[5:] + b"\n"]
-    check_vs_oracle(engine, *docs_to_arrays(docs))
+    return docs_to_arrays(docs)
+
+
+def test_big_docs_split_across_chunks(engine):
+    """Documents far above BIG_DOC are split across work units mid-token; their partial
+    counts are merged."""
+    check_vs_oracle(engine, *big_docs_split_corpus())
 
 
 @pytest.mark.parametrize("cap,load", [("1024", "50"), ("4096", "12")])
