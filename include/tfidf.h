@@ -568,6 +568,92 @@ typedef struct tfidf_similar_info {
 } tfidf_similar_info;
 int tfidf_last_similar_info(const tfidf_ctx* ctx, tfidf_similar_info* info);
 
+/* --------------------------------------------------------------- transform -- */
+
+/* Fit/transform: scores documents the run has not seen against the resident model of the last
+ * run: its vocabulary, its global df, its N and its own idf table, all read-only.  The
+ * reference has one pass over one corpus (TFIDF.c:130-247); appending a document and running
+ * again would change N and every df.
+ *
+ * The batch is a tfidf_corpus and follows that struct's rules: document r (0-based, batch
+ * order) is bytes[doc_off[r], doc_off[r + 1]), windows are allowed (doc_off[0] > 0, trailing
+ * bytes after the last document), document boundaries are token boundaries, and a host pointer
+ * or a TFIDF_CORPUS_DEVICE pointer of any alignment is accepted (for a device batch doc_off is
+ * a device pointer too).  doc_ids and ndocs_total are ignored.  Tokens and terms are the run's
+ * (TFIDF.c:141-147,152): maximal runs of bytes not in {0x20,0x09..0x0D}; a term is the token's
+ * bytes up to its first NUL, and the empty term is a term.  A term of >= 16 bytes matches a
+ * vocabulary term only when the bytes are equal (the 120-bit key alone never decides: the rule
+ * of tfidf_query and TFIDF_E_CAPACITY above).  A token whose term is 16 MiB or longer is
+ * outside every vocabulary (a run refuses it); here it is out of vocabulary, not an error.
+ *   doc_size(r)  every token of the document (TFIDF.c:141-143), those outside the vocabulary
+ *                included: they lower tf, they are not dropped from the denominator
+ *   pairs of r   one per distinct vocabulary term of r, in ascending term rank: the
+ *                strcmp("word\t") order of tfidf_result.pair_term inside a document
+ *   score        fl( fl((double)count / (double)doc_size) * idf(t) ), IEEE binary64, two
+ *                roundings per pair (TFIDF.c:202,243-244); idf(t) is the double the run itself
+ *                used for t, log(1.0 * N / df) on the host's libm, read from the run's table.  A
+ *                score of +0.0 (df = N) is a pair like any other.
+ * Consequence: a batch document that is byte-equal to a document of the run gets that
+ * document's pairs bit for bit (term, count, df, score) and doc_oov = 0.  No floating-point
+ * atomics, no reciprocal: the result does not depend on grid, slices or budget.
+ * Arrays are owned by the library and released by tfidf_rows_free(). */
+typedef struct tfidf_rows {
+    uint32_t  ndocs;      /* rows = the batch's documents, in batch order */
+    uint32_t  reserved;
+    uint64_t  npairs;     /* all rows */
+    uint64_t  ntokens;    /* all rows, out-of-vocabulary tokens included */
+    uint64_t* row_off;    /* ndocs + 1: row r = pairs [row_off[r], row_off[r+1]) */
+    uint32_t* doc_size;   /* per row: every token of the document (TFIDF.c:141-143) */
+    uint32_t* doc_oov;    /* per row: tokens whose term the vocabulary does not hold */
+    uint32_t* term;       /* per pair: term rank = index into this context's term table */
+    uint32_t* count;      /* wordCount of the term in the document */
+    uint32_t* df;         /* the run's global df of the term */
+    double*   score;
+    uint64_t* word_off;   /* offset into the BATCH's bytes of the term's first token in this document */
+    uint32_t* word_len;   /* the term's length (token bytes up to its first NUL) */
+} tfidf_rows;
+/* TFIDF_E_STATE before a successful tfidf_run; TFIDF_E_INVAL for a NULL ctx, batch or out, a
+ * non-monotone doc_off or doc_off[ndocs] > nbytes.  ndocs == 0 and empty documents are valid.
+ * The state rules are tfidf_query's: the run's result is not disturbed (tfidf_fetch,
+ * tfidf_format, tfidf_query and the others give the same bytes afterwards), the run's corpus
+ * must still be valid (long terms are compared with it), and with a communicator attached the
+ * call is local to this shard's vocabulary (with the run's global df and N).
+ * The batch is processed in slices cut at document boundaries.  A slice's device scratch
+ * (boundary bitmap and counts, token records, the sort's ping-pong buffers, pairs) is bounded
+ * before its tokens are known, by one token per two bytes, and slices are cut so that this
+ * bound stays under TFIDF_TRANSFORM_MB MiB (read at tfidf_open); a single document larger than
+ * that is a slice of its own and the buffers grow for it.  The default of 512 is a guess:
+ * nobody has measured which budget serves which batch best.  The buffers belong to the
+ * context, so a repeated identical call allocates nothing (tfidf_alloc_stats). */
+int tfidf_transform(tfidf_ctx* ctx, const tfidf_corpus* batch, tfidf_rows* out);
+/* NULL or an all-zero struct: no-op. */
+void tfidf_rows_free(tfidf_rows* r);
+/* The same over every shard of a group (tfidf_group_run).  Host batches only: a
+ * TFIDF_CORPUS_DEVICE batch is TFIDF_E_INVAL.  Every rank transforms the whole batch against
+ * its own vocabulary on its own host thread; the host merges each row across the ranks in
+ * strcmp("word\t") order of the words (read from the batch bytes; every rank's row is already
+ * in that order).  A pair several ranks found is kept once: equal word_off identifies it, and
+ * the ranks agree on count, df and score because df and N are global.  doc_oov = doc_size
+ * minus the merged counts.  term is UINT32_MAX (the shards share no term table).  The merged
+ * result is bit-identical to a single-shard run of the same corpus. */
+int tfidf_group_transform(tfidf_group* g, const tfidf_corpus* batch, tfidf_rows* out);
+/* Counters of the last tfidf_transform (the caller sets `size` = sizeof, as tfidf_query_info). */
+typedef struct tfidf_transform_info {
+    uint64_t size;
+    uint32_t ndocs;
+    uint32_t nslices;
+    uint64_t ntokens;
+    uint64_t npairs;
+    uint64_t noov;            /* tokens outside the vocabulary */
+    uint64_t scratch_bytes;   /* device scratch of the largest slice */
+    double   ms_tokens;       /* device times (HIP events), summed over the slices: token boundaries */
+    double   ms_resolve;      /* rows, terms, vocabulary probes */
+    double   ms_sort;         /* the (row, term) sort */
+    double   ms_pairs;        /* run heads, counts, scores, row offsets */
+    double   ms_total;        /* host wall time of the whole call */
+} tfidf_transform_info;
+int tfidf_last_transform_info(const tfidf_ctx* ctx, tfidf_transform_info* info);
+
 /* ---------------------------------------------------------------- ingest ---- */
 
 /* Reference input contract (TFIDF.c:98-110,130-147): N = number of entries of `dir`

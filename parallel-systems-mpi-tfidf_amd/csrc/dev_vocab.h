@@ -108,4 +108,33 @@ __device__ __forceinline__ uint32_t vocab_insert(const VocabDev& v, uint64_t klo
     return vocab_insert_s<HOME>(v.keys, v.rep, v.mask, klo, khi, rep, status, bytes);
 }
 
+/* Read-only probe of a finished run's table (VocabRO, kernels.h) from the key's home slot: the term rank of the
+ * term p[0, n) whose identity key is (klo, khi), or QUERY_NO_TERM.  No slot is PENDING after a
+ * run, so plain loads suffice.  A long key (a 120-bit hash) matches only when the bytes of the
+ * vocabulary's occurrence equal p's: the rule of long_term_differs. */
+__device__ __forceinline__ uint32_t vocab_find_rank(const VocabRO& v, uint64_t klo, uint64_t khi, const uint8_t* p,
+                                                    uint64_t n) {
+    uint64_t h = key_hash(klo, khi) & v.mask & v.home;
+    for (uint32_t probe = 0; probe < VOCAB_MAX_PROBE && probe <= v.mask; ++probe) {
+        const uint4 s = gload(v.vkeys + h);
+        const uint64_t lo = ((uint64_t)s.y << 32) | s.x, hi = ((uint64_t)s.w << 32) | s.z;
+        if (hi == KEY_EMPTY_HI) break;
+        if (hi == khi && lo == klo) {
+            bool same = true;
+            if ((khi >> 56) == 0xFFu) {   /* a 120-bit hash: the bytes decide */
+                const uint64_t rep = v.vrep[h], len = rep >> 40, off = rep & 0xFFFFFFFFFFull;
+                same = len == n && off + len <= v.corpus_bytes;
+                for (uint64_t b = 0; same && b < n; ++b) same = v.corpus[off + b] == p[b];
+            }
+            if (same) {
+                const uint32_t r = v.rank_of_slot[h];
+                if (r < v.V) return r;
+            }
+            break;   /* a key sits in one slot only */
+        }
+        h = (h + 1) & v.mask;
+    }
+    return QUERY_NO_TERM;
+}
+
 #endif

@@ -267,6 +267,13 @@ struct tfidf_ctx {
     hipEvent_t ev_s[6] = {};                    /* norms / table / score / top-k bounds (created by the first call) */
     bool norm_valid = false;                    /* sm_norm holds this run's norms */
     tfidf_similar_info sinfo{};
+    /* unseen documents against the resident model (tfidf_transform, transform.hip): a host
+     * batch's bytes and offsets, a slice's boundary scratch (document-start bitmap, per-tile
+     * counts, per-document words) and its token and pair arrays */
+    DevBuf tr_bytes, tr_off, tr_a, tr_b;
+    uint64_t transform_bytes = 512ull << 20;    /* env TFIDF_TRANSFORM_MB: device scratch of a slice */
+    hipEvent_t ev_tr[5] = {};                   /* tokens / resolve / sort / pairs bounds (created by the first call) */
+    tfidf_transform_info trinfo{};
 #define WR_NBUF 8
 #define WR_BUF (16ull << 20)
 #define WR_GROUPS 8
@@ -456,6 +463,11 @@ int tfidf_open(int device, tfidf_ctx** out) {
         const unsigned long long mb = strtoull(kt, nullptr, 0);
         if (mb >= 1 && mb <= (1ull << 20)) ctx->terms_bytes = mb << 20;
     }
+    const char* ktr = getenv("TFIDF_TRANSFORM_MB");
+    if (ktr) {
+        const unsigned long long mb = strtoull(ktr, nullptr, 0);
+        if (mb >= 1 && mb <= (1ull << 20)) ctx->transform_bytes = mb << 20;
+    }
     const char* kn = getenv("TFIDF_TEST_XNOMEM_RANK");
     ctx->xnomem_rank = kn ? atoi(kn) : -1;
     /* diagnostics: initial vocabulary capacity (power of two) and the loads it may reach
@@ -542,6 +554,9 @@ void tfidf_close(tfidf_ctx* ctx) {
                       &ctx->sm_res, &ctx->sm_escore, &ctx->sm_xterm, &ctx->sm_xscore, &ctx->sm_xwoff, &ctx->sm_xwords,
                       &ctx->sm_xoff})
         b->release();
+    for (hipEvent_t e : ctx->ev_tr)
+        if (e) (void)hipEventDestroy(e);
+    for (DevBuf* b : {&ctx->tr_bytes, &ctx->tr_off, &ctx->tr_a, &ctx->tr_b}) b->release();
     DevBuf* bufs[] = {&ctx->arena_buf, &ctx->in_bytes, &ctx->in_off, &ctx->in_ids, &ctx->syn_bytes, &ctx->syn_off,
                       &ctx->syn_ids, &ctx->syn_ntok, &ctx->syn_blkfirst, &ctx->syn_blkbytes, &ctx->syn_cdf,
                       &ctx->chunk_start, &ctx->chunk_doc, &ctx->vkeys, &ctx->vrep, &ctx->rec_slot, &ctx->rec_cnt,
@@ -2790,6 +2805,294 @@ extern "C" int tfidf_last_query_info(const tfidf_ctx* ctx, tfidf_query_info* inf
     if (!ctx || !info || info->size < sizeof(uint64_t)) return TFIDF_E_INVAL;
     const uint64_t n = info->size < sizeof(tfidf_query_info) ? info->size : sizeof(tfidf_query_info);
     tfidf_query_info o = ctx->qinfo;
+    o.size = n;
+    memcpy(info, &o, (size_t)n);
+    return TFIDF_OK;
+}
+
+/* --------------------------------------------------------------- transform ----
+ * Unseen documents against the resident model (transform.hip).  The run leaves vkeys / vrep /
+ * rank_of_slot, df_of_run, idf_vals and (N over IDF_FULL_MAX) its `present` index in buffers of
+ * the context that nothing after the run writes (tfidf_query's note above; the query, keyword
+ * and similarity calls use their own buffers and the arena only as scratch), so the scores
+ * read the very doubles the run multiplied with.  The batch is cut into slices at document
+ * boundaries; a slice is: boundaries (counted, scanned, written) -> one round trip for the
+ * token total -> resolve -> stable sort of (row << 32 | rank, token index) -> run heads, scan,
+ * pairs -> copies into the caller's arrays. */
+
+extern "C" void tfidf_rows_free(tfidf_rows* r) {
+    if (!r) return;
+    free(r->row_off); free(r->doc_size); free(r->doc_oov); free(r->term); free(r->count); free(r->df);
+    free(r->score); free(r->word_off); free(r->word_len);
+    memset(r, 0, sizeof(*r));
+}
+
+namespace {
+struct RowsGuard {   /* an error return leaves *out zeroed */
+    tfidf_rows* r;
+    ~RowsGuard() { if (r) tfidf_rows_free(r); }
+};
+template <typename T> bool grow_host(T*& p, uint64_t n) {
+    void* q = realloc(p, (size_t)(n + 1) * sizeof(T));
+    if (!q) return false;
+    p = (T*)q;
+    return true;
+}
+/* the upper bound of a slice's device scratch before its tokens are known: its bytes hold at
+ * most one token per two bytes and one more per document (a document boundary ends a token);
+ * per token 84 bytes of records, sort buffers and pairs */
+constexpr uint64_t TR_TOKEN_BYTES = 84;
+inline uint64_t tr_max_tokens(uint64_t nbytes, uint64_t nd) {
+    const uint64_t t = (nbytes + 1) / 2 + nd;
+    return t < nbytes ? t : nbytes;
+}
+inline uint64_t tr_a_bytes(uint64_t nbytes, uint64_t nd) {
+    const uint64_t ntiles = nbytes / TR_TILE + 2;
+    return (ntiles * (TR_TILE / 32u) + 1u) * 4u + 2 * (ntiles + 1) * 8 + nd * 8 + (nd + 1) * 8 + 4096;
+}
+inline uint64_t tr_bound(uint64_t nbytes, uint64_t nd) {
+    return tr_a_bytes(nbytes, nd) + tr_max_tokens(nbytes, nd) * TR_TOKEN_BYTES + 4096;
+}
+inline size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
+}  // namespace
+
+extern "C" int tfidf_transform(tfidf_ctx* ctx, const tfidf_corpus* batch, tfidf_rows* out) {
+    if (!ctx || !batch || !out) return TFIDF_E_INVAL;
+    const uint32_t N = batch->ndocs;
+    if (N && !batch->doc_off) return TFIDF_E_INVAL;
+    if (!ctx->have_result) return TFIDF_E_STATE;
+    const auto wall0 = std::chrono::steady_clock::now();
+    HIPCHK(hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    const bool dev = (batch->flags & TFIDF_CORPUS_DEVICE) != 0;
+    /* the offsets on the host: the slices are cut here */
+    std::vector<uint64_t> off_copy;
+    const uint64_t* off = batch->doc_off;
+    if (dev && N) {
+        off_copy.resize((size_t)N + 1);
+        HIPCHK(hipMemcpyAsync(off_copy.data(), batch->doc_off, ((size_t)N + 1) * 8, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        off = off_copy.data();
+    }
+    for (uint32_t d = 0; d < N; ++d)
+        if (off[d] > off[d + 1]) return TFIDF_E_INVAL;
+    if (N && (off[N] > batch->nbytes || (off[N] > off[0] && !batch->bytes))) return TFIDF_E_INVAL;
+    const uint8_t* d_bytes = batch->bytes;
+    const uint64_t* d_off = batch->doc_off;
+    if (!dev && N) {   /* the run's own host corpus lives in in_bytes: the batch gets its own buffers */
+        ENSURE(ctx->tr_bytes, batch->nbytes + 64);
+        ENSURE(ctx->tr_off, ((size_t)N + 1) * 8);
+        if (off[N] > off[0])
+            HIPCHK(hipMemcpyAsync(ctx->tr_bytes.as<uint8_t>() + off[0], batch->bytes + off[0], off[N] - off[0],
+                                  hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(ctx->tr_off.p, off, ((size_t)N + 1) * 8, hipMemcpyHostToDevice, s));
+        d_bytes = ctx->tr_bytes.as<uint8_t>();
+        d_off = ctx->tr_off.as<uint64_t>();
+    }
+    for (hipEvent_t& e : ctx->ev_tr)
+        if (!e) HIPCHK(hipEventCreate(&e));
+
+    memset(out, 0, sizeof(*out));
+    RowsGuard guard{out};
+    out->ndocs = N;
+    out->row_off = (uint64_t*)calloc((size_t)N + 1, 8);
+    out->doc_size = (uint32_t*)calloc((size_t)N + 1, 4);
+    out->doc_oov = (uint32_t*)calloc((size_t)N + 1, 4);
+    if (!out->row_off || !out->doc_size || !out->doc_oov) return TFIDF_E_NOMEM;
+    if (!grow_host(out->term, 0) || !grow_host(out->count, 0) || !grow_host(out->df, 0) || !grow_host(out->score, 0) ||
+        !grow_host(out->word_off, 0) || !grow_host(out->word_len, 0))
+        return TFIDF_E_NOMEM;
+
+    tfidf_transform_info ti{};
+    ti.ndocs = N;
+    const uint32_t V = ctx->V;
+    const bool full_lut = ctx->ndocs_total <= IDF_FULL_MAX;   /* run_post: idf_vals by df, else through `present` */
+    uint64_t Ptot = 0;
+    std::vector<uint64_t> h_rowoff;
+    for (uint32_t d0 = 0; d0 < N;) {
+        /* ---- the slice: documents [d0, d1) whose scratch bound stays under the budget ---- */
+        uint32_t d1 = d0 + 1;
+        while (d1 < N && tr_bound(off[d1 + 1] - off[d0], (uint64_t)d1 + 1 - d0) <= ctx->transform_bytes) ++d1;
+        const uint32_t nd = d1 - d0;
+        const uint64_t b0 = off[d0], b1 = off[d1];
+        ++ti.nslices;
+        for (uint32_t r = 0; r <= nd; ++r) out->row_off[d0 + r] = Ptot;   /* rows without a token stay empty */
+        if (b1 == b0) { d0 = d1; continue; }
+        TrSlice sl{};
+        sl.bytes = d_bytes;
+        sl.nbytes = batch->nbytes;
+        sl.doc_off = d_off;
+        sl.d0 = d0;
+        sl.d1 = d1;
+        sl.b0 = b0;
+        sl.b1 = b1;
+        sl.p0 = (long long)b0 - (long long)(((uintptr_t)d_bytes + b0) & 15u);
+        sl.ntiles = (uint64_t)((long long)b1 - sl.p0 + (TR_TILE - 1)) / TR_TILE;
+        /* tr_a: status, per-document words, the bitmap, the per-tile counts */
+        const size_t a_status = 0, a_dsize = 256, a_doov = al256(a_dsize + (size_t)nd * 4);
+        const size_t a_rowoff = al256(a_doov + (size_t)nd * 4), a_dstart = al256(a_rowoff + ((size_t)nd + 1) * 8);
+        const size_t a_cs = al256(a_dstart + (size_t)(sl.ntiles * (TR_TILE / 32u) + 1u) * 4);
+        const size_t a_ce = al256(a_cs + (size_t)(sl.ntiles + 1) * 8), a_end = al256(a_ce + (size_t)(sl.ntiles + 1) * 8);
+        ENSURE(ctx->tr_a, a_end);
+        uint8_t* A = ctx->tr_a.as<uint8_t>();
+        sl.status = (uint32_t*)(A + a_status);
+        sl.dstart = (uint32_t*)(A + a_dstart);
+        sl.cnt_s = (uint64_t*)(A + a_cs);
+        sl.cnt_e = (uint64_t*)(A + a_ce);
+        HIPCHK(hipMemsetAsync(A, 0, a_rowoff, s));   /* status, doc_size, doc_oov */
+        HIPCHK(hipEventRecord(ctx->ev_tr[0], s));
+        ctx->arena.used = 0;   /* as format_prepare: nothing of the result lives in the arena */
+        if (launch_tr_docstarts(sl, s) || launch_tr_count(sl, s)) { HIPCHK(hipGetLastError()); return TFIDF_E_HIP; }
+        if (scan_excl_u64(sl.cnt_s, sl.cnt_s, sl.ntiles, ctx->arena, s) ||
+            scan_excl_u64(sl.cnt_e, sl.cnt_e, sl.ntiles, ctx->arena, s)) {
+            HIPCHK(hipGetLastError());
+            return TFIDF_E_HIP;
+        }
+        uint64_t tot[2] = {0, 0};
+        HIPCHK(hipMemcpyAsync(&tot[0], sl.cnt_s + sl.ntiles, 8, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(&tot[1], sl.cnt_e + sl.ntiles, 8, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        const uint64_t T = tot[0];
+        if (tot[1] != T || T > tr_max_tokens(b1 - b0, nd)) {
+            fprintf(stderr, "tfidf: transform: %llu token starts, %llu ends in %llu bytes\n", (unsigned long long)tot[0],
+                    (unsigned long long)tot[1], (unsigned long long)(b1 - b0));
+            return TFIDF_E_STATE;
+        }
+        if (T > 0xFFFFFFFEull) return TFIDF_E_CAPACITY;
+        if (T == 0) {   /* whitespace only */
+            const uint64_t sb = a_end;
+            if (sb > ti.scratch_bytes) ti.scratch_bytes = sb;
+            d0 = d1;
+            continue;
+        }
+        /* tr_b: token records, sort buffers, pairs (sized by the slice's tokens) */
+        size_t bo = 0;
+        auto take = [&bo](size_t bytes) { const size_t at = bo; bo = al256(bo + bytes); return at; };
+        const size_t b_ts = take(T * 8), b_te = take(T * 8), b_tl = take(T * 4);
+        const size_t b_k0 = take(T * 8), b_k1 = take(T * 8), b_v0 = take(T * 4), b_v1 = take(T * 4);
+        const size_t b_pos = take((T + 1) * 4);
+        const size_t b_prow = take(T * 4), b_pterm = take(T * 4), b_pcnt = take(T * 4), b_pdf = take(T * 4);
+        const size_t b_psc = take(T * 8), b_pwo = take(T * 8), b_pwl = take(T * 4);
+        ENSURE(ctx->tr_b, bo);
+        if (a_end + bo > ti.scratch_bytes) ti.scratch_bytes = a_end + bo;
+        {   /* the sort's histograms and the scans' block sums */
+            const size_t want = (size_t)(T / 2 + T / 64) + (8u << 20);
+            if (want > ctx->arena_buf.cap && arena_reset(ctx, want) != 0) return TFIDF_E_NOMEM;
+            ctx->arena.used = 0;
+        }
+        uint8_t* B = ctx->tr_b.as<uint8_t>();
+        sl.tok_start = (uint64_t*)(B + b_ts);
+        sl.tok_end = (uint64_t*)(B + b_te);
+        sl.tok_cap = T;
+        if (launch_tr_write(sl, s)) { HIPCHK(hipGetLastError()); return TFIDF_E_HIP; }
+        HIPCHK(hipEventRecord(ctx->ev_tr[1], s));
+        TrResolve ra{};
+        ra.sl = sl;
+        ra.ntok = T;
+        ra.voc = VocabRO{ctx->vkeys.as<uint4>(), ctx->vrep.as<uint64_t>(), ctx->vcap - 1, ~1ull,
+                         ctx->rank_of_slot.as<uint32_t>(), ctx->dev_bytes, ctx->corpus.nbytes, V};
+        ra.key = (uint64_t*)(B + b_k0);
+        ra.val = (uint32_t*)(B + b_v0);
+        ra.tlen = (uint32_t*)(B + b_tl);
+        if (launch_tr_resolve(ra, s)) { HIPCHK(hipGetLastError()); return TFIDF_E_HIP; }
+        HIPCHK(hipEventRecord(ctx->ev_tr[2], s));
+        /* only the bytes that vary are sorted: the ranks 0..V below, the rows d0..d1-1 above */
+        uint32_t byte_mask = 0;
+        for (uint32_t b = 0; b < 4; ++b) {
+            if ((V >> (8 * b)) != 0) byte_mask |= 1u << b;
+            if (((d0 ^ (d1 - 1)) >> (8 * b)) != 0) byte_mask |= 1u << (4 + b);
+        }
+        const int where = radix_sort_u64(ra.key, ra.val, (uint64_t*)(B + b_k1), (uint32_t*)(B + b_v1), T, byte_mask,
+                                         ctx->arena, s);
+        if (where < 0) { HIPCHK(hipGetLastError()); return where == -2 ? TFIDF_E_NOMEM : TFIDF_E_HIP; }
+        HIPCHK(hipEventRecord(ctx->ev_tr[3], s));
+        TrPairs pa{};
+        pa.key = where ? (uint64_t*)(B + b_k1) : ra.key;
+        pa.val = where ? (uint32_t*)(B + b_v1) : ra.val;
+        pa.ntok = T;
+        pa.d0 = d0;
+        pa.d1 = d1;
+        pa.V = V;
+        pa.doc_off = d_off;
+        pa.tok_start = sl.tok_start;
+        pa.tlen = ra.tlen;
+        pa.flag = (uint32_t*)(B + b_pos);
+        pa.pos = pa.flag;   /* scanned in place */
+        pa.df = df_of_run(ctx);
+        pa.idf_idx = full_lut ? nullptr : ctx->present.as<uint32_t>();
+        pa.idf = ctx->idf_vals.as<double>();
+        pa.Nt = ctx->ndocs_total;
+        pa.doc_size = (uint32_t*)(A + a_dsize);
+        pa.doc_oov = (uint32_t*)(A + a_doov);
+        pa.row_off = (uint64_t*)(A + a_rowoff);
+        pa.p_row = (uint32_t*)(B + b_prow);
+        pa.p_term = (uint32_t*)(B + b_pterm);
+        pa.p_count = (uint32_t*)(B + b_pcnt);
+        pa.p_df = (uint32_t*)(B + b_pdf);
+        pa.p_score = (double*)(B + b_psc);
+        pa.p_woff = (uint64_t*)(B + b_pwo);
+        pa.p_wlen = (uint32_t*)(B + b_pwl);
+        pa.status = sl.status;
+        if (launch_tr_flags(pa, s) || scan_excl_u32(pa.flag, pa.flag, T, ctx->arena, s) || launch_tr_pairs(pa, s)) {
+            HIPCHK(hipGetLastError());
+            return TFIDF_E_HIP;
+        }
+        HIPCHK(hipEventRecord(ctx->ev_tr[4], s));
+        /* ---- back to the host: the slice's words first (the pair total sizes the rest) ---- */
+        uint32_t P32 = 0, st = 0;
+        h_rowoff.resize((size_t)nd + 1);
+        HIPCHK(hipMemcpyAsync(&P32, pa.pos + T, 4, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(&st, sl.status, 4, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(out->doc_size + d0, pa.doc_size, (size_t)nd * 4, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(out->doc_oov + d0, pa.doc_oov, (size_t)nd * 4, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(h_rowoff.data(), pa.row_off, ((size_t)nd + 1) * 8, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        if (st & ST_BOUNDS) {
+            fprintf(stderr, "tfidf: transform: internal bounds check tripped (status 0x%x)\n", st);
+            return TFIDF_E_STATE;
+        }
+        const uint64_t P = P32;
+        if (!grow_host(out->term, Ptot + P) || !grow_host(out->count, Ptot + P) || !grow_host(out->df, Ptot + P) ||
+            !grow_host(out->score, Ptot + P) || !grow_host(out->word_off, Ptot + P) || !grow_host(out->word_len, Ptot + P))
+            return TFIDF_E_NOMEM;
+        if (P) {
+            HIPCHK(hipMemcpyAsync(out->term + Ptot, pa.p_term, (size_t)P * 4, hipMemcpyDeviceToHost, s));
+            HIPCHK(hipMemcpyAsync(out->count + Ptot, pa.p_count, (size_t)P * 4, hipMemcpyDeviceToHost, s));
+            HIPCHK(hipMemcpyAsync(out->df + Ptot, pa.p_df, (size_t)P * 4, hipMemcpyDeviceToHost, s));
+            HIPCHK(hipMemcpyAsync(out->score + Ptot, pa.p_score, (size_t)P * 8, hipMemcpyDeviceToHost, s));
+            HIPCHK(hipMemcpyAsync(out->word_off + Ptot, pa.p_woff, (size_t)P * 8, hipMemcpyDeviceToHost, s));
+            HIPCHK(hipMemcpyAsync(out->word_len + Ptot, pa.p_wlen, (size_t)P * 4, hipMemcpyDeviceToHost, s));
+            HIPCHK(hipStreamSynchronize(s));
+        }
+        for (uint32_t r = 0; r <= nd; ++r) out->row_off[d0 + r] = Ptot + h_rowoff[r];
+        Ptot += P;
+        ti.ntokens += T;
+        float ms = 0;
+        (void)hipEventElapsedTime(&ms, ctx->ev_tr[0], ctx->ev_tr[1]);
+        ti.ms_tokens += ms;
+        (void)hipEventElapsedTime(&ms, ctx->ev_tr[1], ctx->ev_tr[2]);
+        ti.ms_resolve += ms;
+        (void)hipEventElapsedTime(&ms, ctx->ev_tr[2], ctx->ev_tr[3]);
+        ti.ms_sort += ms;
+        (void)hipEventElapsedTime(&ms, ctx->ev_tr[3], ctx->ev_tr[4]);
+        ti.ms_pairs += ms;
+        d0 = d1;
+    }
+    if (N) out->row_off[N] = Ptot;
+    out->npairs = Ptot;
+    out->ntokens = ti.ntokens;
+    for (uint32_t d = 0; d < N; ++d) ti.noov += out->doc_oov[d];
+    ti.npairs = Ptot;
+    ti.ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - wall0).count();
+    ctx->trinfo = ti;
+    guard.r = nullptr;
+    return TFIDF_OK;
+}
+
+extern "C" int tfidf_last_transform_info(const tfidf_ctx* ctx, tfidf_transform_info* info) {
+    if (!ctx || !info || info->size < sizeof(uint64_t)) return TFIDF_E_INVAL;
+    const uint64_t n = info->size < sizeof(tfidf_transform_info) ? info->size : sizeof(tfidf_transform_info);
+    tfidf_transform_info o = ctx->trinfo;
     o.size = n;
     memcpy(info, &o, (size_t)n);
     return TFIDF_OK;

@@ -929,6 +929,99 @@ int tfidf_group_similar(tfidf_group* g, const uint32_t* doc_ids, uint32_t ndocs,
     return TFIDF_OK;
 }
 
+/* strcmp order of "a\t" and "b\t" (TFIDF.c:245,273): words hold no NUL and no whitespace, so
+ * the TAB meets a byte it differs from when one word is a prefix of the other */
+static int word_tab_cmp(const uint8_t* a, uint32_t na, const uint8_t* b, uint32_t nb) {
+    const uint32_t n = na < nb ? na : nb;
+    const int c = n ? memcmp(a, b, n) : 0;
+    if (c || na == nb) return c;
+    return na < nb ? (0x09 < b[n] ? -1 : 1) : (a[n] < 0x09 ? -1 : 1);
+}
+
+/* Every rank transforms the whole batch against its own vocabulary (tfidf_transform is local
+ * to a context), one host thread per rank as in tfidf_group_run.  Term-table order is the
+ * word order in every shard, so each rank's row is sorted by word and the rows merge by a
+ * k-way merge over the batch's bytes; a pair several ranks hold (equal word_off: the term's
+ * first token in the document) is kept once — df and N are global, so the ranks agree on it. */
+int tfidf_group_transform(tfidf_group* g, const tfidf_corpus* batch, tfidf_rows* out) {
+    if (!g || !batch || !out) return TFIDF_E_INVAL;
+    if (batch->flags & TFIDF_CORPUS_DEVICE) return TFIDF_E_INVAL;   /* the merge reads the words on the host */
+    const int R = g->n;
+    std::vector<int> rc((size_t)R, TFIDF_OK);
+    std::vector<tfidf_rows> part((size_t)R);
+    for (tfidf_rows& p : part) memset(&p, 0, sizeof(p));
+    {
+        std::vector<std::thread> th;
+        for (int r = 1; r < R; ++r) th.emplace_back([&, r] { rc[r] = tfidf_transform(g->ctx[r], batch, &part[r]); });
+        rc[0] = tfidf_transform(g->ctx[0], batch, &part[0]);
+        for (auto& t : th) t.join();
+    }
+    int err = TFIDF_OK;
+    for (int r = 0; r < R && !err; ++r) err = rc[r];
+    const uint32_t N = batch->ndocs;
+    tfidf_rows m;
+    memset(&m, 0, sizeof(m));
+    uint64_t cap = 0;
+    for (int r = 0; r < R && !err; ++r) cap += part[r].npairs;
+    if (!err) {
+        m.ndocs = N;
+        m.ntokens = part[0].ntokens;
+        m.row_off = (uint64_t*)calloc((size_t)N + 1, 8);
+        m.doc_size = (uint32_t*)calloc((size_t)N + 1, 4);
+        m.doc_oov = (uint32_t*)calloc((size_t)N + 1, 4);
+        m.term = (uint32_t*)calloc((size_t)cap + 1, 4);
+        m.count = (uint32_t*)calloc((size_t)cap + 1, 4);
+        m.df = (uint32_t*)calloc((size_t)cap + 1, 4);
+        m.score = (double*)calloc((size_t)cap + 1, 8);
+        m.word_off = (uint64_t*)calloc((size_t)cap + 1, 8);
+        m.word_len = (uint32_t*)calloc((size_t)cap + 1, 4);
+        if (!m.row_off || !m.doc_size || !m.doc_oov || !m.term || !m.count || !m.df || !m.score || !m.word_off || !m.word_len)
+            err = TFIDF_E_NOMEM;
+    }
+    uint64_t P = 0;
+    std::vector<uint64_t> at((size_t)R);
+    for (uint32_t d = 0; d < N && !err; ++d) {
+        m.row_off[d] = P;
+        m.doc_size[d] = part[0].doc_size[d];
+        uint64_t in_vocab = 0;
+        for (int r = 0; r < R; ++r) at[r] = part[r].row_off[d];
+        for (;;) {
+            int best = -1;
+            for (int r = 0; r < R; ++r) {
+                if (at[r] >= part[r].row_off[d + 1]) continue;
+                if (best < 0 || word_tab_cmp(batch->bytes + part[r].word_off[at[r]], part[r].word_len[at[r]],
+                                             batch->bytes + part[best].word_off[at[best]], part[best].word_len[at[best]]) < 0)
+                    best = r;
+            }
+            if (best < 0) break;
+            const uint64_t x = at[best], wo = part[best].word_off[x];
+            m.term[P] = 0xFFFFFFFFu;
+            m.count[P] = part[best].count[x];
+            m.df[P] = part[best].df[x];
+            m.score[P] = part[best].score[x];
+            m.word_off[P] = wo;
+            m.word_len[P] = part[best].word_len[x];
+            in_vocab += m.count[P];
+            ++P;
+            for (int r = 0; r < R; ++r)   /* the same pair on the other ranks */
+                if (at[r] < part[r].row_off[d + 1] && part[r].word_off[at[r]] == wo) ++at[r];
+        }
+        m.doc_oov[d] = (uint32_t)(m.doc_size[d] - in_vocab);
+    }
+    if (!err) {
+        m.row_off[N] = P;
+        m.npairs = P;
+    }
+    for (tfidf_rows& p : part) tfidf_rows_free(&p);
+    if (err) {
+        tfidf_rows_free(&m);
+        memset(out, 0, sizeof(*out));
+        return err;
+    }
+    *out = m;
+    return TFIDF_OK;
+}
+
 void tfidf_group_close(tfidf_group* g) {
     if (!g) return;
     for (tfidf_ctx* c : g->ctx)

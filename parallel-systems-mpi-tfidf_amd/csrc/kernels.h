@@ -579,4 +579,87 @@ struct SimExportArgs {
 };
 int launch_sim_export(const SimExportArgs& a, hipStream_t s);
 
+/* ---- scoring unseen documents against the resident model (transform.hip, tfidf_transform) ---- */
+/* The frozen vocabulary of a finished run, as its read-only consumers probe it
+ * (vocab_find_rank, dev_vocab.h). */
+struct VocabRO {
+    const uint4* vkeys;          /* the run's table, read only */
+    const uint64_t* vrep;
+    uint64_t mask;               /* capacity - 1 */
+    uint64_t home;               /* home alignment of the run's inserts: ~1 pairs, ~3 quads */
+    const uint32_t* rank_of_slot;
+    const uint8_t* corpus;       /* the run's corpus: long terms' bytes */
+    uint64_t corpus_bytes;
+    uint32_t V;
+};
+#define TR_TILE 4096u            /* bytes per boundary workgroup: 256 lanes x one 16-byte group */
+/* One slice of a batch: the documents [d0, d1), bytes [b0, b1) of the batch buffer.  Tile t
+ * covers the positions [p0 + t * TR_TILE, + TR_TILE); p0 = b0 minus the misalignment of
+ * bytes + b0 (it may be negative), so every group that lies inside the window is one aligned
+ * 16-byte load; groups that straddle a window edge take the byte path. */
+struct TrSlice {
+    const uint8_t* bytes;
+    uint64_t nbytes;             /* bound of `bytes` */
+    const uint64_t* doc_off;     /* the batch's ndocs + 1 offsets (device) */
+    uint32_t d0, d1;
+    uint64_t b0, b1;
+    long long p0;
+    uint64_t ntiles;
+    uint32_t* dstart;            /* ntiles * (TR_TILE / 32) + 1 words: bit i = a document other than d0 starts at p0 + i */
+    uint64_t* cnt_s;             /* ntiles + 1: token starts per tile, then their exclusive scan */
+    uint64_t* cnt_e;             /* the same for token ends */
+    uint64_t* tok_start;         /* tok_cap: token i = bytes [tok_start[i], tok_end[i]) */
+    uint64_t* tok_end;
+    uint64_t tok_cap;
+    uint32_t* status;            /* ST_BOUNDS instead of a fault */
+};
+/* zeroes dstart and marks the starts of the documents (d0, d1) */
+int launch_tr_docstarts(const TrSlice& a, hipStream_t s);
+/* per-tile counts of token starts and ends -> cnt_s / cnt_e */
+int launch_tr_count(const TrSlice& a, hipStream_t s);
+/* after the scans of cnt_s / cnt_e: tok_start / tok_end (the i-th start pairs with the i-th end) */
+int launch_tr_write(const TrSlice& a, hipStream_t s);
+/* one lane per token: its row (upper_bound of the start in doc_off), its term (cut at the first
+ * NUL), the term's rank in the frozen vocabulary.  key = row << 32 | rank, rank = V for a term
+ * the vocabulary does not hold (it sorts behind the row's pairs); val = the token index. */
+struct TrResolve {
+    TrSlice sl;
+    uint64_t ntok;
+    VocabRO voc;
+    uint64_t* key;
+    uint32_t* val;
+    uint32_t* tlen;              /* the term's length */
+};
+int launch_tr_resolve(const TrResolve& a, hipStream_t s);
+/* over the sorted (key, val): flag = first record of a run of equal keys whose rank is < V;
+ * after pos = the exclusive scan of flag (pos[ntok] = the slice's pairs), the pairs */
+struct TrPairs {
+    const uint64_t* key;         /* sorted */
+    const uint32_t* val;
+    uint64_t ntok;
+    uint32_t d0, d1, V;
+    const uint64_t* doc_off;
+    const uint64_t* tok_start;   /* ascending */
+    const uint32_t* tlen;
+    uint32_t* flag;
+    const uint32_t* pos;
+    const uint32_t* df;          /* the run's global df by rank */
+    const uint32_t* idf_idx;     /* df -> index into idf; null: idf is indexed by df */
+    const double* idf;
+    uint64_t Nt;
+    uint32_t* doc_size;          /* d1 - d0, every token */
+    uint32_t* doc_oov;           /* d1 - d0, zeroed by the caller */
+    uint64_t* row_off;           /* d1 - d0 + 1, slice-local */
+    uint32_t* p_row;             /* per pair */
+    uint32_t* p_term;
+    uint32_t* p_count;
+    uint32_t* p_df;
+    double* p_score;
+    uint64_t* p_woff;
+    uint32_t* p_wlen;
+    uint32_t* status;
+};
+int launch_tr_flags(const TrPairs& a, hipStream_t s);
+int launch_tr_pairs(const TrPairs& a, hipStream_t s);
+
 #endif

@@ -24,6 +24,7 @@
  */
 #include "kernels.h"
 #include "dev_common.h"
+#include "dev_vocab.h"
 
 namespace {
 
@@ -34,7 +35,6 @@ int ok() { return hipGetLastError() == hipSuccess ? 0 : -1; }
 constexpr uint32_t QF_BITS = 1u << 18;          /* LDS filter: 32 KiB */
 constexpr uint32_t QF_WORDS = QF_BITS / 32u;
 constexpr uint32_t QTAB_WORDS = 4096u;          /* a group's term table staged in LDS when it fits (16 KiB) */
-constexpr uint32_t Q_PROBE_MAX = 4096u;         /* VOCAB_MAX_PROBE: no insert went further */
 
 /* ------------------------------------------------------------------ lookup -- */
 
@@ -55,28 +55,8 @@ __global__ void k_query_lookup(const QLookupArgs a) {
     } else {
         make_long_key(p, n, &klo, &khi);
     }
-    uint32_t rank = QUERY_NO_TERM;
-    uint64_t h = key_hash(klo, khi) & a.mask & a.home;
-    for (uint32_t probe = 0; probe < Q_PROBE_MAX && probe <= a.mask; ++probe) {
-        const uint4 s = gload(a.vkeys + h);
-        const uint64_t lo = ((uint64_t)s.y << 32) | s.x, hi = ((uint64_t)s.w << 32) | s.z;
-        if (hi == KEY_EMPTY_HI) break;
-        if (hi == khi && lo == klo) {
-            bool same = true;
-            if ((khi >> 56) == 0xFFu) {   /* a 120-bit hash: the bytes decide (dev_vocab.h) */
-                const uint64_t rep = a.vrep[h], len = rep >> 40, off = rep & 0xFFFFFFFFFFull;
-                same = len == n && off + len <= a.corpus_bytes;
-                for (uint64_t b = 0; same && b < n; ++b) same = a.corpus[off + b] == p[b];
-            }
-            if (same) {
-                const uint32_t r = a.rank_of_slot[h];
-                if (r < a.V) rank = r;
-            }
-            break;   /* a key sits in one slot only */
-        }
-        h = (h + 1) & a.mask;
-    }
-    a.rank_out[i] = rank;
+    const VocabRO v{a.vkeys, a.vrep, a.mask, a.home, a.rank_of_slot, a.corpus, a.corpus_bytes, a.V};
+    a.rank_out[i] = vocab_find_rank(v, klo, khi, p, n);
 }
 
 /* ------------------------------------------------------------------- score -- */

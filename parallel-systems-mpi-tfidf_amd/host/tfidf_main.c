@@ -53,6 +53,17 @@
  *                         order;
  *   --similar-file FILE   the neighbours file (default similar.txt).
  * With several shards the result is the single-shard one (tfidf_group_similar).
+ *
+ * Transform (documents the run has not seen, scored with the run's vocabulary, df, N and idf,
+ * tfidf_transform):
+ *   --transform DIR        after output.txt (and the other files), DIR/doc1..docM are read under
+ *                          the input contract (TFIDF.c:98-110,130-147) and written as
+ *                          "docM@word\t%.16f" lines, documents in "docN@" order, a document's
+ *                          words in output.txt's order; words the run's vocabulary does not hold
+ *                          give no line (they still count in docSize).  `--transform input`
+ *                          reproduces output.txt byte for byte;
+ *   --transform-file FILE  the file (default transform.txt).
+ * With several shards the ranks' rows are merged by word (tfidf_group_transform).
  */
 #include <dirent.h>
 #include <pthread.h>
@@ -241,6 +252,52 @@ static int run_similar(tfidf_ctx* ctx, tfidf_group* g) {
     return rc;
 }
 
+/* -------------------------------------------------------------- transform -- */
+
+static struct {
+    const char* dir;    /* NULL: no transform, behaviour and bytes as without the option */
+    const char* file;
+} g_transform = {NULL, "transform.txt"};
+
+/* --transform: DIR's documents against the model of ctx (one shard) or of every rank of g */
+static int run_transform(tfidf_ctx* ctx, tfidf_group* g) {
+    if (!g_transform.dir) return TFIDF_OK;
+    tfidf_corpus b;
+    memset(&b, 0, sizeof(b));
+    uint8_t* bytes = NULL;
+    uint64_t* off = NULL;
+    uint32_t bad = 0;
+    int rc = tfidf_ingest_dir(g_transform.dir, &bytes, &b.nbytes, &off, &b.ndocs, &bad);
+    if (rc == TFIDF_E_NOINPUT) { printf("Directory failed to open\n"); return TFIDF_OK; }
+    if (rc == TFIDF_E_NODOC) { (void)missing_doc(g_transform.dir, bad, b.ndocs); return TFIDF_OK; }
+    if (rc) return rc;
+    b.bytes = bytes;
+    b.doc_off = off;
+    tfidf_rows t;
+    memset(&t, 0, sizeof(t));
+    uint32_t* ids = (uint32_t*)malloc(((size_t)b.ndocs + 1) * sizeof(uint32_t));
+    rc = ids ? tfidf_doc_name_order(b.ndocs, ids) : TFIDF_E_NOMEM;
+    if (!rc) rc = g ? tfidf_group_transform(g, &b, &t) : tfidf_transform(ctx, &b, &t);
+    if (!rc) {
+        FILE* f = fopen(g_transform.file, "w");
+        if (!f) printf("Error Opening File: %s\n", g_transform.file);
+        for (uint32_t i = 0; f && i < t.ndocs; ++i) {   /* rows in "docN@" order (TFIDF.c:273) */
+            const uint32_t r = ids[i] - 1;
+            for (uint64_t x = t.row_off[r]; x < t.row_off[r + 1]; ++x) {
+                fprintf(f, "doc%u@", ids[i]);
+                fwrite(bytes + t.word_off[x], 1, t.word_len[x], f);
+                fprintf(f, "\t%.16f\n", t.score[x]);
+            }
+        }
+        if (f && fclose(f) != 0) rc = TFIDF_E_OUTPUT;
+    }
+    tfidf_rows_free(&t);
+    free(ids);
+    tfidf_free(bytes);
+    tfidf_free(off);
+    return rc;
+}
+
 /* ------------------------------------------------------------- one shard -- */
 
 static int run_single(int device, const char* indir, const char* outpath, int debug, int stats) {
@@ -285,6 +342,7 @@ static int run_single(int device, const char* indir, const char* outpath, int de
     rc = run_queries(ctx, NULL);
     if (!rc) rc = run_keywords(ctx, NULL);
     if (!rc) rc = run_similar(ctx, NULL);
+    if (!rc) rc = run_transform(ctx, NULL);
     tfidf_close(ctx);
     if (rc) return fail(rc);
     return 0;
@@ -385,6 +443,7 @@ static int run_sharded(int ngpus, int nshards, const char* indir, const char* ou
     rc = run_queries(NULL, g);
     if (!rc) rc = run_keywords(NULL, g);
     if (!rc) rc = run_similar(NULL, g);
+    if (!rc) rc = run_transform(NULL, g);
     tfidf_group_close(g);
     tfidf_plan_free(&plan);
     if (rc) return fail(rc);
@@ -432,6 +491,8 @@ int main(int argc, char** argv) {
             if (k < 1 || k > (long)TFIDF_TERMS_MAX_K) { fprintf(stderr, "tfidf: --keywords takes 1..%u\n", TFIDF_TERMS_MAX_K); return 2; }
             g_keywords.k = (uint32_t)k;
         }
+        else if (!strcmp(argv[i], "--transform-file") && i + 1 < argc) g_transform.file = argv[++i];
+        else if (!strcmp(argv[i], "--transform") && i + 1 < argc) g_transform.dir = argv[++i];
         else if (!strcmp(argv[i], "--similar-docs") && i + 1 < argc) g_similar.docs = argv[++i];
         else if (!strcmp(argv[i], "--similar-file") && i + 1 < argc) g_similar.file = argv[++i];
         else if (!strcmp(argv[i], "--similar") && i + 1 < argc) {
@@ -443,7 +504,8 @@ int main(int argc, char** argv) {
             fprintf(stderr, "usage: tfidf [--debug-jobs] [--stats] [--gpus N] [--shards K] [--device D] "
                             "[--input DIR] [--output FILE] [--query FILE [--top K] [--hits FILE] [--bm25 [--bm25-k1 X] [--bm25-b Y]]] "
                             "[--keywords K [--keywords-file FILE]] "
-                            "[--similar K [--similar-docs FILE] [--similar-file FILE]]\n"
+                            "[--similar K [--similar-docs FILE] [--similar-file FILE]] "
+                            "[--transform DIR [--transform-file FILE]]\n"
                             "  --similar K without --similar-docs searches for every document: "
                             "ceil(N / group) scans of the scored pairs, group <= 64\n");
             return 2;

@@ -42,6 +42,7 @@ EXPORTS = [
     "tfidf_top_terms", "tfidf_doc_terms_free", "tfidf_group_top_terms", "tfidf_last_terms_info",
     "tfidf_similar", "tfidf_neighbors_free", "tfidf_group_similar", "tfidf_last_similar_info",
     "tfidf_query_bm25", "tfidf_group_query_bm25", "tfidf_last_bm25_info",
+    "tfidf_transform", "tfidf_rows_free", "tfidf_group_transform", "tfidf_last_transform_info",
 ]
 QUERY_MAX_K = 1024  # TFIDF_QUERY_MAX_K
 TERMS_MAX_K = 1024  # TFIDF_TERMS_MAX_K
@@ -159,6 +160,23 @@ class SimilarInfo(C.Structure):
     ]
 
 
+class Rows(C.Structure):
+    _fields_ = [
+        ("ndocs", C.c_uint32), ("reserved", C.c_uint32), ("npairs", C.c_uint64), ("ntokens", C.c_uint64),
+        ("row_off", C.POINTER(C.c_uint64)), ("doc_size", C.POINTER(C.c_uint32)), ("doc_oov", C.POINTER(C.c_uint32)),
+        ("term", C.POINTER(C.c_uint32)), ("count", C.POINTER(C.c_uint32)), ("df", C.POINTER(C.c_uint32)),
+        ("score", C.POINTER(C.c_double)), ("word_off", C.POINTER(C.c_uint64)), ("word_len", C.POINTER(C.c_uint32)),
+    ]
+
+
+class TransformInfo(C.Structure):
+    _fields_ = [
+        ("size", C.c_uint64), ("ndocs", C.c_uint32), ("nslices", C.c_uint32), ("ntokens", C.c_uint64),
+        ("npairs", C.c_uint64), ("noov", C.c_uint64), ("scratch_bytes", C.c_uint64), ("ms_tokens", C.c_double),
+        ("ms_resolve", C.c_double), ("ms_sort", C.c_double), ("ms_pairs", C.c_double), ("ms_total", C.c_double),
+    ]
+
+
 class DirPlan(C.Structure):
     _fields_ = [
         ("ndocs", C.c_uint32), ("nshards", C.c_uint32), ("doc_ids", C.POINTER(C.c_uint32)),
@@ -245,6 +263,11 @@ def lib() -> C.CDLL:
         L.tfidf_neighbors_free.argtypes = [C.POINTER(Neighbors)]
         L.tfidf_neighbors_free.restype = None
         L.tfidf_last_similar_info.argtypes = [C.c_void_p, C.POINTER(SimilarInfo)]
+        L.tfidf_transform.argtypes = [C.c_void_p, C.POINTER(Corpus), C.POINTER(Rows)]
+        L.tfidf_group_transform.argtypes = [C.c_void_p, C.POINTER(Corpus), C.POINTER(Rows)]
+        L.tfidf_rows_free.argtypes = [C.POINTER(Rows)]
+        L.tfidf_rows_free.restype = None
+        L.tfidf_last_transform_info.argtypes = [C.c_void_p, C.POINTER(TransformInfo)]
         if L.tfidf_abi_version() != ABI_VERSION:
             raise RuntimeError(f"{LIB_PATH}: ABI version {L.tfidf_abi_version()}, binding expects {ABI_VERSION} "
                                f"(stale build: rebuild with __graft_entry__.build())")
@@ -363,6 +386,47 @@ def _similar(fn, handle, k: int, docs, what: str) -> dict:
         }
     finally:
         lib().tfidf_neighbors_free(C.byref(t))
+
+
+def _host_corpus(data, doc_off):
+    """A host tfidf_corpus over numpy arrays; returns (Corpus, the arrays it points into)."""
+    data = np.ascontiguousarray(data, dtype=np.uint8)
+    doc_off = np.ascontiguousarray(doc_off, dtype=np.uint64)
+    c = Corpus()
+    c.bytes = data.ctypes.data if len(data) else None
+    c.nbytes = len(data)
+    c.doc_off = doc_off.ctypes.data
+    c.doc_ids = None
+    c.ndocs = len(doc_off) - 1
+    c.flags = 0
+    c.ndocs_total = 0
+    return c, (data, doc_off)
+
+
+def _transform(fn, handle, c: Corpus, batch_bytes, what: str) -> dict:
+    """tfidf_transform / tfidf_group_transform of the batch c; batch_bytes: the batch's bytes on
+    the host (the words are cut from them), or a callable that fetches them."""
+    t = Rows()
+    _chk(fn(handle, C.byref(c), C.byref(t)), what)
+    try:
+        N, P = int(t.ndocs), int(t.npairs)
+
+        def arr(p, n, dt):
+            return np.ctypeslib.as_array(p, shape=(n,)).astype(dt, copy=True) if n else np.zeros(0, dtype=dt)
+
+        out = {
+            "ndocs": N, "npairs": P, "ntokens": int(t.ntokens), "row_off": arr(t.row_off, N + 1, np.uint64),
+            "doc_size": arr(t.doc_size, N, np.uint32), "doc_oov": arr(t.doc_oov, N, np.uint32),
+            "term": arr(t.term, P, np.uint32), "count": arr(t.count, P, np.uint32), "df": arr(t.df, P, np.uint32),
+            "score": arr(t.score, P, np.float64), "word_off": arr(t.word_off, P, np.uint64),
+            "word_len": arr(t.word_len, P, np.uint32),
+        }
+    finally:
+        lib().tfidf_rows_free(C.byref(t))
+    bb = batch_bytes() if callable(batch_bytes) else batch_bytes
+    bb = bb.tobytes() if isinstance(bb, np.ndarray) else bytes(bb)
+    out["words"] = [bb[o:o + n] for o, n in zip(out["word_off"].tolist(), out["word_len"].tolist())]
+    return out
 
 
 def synth_host(seed: int, V: int, mode: int, cdf, doc_ids, ntok):
@@ -580,6 +644,30 @@ class Engine:
         _chk(lib().tfidf_last_similar_info(self.h, C.byref(t)), "tfidf_last_similar_info")
         return {k: getattr(t, k) for k, _ in SimilarInfo._fields_ if k not in ("size", "reserved")}
 
+    def transform(self, data, doc_off) -> dict:
+        """Scores a host batch of unseen documents against the resident model of the last run
+        (tfidf_transform): document r is data[doc_off[r]:doc_off[r + 1]].  Returns numpy arrays
+        row_off[ndocs + 1], doc_size / doc_oov [ndocs] and, per pair in row order, term, count,
+        df, score, word_off, word_len, plus words: the pairs' words as bytes."""
+        c, keep = _host_corpus(data, doc_off)
+        return _transform(lib().tfidf_transform, self.h, c, keep[0], "tfidf_transform")
+
+    def transform_corpus(self, c: Corpus) -> dict:
+        """Engine.transform of a tfidf_corpus, host or device (ingest_dir, synth_device, tests'
+        device copies); a device batch's bytes are copied back once to cut the words."""
+        if c.flags & TFIDF_CORPUS_DEVICE:
+            words_from = lambda: self.corpus_bytes(c)[0] if c.nbytes else b""   # noqa: E731
+        else:
+            words_from = C.string_at(c.bytes, c.nbytes) if c.nbytes and c.bytes else b""
+        return _transform(lib().tfidf_transform, self.h, c, words_from, "tfidf_transform")
+
+    def transform_info(self) -> dict:
+        """Counters and device times of the last transform (tfidf_last_transform_info)."""
+        t = TransformInfo()
+        t.size = C.sizeof(TransformInfo)
+        _chk(lib().tfidf_last_transform_info(self.h, C.byref(t)), "tfidf_last_transform_info")
+        return {k: getattr(t, k) for k, _ in TransformInfo._fields_ if k != "size"}
+
     @contextlib.contextmanager
     def fetched(self):
         """The last run's result as numpy views of the library's host arrays (tfidf_fetch
@@ -706,6 +794,19 @@ class Group:
         """The k nearest neighbours of each document over all shards (tfidf_group_similar): the
         single-shard result bit for bit; see Engine.similar."""
         return _similar(lib().tfidf_group_similar, self.h, k, docs, "tfidf_group_similar")
+
+    def transform(self, data, doc_off) -> dict:
+        """Scores a host batch against every shard's vocabulary, rows merged by word
+        (tfidf_group_transform): the single-shard result bit for bit, term = 0xFFFFFFFF; see
+        Engine.transform."""
+        c, keep = _host_corpus(data, doc_off)
+        return _transform(lib().tfidf_group_transform, self.h, c, keep[0], "tfidf_group_transform")
+
+    def transform_corpus(self, c: Corpus) -> dict:
+        """Group.transform of a tfidf_corpus (a device batch is E_INVAL)."""
+        host = not (c.flags & TFIDF_CORPUS_DEVICE)
+        bb = C.string_at(c.bytes, c.nbytes) if host and c.nbytes and c.bytes else b""
+        return _transform(lib().tfidf_group_transform, self.h, c, bb, "tfidf_group_transform")
 
 
 def plan_dir(path: str, nshards: int, threads: int = 0) -> dict:
