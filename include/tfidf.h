@@ -42,7 +42,8 @@ enum tfidf_status {
                                more share their 120-bit identity key (compared byte by byte on
                                every key match: reported, never merged) */
     TFIDF_E_STATE = -10,    /* call out of order (e.g. fetch before run) */
-    TFIDF_E_PEER = -11      /* another rank of the DF exchange failed (this rank did not) */
+    TFIDF_E_PEER = -11,     /* another rank of the DF exchange failed (this rank did not) */
+    TFIDF_E_MODEL = -12     /* a model file cannot be read or does not hold a valid model */
 };
 
 /* ---------------------------------------------------------------- corpus ---- */
@@ -612,7 +613,9 @@ typedef struct tfidf_rows {
     uint64_t* word_off;   /* offset into the BATCH's bytes of the term's first token in this document */
     uint32_t* word_len;   /* the term's length (token bytes up to its first NUL) */
 } tfidf_rows;
-/* TFIDF_E_STATE before a successful tfidf_run; TFIDF_E_INVAL for a NULL ctx, batch or out, a
+/* TFIDF_E_STATE before a successful tfidf_run or tfidf_model_import (section "model": an imported
+ * model stands for the run's, with its own copy of the term bytes in the corpus's place);
+ * TFIDF_E_INVAL for a NULL ctx, batch or out, a
  * non-monotone doc_off or doc_off[ndocs] > nbytes.  ndocs == 0 and empty documents are valid.
  * The state rules are tfidf_query's: the run's result is not disturbed (tfidf_fetch,
  * tfidf_format, tfidf_query and the others give the same bytes afterwards), the run's corpus
@@ -653,6 +656,84 @@ typedef struct tfidf_transform_info {
     double   ms_total;        /* host wall time of the whole call */
 } tfidf_transform_info;
 int tfidf_last_transform_info(const tfidf_ctx* ctx, tfidf_transform_info* info);
+
+/* ------------------------------------------------------------------- model -- */
+
+/* The model tfidf_transform scores against, as an object of its own: the term table in
+ * strcmp("word\t") order (the order of tfidf_result.term_off), the global df of every term and
+ * N.  It is exported from a fitted context or a whole group, written to a file, read back and
+ * imported into a fresh context, which then answers tfidf_transform bit for bit as the fitted
+ * context would, with no corpus anywhere.  The reference keeps none of this past its one pass
+ * (TFIDF.c:130-247).
+ * idf is never part of a model: the importing host's libm computes log(1.0 * N / df)
+ * (TFIDF.c:243), the rule of a run. */
+typedef struct tfidf_model {
+    uint64_t  size;          /* sizeof(tfidf_model), set by whoever fills the struct */
+    uint64_t  ndocs_total;   /* N of log(N/df) */
+    uint32_t  nterms;        /* V */
+    uint32_t  reserved;
+    uint64_t* term_off;      /* nterms + 1; term t = term_bytes[term_off[t], term_off[t+1]) */
+    uint8_t*  term_bytes;
+    uint32_t* term_df;       /* global df */
+} tfidf_model;
+/* Host only.  TFIDF_E_INVAL unless: size >= sizeof(tfidf_model); term_off is non-decreasing;
+ * every term is shorter than 16 MiB and holds no NUL and none of the separator bytes
+ * {0x20,0x09..0x0D} (no token contains them); the terms are strictly ascending compared as
+ * word + "\t" with strcmp on unsigned bytes (which also rules out duplicates); 1 <= df <= N for
+ * every term; nterms < 2^32 - 1.  The empty term is a term; nterms == 0 is valid for any N. */
+int tfidf_model_check(const tfidf_model* m);
+/* The context's term table, global df and N: byte for byte tfidf_fetch's term_off, term_bytes,
+ * term_df and ndocs_total, without the pairs.  The words are gathered on the device (short
+ * terms from their keys, long terms from the run's corpus, which must still be valid, or from
+ * the imported model's own bytes) and come back in three copies.  TFIDF_E_STATE unless the
+ * context holds a model, from a run or from an import.  With a communicator attached the call
+ * is local: this shard's vocabulary with the global df.  The arrays are owned by the library
+ * and released by tfidf_model_free(). */
+int tfidf_model_export(tfidf_ctx* ctx, tfidf_model* out);
+/* The model of a whole group (tfidf_group_run): every rank exports on its own host thread and
+ * the host k-way merges the sorted term tables in the same order.  A word several ranks hold is
+ * kept once; ranks that disagree on its df make the call return TFIDF_E_STATE.  Byte-identical
+ * to a single-shard export of the same corpus. */
+int tfidf_group_model_export(tfidf_group* g, tfidf_model* out);
+/* Checks the model (TFIDF_E_INVAL; the context is then left as it was) and puts the context
+ * into a model-only state: tfidf_transform and tfidf_model_export work, everything that needs
+ * pairs (tfidf_fetch, tfidf_format, tfidf_write_output_gpu, tfidf_query*, tfidf_top_terms,
+ * tfidf_similar) returns TFIDF_E_STATE.  A previous run's result is discarded; a later tfidf_run
+ * replaces the imported model as it replaces a previous run.  The context builds what a run
+ * leaves behind (the slot table, the ranks, df, the idf table of this host's libm) from its own
+ * device copy of the term bytes: the caller may free `m` as soon as the call returns.  The table
+ * has the smallest power-of-two size, not below the context's current one, that keeps V under
+ * the run's load limits; more than 2^28 slots is TFIDF_E_CAPACITY, as are two distinct terms of
+ * 16 bytes or more that share their 120-bit identity key.  The buffers belong to the context:
+ * a repeated import of the same model allocates nothing (tfidf_alloc_stats). */
+int tfidf_model_import(tfidf_ctx* ctx, const tfidf_model* m);
+/* Host only.  The file is little-endian without padding and depends on the model alone:
+ *   0  "TFIDFMDL"   8  u32 version = 1   12  u32 nterms   16  u64 ndocs_total
+ *   24 u64 nbytes = term_off[V] - term_off[0]
+ *   32 u64 FNV-1a-64 (offset basis 0xcbf29ce484222325, prime 0x100000001b3) of every byte from 40 on
+ *   40 u64 term_off[V + 1] rebased to term_off[0] = 0, then u32 term_df[V], then the term bytes
+ * save: TFIDF_E_INVAL for a model that fails tfidf_model_check, TFIDF_E_OUTPUT when the file
+ * cannot be written.  load: TFIDF_E_MODEL when the file cannot be opened, is shorter or longer
+ * than its header implies, has a wrong magic, version or checksum, or holds arrays that fail
+ * tfidf_model_check; TFIDF_E_NOMEM; *out is zeroed on every error, else released by
+ * tfidf_model_free(). */
+int tfidf_model_save(const tfidf_model* m, const char* path);
+int tfidf_model_load(const char* path, tfidf_model* out);
+/* NULL or an all-zero struct: no-op.  Only for models the library filled. */
+void tfidf_model_free(tfidf_model* m);
+/* Counters of the last tfidf_model_import or tfidf_model_export (the caller sets `size` =
+ * sizeof, as tfidf_query_info). */
+typedef struct tfidf_model_info {
+    uint64_t size;
+    uint32_t nterms;
+    uint32_t reserved;
+    uint64_t table_slots;     /* the vocabulary table's slots */
+    uint64_t blob_bytes;      /* term bytes */
+    uint64_t long_terms;      /* terms of >= 16 bytes (import; 0 after an export) */
+    double   ms_build;        /* import: device time of the table's clear + build (HIP events); export: 0 */
+    double   ms_total;        /* host wall time of the whole call */
+} tfidf_model_info;
+int tfidf_last_model_info(const tfidf_ctx* ctx, tfidf_model_info* info);
 
 /* ---------------------------------------------------------------- ingest ---- */
 

@@ -1022,6 +1022,88 @@ int tfidf_group_transform(tfidf_group* g, const tfidf_corpus* batch, tfidf_rows*
     return TFIDF_OK;
 }
 
+/* Every rank exports its own term table (tfidf_model_export is local to a context), one host
+ * thread per rank; each table is in strcmp("word\t") order, so the group's table is their
+ * k-way merge in that order.  A word several ranks hold is kept once: df is global, so the
+ * ranks agree on it (a disagreement is reported, not resolved).  N is the run's on every rank. */
+int tfidf_group_model_export(tfidf_group* g, tfidf_model* out) {
+    if (!g || !out) return TFIDF_E_INVAL;
+    memset(out, 0, sizeof(*out));
+    const int R = g->n;
+    std::vector<int> rc((size_t)R, TFIDF_OK);
+    std::vector<tfidf_model> part((size_t)R);
+    for (tfidf_model& p : part) memset(&p, 0, sizeof(p));
+    {
+        std::vector<std::thread> th;
+        for (int r = 1; r < R; ++r) th.emplace_back([&, r] { rc[r] = tfidf_model_export(g->ctx[r], &part[r]); });
+        rc[0] = tfidf_model_export(g->ctx[0], &part[0]);
+        for (auto& t : th) t.join();
+    }
+    int err = TFIDF_OK;
+    for (int r = 0; r < R && !err; ++r) err = rc[r];
+    for (int r = 1; r < R && !err; ++r)
+        if (part[r].ndocs_total != part[0].ndocs_total) err = TFIDF_E_STATE;
+    tfidf_model m;
+    memset(&m, 0, sizeof(m));
+    uint64_t vsum = 0, bsum = 0;
+    for (int r = 0; r < R && !err; ++r) {
+        vsum += part[r].nterms;
+        bsum += part[r].term_off[part[r].nterms];
+    }
+    if (!err) {
+        m.size = sizeof(tfidf_model);
+        m.ndocs_total = part[0].ndocs_total;
+        m.term_off = (uint64_t*)calloc((size_t)vsum + 1, 8);
+        m.term_df = (uint32_t*)calloc((size_t)vsum + 1, 4);
+        m.term_bytes = (uint8_t*)malloc((size_t)bsum + 1);
+        if (!m.term_off || !m.term_df || !m.term_bytes) err = TFIDF_E_NOMEM;
+    }
+    uint64_t V = 0, B = 0;
+    std::vector<uint32_t> at((size_t)R, 0u);
+    while (!err) {
+        int best = -1;
+        for (int r = 0; r < R; ++r) {
+            if (at[r] >= part[r].nterms) continue;
+            const tfidf_model& p = part[r];
+            if (best < 0) { best = r; continue; }
+            const tfidf_model& q = part[best];
+            if (word_tab_cmp(p.term_bytes + p.term_off[at[r]], (uint32_t)(p.term_off[at[r] + 1] - p.term_off[at[r]]),
+                             q.term_bytes + q.term_off[at[best]],
+                             (uint32_t)(q.term_off[at[best] + 1] - q.term_off[at[best]])) < 0)
+                best = r;
+        }
+        if (best < 0) break;
+        const tfidf_model& q = part[best];
+        const uint64_t wo = q.term_off[at[best]], wl = q.term_off[at[best] + 1] - wo;
+        const uint32_t df = q.term_df[at[best]];
+        if (V >= 0xFFFFFFFEull) { err = TFIDF_E_CAPACITY; break; }
+        m.term_off[V] = B;
+        memcpy(m.term_bytes + B, q.term_bytes + wo, (size_t)wl);
+        m.term_df[V] = df;
+        for (int r = 0; r < R; ++r) {   /* the same word on the other ranks (and this one) */
+            if (at[r] >= part[r].nterms) continue;
+            const tfidf_model& p = part[r];
+            const uint64_t po = p.term_off[at[r]], pl = p.term_off[at[r] + 1] - po;
+            if (pl != wl || (wl && memcmp(p.term_bytes + po, m.term_bytes + B, (size_t)wl) != 0)) continue;
+            if (p.term_df[at[r]] != df) err = TFIDF_E_STATE;
+            ++at[r];
+        }
+        B += wl;
+        ++V;
+    }
+    if (!err) {
+        m.term_off[V] = B;
+        m.nterms = (uint32_t)V;
+    }
+    for (tfidf_model& p : part) tfidf_model_free(&p);
+    if (err) {
+        tfidf_model_free(&m);
+        return err;
+    }
+    *out = m;
+    return TFIDF_OK;
+}
+
 void tfidf_group_close(tfidf_group* g) {
     if (!g) return;
     for (tfidf_ctx* c : g->ctx)

@@ -29,6 +29,7 @@ const char* tfidf_strerror(int s) {
     case TFIDF_E_CAPACITY: return "capacity exceeded";
     case TFIDF_E_STATE: return "call out of order";
     case TFIDF_E_PEER: return "another rank failed";
+    case TFIDF_E_MODEL: return "not a valid model file";
     default: return "unknown error";
     }
 }

@@ -662,4 +662,29 @@ struct TrPairs {
 int launch_tr_flags(const TrPairs& a, hipStream_t s);
 int launch_tr_pairs(const TrPairs& a, hipStream_t s);
 
+/* ---- the portable model (model.hip, tfidf_model_import / tfidf_model_export) ---- */
+#define ST_MODEL_DUP 256u   /* import: a term's key was in the table already (the host check excludes it) */
+/* The frozen table a run leaves behind, built from a model's term list instead: term t =
+ * blob[term_off[t], term_off[t + 1]) in term-table order, so t is the term's rank.  One lane
+ * per term: the identity key from the bytes, vocab_insert_s at home alignment ~1 with the blob
+ * in the corpus's place (a long term's rep = len << 40 | offset into the blob), then
+ * rank_of_slot[slot] = t.  The caller has cleared keys to KEY_EMPTY_HI and rank_of_slot to
+ * QUERY_NO_TERM: a lane that finds a rank already there sets ST_MODEL_DUP.  Every read of the
+ * blob is guarded by blob_bytes (ST_BOUNDS), a term of >= 16 MiB sets ST_TERM_LONG. */
+struct ModelBuild {
+    const uint64_t* term_off;    /* nterms + 1 */
+    const uint8_t* blob;
+    uint64_t blob_bytes;
+    uint32_t nterms;
+    uint4* keys;
+    uint64_t* rep;
+    uint64_t mask;               /* capacity - 1 */
+    uint32_t* rank_of_slot;
+    uint32_t* status;
+};
+int launch_model_build(const ModelBuild& a, hipStream_t s);
+/* export: term[t] = t and wlen[t] = tlen[t] for t < n, wlen[n] = 0: the identity selection and
+ * the lengths (scanned by the caller) that launch_terms_words gathers the whole table with */
+int launch_model_lens(const uint32_t* tlen, uint32_t n, uint32_t* term, uint64_t* wlen, hipStream_t s);
+
 #endif

@@ -64,6 +64,16 @@
  *                          reproduces output.txt byte for byte;
  *   --transform-file FILE  the file (default transform.txt).
  * With several shards the ranks' rows are merged by word (tfidf_group_transform).
+ *
+ * Model (the term table, the global df and N as a file: fit once, serve from the file):
+ *   --save-model FILE      after output.txt and the other files, the run's model is written to
+ *                          FILE (tfidf_model_export + tfidf_model_save; with several shards
+ *                          tfidf_group_model_export: the same bytes as with one);
+ *   --model FILE           no run: input/ is not read and output.txt is not written; FILE is
+ *                          imported (tfidf_model_load + tfidf_model_import) and --transform DIR,
+ *                          which must be given, is scored against it on one GPU.  With an option
+ *                          that needs the run's pairs (--query, --keywords, --similar,
+ *                          --save-model, --debug-jobs) it is a usage error (exit 2).
  */
 #include <dirent.h>
 #include <pthread.h>
@@ -298,6 +308,40 @@ static int run_transform(tfidf_ctx* ctx, tfidf_group* g) {
     return rc;
 }
 
+/* ------------------------------------------------------------------ model -- */
+
+static struct {
+    const char* save;   /* NULL: no model file, behaviour and bytes as without the option */
+    const char* load;
+} g_model = {NULL, NULL};
+
+/* --save-model: the model of ctx (one shard) or of every rank of g */
+static int save_model(tfidf_ctx* ctx, tfidf_group* g) {
+    if (!g_model.save) return TFIDF_OK;
+    tfidf_model m;
+    memset(&m, 0, sizeof(m));
+    int rc = g ? tfidf_group_model_export(g, &m) : tfidf_model_export(ctx, &m);
+    if (rc) return rc;
+    rc = tfidf_model_save(&m, g_model.save);
+    tfidf_model_free(&m);
+    if (rc == TFIDF_E_OUTPUT) { printf("Error Opening File: %s\n", g_model.save); return TFIDF_OK; }
+    return rc;
+}
+
+/* --model: no run; the file's model is imported and --transform scored against it */
+static int run_model(int device) {
+    tfidf_model m;
+    int rc = tfidf_model_load(g_model.load, &m);
+    if (rc) { fprintf(stderr, "tfidf: %s: %s\n", g_model.load, tfidf_strerror(rc)); return 3; }
+    tfidf_ctx* ctx = NULL;
+    rc = tfidf_open(device, &ctx);
+    if (!rc) rc = tfidf_model_import(ctx, &m);
+    tfidf_model_free(&m);   /* the context owns what it needs */
+    if (!rc) rc = run_transform(ctx, NULL);
+    tfidf_close(ctx);
+    return rc ? fail(rc) : 0;
+}
+
 /* ------------------------------------------------------------- one shard -- */
 
 static int run_single(int device, const char* indir, const char* outpath, int debug, int stats) {
@@ -343,6 +387,7 @@ static int run_single(int device, const char* indir, const char* outpath, int de
     if (!rc) rc = run_keywords(ctx, NULL);
     if (!rc) rc = run_similar(ctx, NULL);
     if (!rc) rc = run_transform(ctx, NULL);
+    if (!rc) rc = save_model(ctx, NULL);
     tfidf_close(ctx);
     if (rc) return fail(rc);
     return 0;
@@ -444,6 +489,7 @@ static int run_sharded(int ngpus, int nshards, const char* indir, const char* ou
     if (!rc) rc = run_keywords(NULL, g);
     if (!rc) rc = run_similar(NULL, g);
     if (!rc) rc = run_transform(NULL, g);
+    if (!rc) rc = save_model(NULL, g);
     tfidf_group_close(g);
     tfidf_plan_free(&plan);
     if (rc) return fail(rc);
@@ -493,6 +539,8 @@ int main(int argc, char** argv) {
         }
         else if (!strcmp(argv[i], "--transform-file") && i + 1 < argc) g_transform.file = argv[++i];
         else if (!strcmp(argv[i], "--transform") && i + 1 < argc) g_transform.dir = argv[++i];
+        else if (!strcmp(argv[i], "--save-model") && i + 1 < argc) g_model.save = argv[++i];
+        else if (!strcmp(argv[i], "--model") && i + 1 < argc) g_model.load = argv[++i];
         else if (!strcmp(argv[i], "--similar-docs") && i + 1 < argc) g_similar.docs = argv[++i];
         else if (!strcmp(argv[i], "--similar-file") && i + 1 < argc) g_similar.file = argv[++i];
         else if (!strcmp(argv[i], "--similar") && i + 1 < argc) {
@@ -505,11 +553,27 @@ int main(int argc, char** argv) {
                             "[--input DIR] [--output FILE] [--query FILE [--top K] [--hits FILE] [--bm25 [--bm25-k1 X] [--bm25-b Y]]] "
                             "[--keywords K [--keywords-file FILE]] "
                             "[--similar K [--similar-docs FILE] [--similar-file FILE]] "
-                            "[--transform DIR [--transform-file FILE]]\n"
+                            "[--transform DIR [--transform-file FILE]] [--save-model FILE]\n"
+                            "       tfidf --model FILE --transform DIR [--transform-file FILE] [--device D]\n"
                             "  --similar K without --similar-docs searches for every document: "
-                            "ceil(N / group) scans of the scored pairs, group <= 64\n");
+                            "ceil(N / group) scans of the scored pairs, group <= 64\n"
+                            "  --save-model FILE writes the run's term table, df and N; --model FILE scores "
+                            "--transform DIR against such a file without input/ or output.txt\n");
             return 2;
         }
+    }
+    if (g_model.load) {   /* a model holds no pairs: nothing to rank, list or print */
+        if (!g_transform.dir) {
+            fprintf(stderr, "tfidf: --model needs --transform DIR\n");
+            return 2;
+        }
+        if (g_query.file || g_keywords.k || g_similar.k || g_model.save || debug) {
+            fprintf(stderr, "tfidf: --model cannot be combined with --query, --keywords, --similar, --save-model or "
+                            "--debug-jobs: they need a run's pairs\n");
+            return 2;
+        }
+        if (tfidf_device_count() <= 0) return fail(TFIDF_E_NODEV);
+        return run_model(device >= 0 ? device : 0);
     }
     if (g_query.bm25 && !g_query.file) {   /* nothing to rank: say so instead of ignoring the switch */
         fprintf(stderr, "tfidf: --bm25, --bm25-k1 and --bm25-b need --query FILE\n");

@@ -43,6 +43,8 @@ EXPORTS = [
     "tfidf_similar", "tfidf_neighbors_free", "tfidf_group_similar", "tfidf_last_similar_info",
     "tfidf_query_bm25", "tfidf_group_query_bm25", "tfidf_last_bm25_info",
     "tfidf_transform", "tfidf_rows_free", "tfidf_group_transform", "tfidf_last_transform_info",
+    "tfidf_model_check", "tfidf_model_export", "tfidf_group_model_export", "tfidf_model_import",
+    "tfidf_model_save", "tfidf_model_load", "tfidf_model_free", "tfidf_last_model_info",
 ]
 QUERY_MAX_K = 1024  # TFIDF_QUERY_MAX_K
 TERMS_MAX_K = 1024  # TFIDF_TERMS_MAX_K
@@ -52,6 +54,9 @@ E_INVAL = -1
 E_STATE = -10
 TFIDF_GROUP_LOCAL = 1
 E_PEER = -11
+E_CAPACITY = -9
+E_OUTPUT = -8
+E_MODEL = -12
 
 
 class Corpus(C.Structure):
@@ -177,6 +182,20 @@ class TransformInfo(C.Structure):
     ]
 
 
+class Model(C.Structure):
+    _fields_ = [
+        ("size", C.c_uint64), ("ndocs_total", C.c_uint64), ("nterms", C.c_uint32), ("reserved", C.c_uint32),
+        ("term_off", C.POINTER(C.c_uint64)), ("term_bytes", C.POINTER(C.c_uint8)), ("term_df", C.POINTER(C.c_uint32)),
+    ]
+
+
+class ModelInfo(C.Structure):
+    _fields_ = [
+        ("size", C.c_uint64), ("nterms", C.c_uint32), ("reserved", C.c_uint32), ("table_slots", C.c_uint64),
+        ("blob_bytes", C.c_uint64), ("long_terms", C.c_uint64), ("ms_build", C.c_double), ("ms_total", C.c_double),
+    ]
+
+
 class DirPlan(C.Structure):
     _fields_ = [
         ("ndocs", C.c_uint32), ("nshards", C.c_uint32), ("doc_ids", C.POINTER(C.c_uint32)),
@@ -268,6 +287,15 @@ def lib() -> C.CDLL:
         L.tfidf_rows_free.argtypes = [C.POINTER(Rows)]
         L.tfidf_rows_free.restype = None
         L.tfidf_last_transform_info.argtypes = [C.c_void_p, C.POINTER(TransformInfo)]
+        L.tfidf_model_check.argtypes = [C.POINTER(Model)]
+        L.tfidf_model_export.argtypes = [C.c_void_p, C.POINTER(Model)]
+        L.tfidf_group_model_export.argtypes = [C.c_void_p, C.POINTER(Model)]
+        L.tfidf_model_import.argtypes = [C.c_void_p, C.POINTER(Model)]
+        L.tfidf_model_save.argtypes = [C.POINTER(Model), C.c_char_p]
+        L.tfidf_model_load.argtypes = [C.c_char_p, C.POINTER(Model)]
+        L.tfidf_model_free.argtypes = [C.POINTER(Model)]
+        L.tfidf_model_free.restype = None
+        L.tfidf_last_model_info.argtypes = [C.c_void_p, C.POINTER(ModelInfo)]
         if L.tfidf_abi_version() != ABI_VERSION:
             raise RuntimeError(f"{LIB_PATH}: ABI version {L.tfidf_abi_version()}, binding expects {ABI_VERSION} "
                                f"(stale build: rebuild with __graft_entry__.build())")
@@ -427,6 +455,68 @@ def _transform(fn, handle, c: Corpus, batch_bytes, what: str) -> dict:
     bb = bb.tobytes() if isinstance(bb, np.ndarray) else bytes(bb)
     out["words"] = [bb[o:o + n] for o, n in zip(out["word_off"].tolist(), out["word_len"].tolist())]
     return out
+
+
+def _model_dict(m: Model) -> dict:
+    """A library-filled tfidf_model as a dict of copies: N, terms (list of bytes), df, term_off,
+    term_bytes (numpy arrays)."""
+    V = int(m.nterms)
+
+    def arr(p, n, dt):
+        return np.ctypeslib.as_array(p, shape=(n,)).astype(dt, copy=True) if n else np.zeros(0, dtype=dt)
+
+    toff = arr(m.term_off, V + 1, np.uint64) if V else np.zeros(1, dtype=np.uint64)
+    tb = arr(m.term_bytes, int(toff[-1]), np.uint8)
+    raw = tb.tobytes()
+    lo = toff.tolist()
+    return {"N": int(m.ndocs_total), "terms": [raw[lo[i]:lo[i + 1]] for i in range(V)],
+            "df": arr(m.term_df, V, np.uint32), "term_off": toff, "term_bytes": tb}
+
+
+def _model_struct(model: dict, size=None):
+    """A tfidf_model over the arrays of a model dict; with term_off / term_bytes present they are
+    passed as they are (tests hand tfidf_model_check broken ones), else built from terms.
+    Returns (struct, arrays to keep alive)."""
+    df = np.ascontiguousarray(model["df"], dtype=np.uint32)
+    if "term_off" in model:
+        toff = np.ascontiguousarray(model["term_off"], dtype=np.uint64)
+        tb = np.ascontiguousarray(model["term_bytes"], dtype=np.uint8)
+    else:
+        terms = list(model["terms"])
+        toff = np.zeros(len(terms) + 1, dtype=np.uint64)
+        if terms:
+            toff[1:] = np.cumsum([len(t) for t in terms], dtype=np.uint64)
+        tb = np.frombuffer(b"".join(terms), dtype=np.uint8)
+    m = Model()
+    m.size = C.sizeof(Model) if size is None else size
+    m.ndocs_total = int(model["N"])
+    m.nterms = len(toff) - 1
+    m.term_off = toff.ctypes.data_as(C.POINTER(C.c_uint64))
+    m.term_bytes = tb.ctypes.data_as(C.POINTER(C.c_uint8)) if len(tb) else None
+    m.term_df = df.ctypes.data_as(C.POINTER(C.c_uint32)) if len(df) else None
+    return m, (toff, tb, df)
+
+
+def model_check(model: dict, size=None) -> int:
+    """tfidf_model_check (host only): 0, or E_INVAL.  size overrides the struct's size field."""
+    m, keep = _model_struct(model, size)
+    return int(lib().tfidf_model_check(C.byref(m)))
+
+
+def model_save(model: dict, path: str) -> None:
+    """tfidf_model_save (host only): the model dict as a file."""
+    m, keep = _model_struct(model)
+    _chk(lib().tfidf_model_save(C.byref(m), os.fsencode(path)), "tfidf_model_save")
+
+
+def model_load(path: str) -> dict:
+    """tfidf_model_load (host only): the file as a model dict; TfidfError E_MODEL when it is none."""
+    m = Model()
+    _chk(lib().tfidf_model_load(os.fsencode(path), C.byref(m)), "tfidf_model_load")
+    try:
+        return _model_dict(m)
+    finally:
+        lib().tfidf_model_free(C.byref(m))
 
 
 def synth_host(seed: int, V: int, mode: int, cdf, doc_ids, ntok):
@@ -668,6 +758,29 @@ class Engine:
         _chk(lib().tfidf_last_transform_info(self.h, C.byref(t)), "tfidf_last_transform_info")
         return {k: getattr(t, k) for k, _ in TransformInfo._fields_ if k != "size"}
 
+    def model_export(self) -> dict:
+        """The context's model (tfidf_model_export): N, terms (list of bytes in term-table order),
+        df, term_off, term_bytes: tfidf_fetch's term table without the pairs."""
+        m = Model()
+        _chk(lib().tfidf_model_export(self.h, C.byref(m)), "tfidf_model_export")
+        try:
+            return _model_dict(m)
+        finally:
+            lib().tfidf_model_free(C.byref(m))
+
+    def model_import(self, model: dict) -> None:
+        """Puts the context into the model-only state of tfidf_model_import: transform and
+        model_export work, everything that needs pairs raises E_STATE."""
+        m, keep = _model_struct(model)
+        _chk(lib().tfidf_model_import(self.h, C.byref(m)), "tfidf_model_import")
+
+    def model_info(self) -> dict:
+        """Counters of the last model_import / model_export (tfidf_last_model_info)."""
+        t = ModelInfo()
+        t.size = C.sizeof(ModelInfo)
+        _chk(lib().tfidf_last_model_info(self.h, C.byref(t)), "tfidf_last_model_info")
+        return {k: getattr(t, k) for k, _ in ModelInfo._fields_ if k not in ("size", "reserved")}
+
     @contextlib.contextmanager
     def fetched(self):
         """The last run's result as numpy views of the library's host arrays (tfidf_fetch
@@ -801,6 +914,16 @@ class Group:
         Engine.transform."""
         c, keep = _host_corpus(data, doc_off)
         return _transform(lib().tfidf_group_transform, self.h, c, keep[0], "tfidf_group_transform")
+
+    def model_export(self) -> dict:
+        """The model of the whole group (tfidf_group_model_export): the ranks' term tables merged,
+        byte-identical to a single-shard export of the same corpus; see Engine.model_export."""
+        m = Model()
+        _chk(lib().tfidf_group_model_export(self.h, C.byref(m)), "tfidf_group_model_export")
+        try:
+            return _model_dict(m)
+        finally:
+            lib().tfidf_model_free(C.byref(m))
 
     def transform_corpus(self, c: Corpus) -> dict:
         """Group.transform of a tfidf_corpus (a device batch is E_INVAL)."""
