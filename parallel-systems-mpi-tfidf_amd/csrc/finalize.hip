@@ -738,8 +738,6 @@ int launch_dense_emit(const uint32_t* dense, uint32_t nb, uint32_t V, const uint
 
 /* -------------------------------------------------------------------- DF -- */
 
-constexpr uint32_t DFH_RECS = 65535;      /* records per workgroup up to which no u16 bin can wrap */
-constexpr uint32_t DFH_MAXV = 65536;
 constexpr uint32_t DFH_ROUNDS = 4;        /* workgroups per resident slot at most: beyond 4 x 65535 records
                                              per slot one workgroup per slot (the wide form) */
 
@@ -941,11 +939,6 @@ __global__ void k_df_hist_atomic(uint32_t* __restrict__ rec_slot, uint64_t nrec,
  *   scan     exclusive scan of cnt (slice-major): each (slice, tile) gets its segment
  *   scatter  the same tiles again: LDS positions within the tile's segments, ranks out
  *   count    one workgroup per slice: u32 LDS bins over its ranks, df stored directly */
-constexpr uint32_t DFS_NT = 1024;
-constexpr uint32_t DFS_PER = 16;
-constexpr uint64_t DFS_TILE = (uint64_t)DFS_NT * DFS_PER;
-constexpr uint32_t DFS_SLICE = 32768;      /* u32 bins: 128 KB of LDS */
-constexpr uint32_t DFS_MAXSL = 4096;       /* slice histogram: 16 KB of LDS (V <= 134 M) */
 __global__ __launch_bounds__(DFS_NT) void k_dfs_count(uint32_t* __restrict__ rec_slot, uint64_t nrec,
                                                       const uint32_t* __restrict__ nrec_extra,
                                                       const uint32_t* __restrict__ rank_of_slot, uint64_t slot_cap,
@@ -1212,10 +1205,6 @@ int launch_gather_meta(const uint32_t* order, const uint32_t* doc_npairs, const 
 
 constexpr int K5_MAX = K5_MAX_PAIRS;
 constexpr uint32_t K5_SMALL = 64;     /* one wave, bitonic across the lanes */
-constexpr uint32_t K5_SMALL_DOC = 128; /* documents up to this many pairs: k_score_small */
-constexpr uint32_t K5_PS_SPLIT = 4096; /* presorted documents over this many pairs: chunk tasks */
-constexpr uint32_t K5_WAVE = 1024;    /* one wave, LDS radix sort of packed (rank, index) keys */
-constexpr uint32_t K5_IDX_BITS = 11;  /* index bits of a packed key (n <= 2048) */
 constexpr int K5_BATCH = 8;           /* gathers per lane in flight together */
 #ifndef K5_EB
 #define K5_EB 4                       /* wide path: idf gathers per lane in flight together */
@@ -1231,10 +1220,7 @@ constexpr int K5_BATCH = 8;           /* gathers per lane in flight together */
 #ifndef K5_WPS_WIDE
 #define K5_WPS_WIDE 4                 /* ... its wide-rank instance */
 #endif
-constexpr uint32_t K5_NB_BITS = 9;    /* bucket sort: 512 buckets by the rank's top bits */
 constexpr uint32_t K5_NB = 1u << K5_NB_BITS;
-constexpr uint32_t K5_GROUP_MAX = 48; /* larger buckets (skewed ranks): the radix path */
-constexpr uint32_t K5L_GROUP_MAX = 32; /* k_score_large: larger buckets (skewed ranks) take the radix path */
 #ifndef K5L_EB
 #define K5L_EB 8                      /* k_score_large: elements per thread in flight together */
 #endif
@@ -1977,10 +1963,6 @@ __global__ __launch_bounds__(256) void k_k5_scatter(K5Args a) {
  * instead of five.  Position of a pair = the number of smaller ranks in its document
  * (ranks are distinct within a document; presorted runs keep their order).
  * TFIDF.c:202,243-245,273. */
-constexpr int K5S_WG = 4;   /* waves per workgroup */
-#ifndef K5S_OCC
-#define K5S_OCC 6           /* workgroups per CU it is compiled for */
-#endif
 struct K5SDoc {
     uint64_t rb, ob;
     uint32_t n;

@@ -31,6 +31,26 @@
 #ifndef K5_MAX_PAIRS
 #define K5_MAX_PAIRS 4096                /* largest complete (unmerged) document K5 sorts in LDS */
 #endif
+/* The thresholds at which the DF and score stages of finalize.hip switch form: here, not in
+ * finalize.hip, so that tests/native/finalize_test.cpp builds its cases from them. */
+constexpr uint32_t DFH_RECS = 65535;      /* records per workgroup up to which no u16 bin can wrap */
+constexpr uint32_t DFH_MAXV = 65536;      /* the largest V the LDS histogram takes */
+constexpr uint32_t DFS_NT = 1024;
+constexpr uint32_t DFS_PER = 16;
+constexpr uint64_t DFS_TILE = (uint64_t)DFS_NT * DFS_PER;   /* records per tile of the sliced form */
+constexpr uint32_t DFS_SLICE = 32768;      /* u32 bins: 128 KB of LDS */
+constexpr uint32_t DFS_MAXSL = 4096;       /* slice histogram: 16 KB of LDS (V <= 134 M) */
+constexpr uint32_t K5_SMALL_DOC = 128; /* documents up to this many pairs: k_score_small */
+constexpr uint32_t K5_PS_SPLIT = 4096; /* presorted documents over this many pairs: chunk tasks */
+constexpr uint32_t K5_WAVE = 1024;    /* one wave, LDS radix sort of packed (rank, index) keys */
+constexpr uint32_t K5_IDX_BITS = 11;  /* index bits of a packed key (n <= 2048) */
+constexpr uint32_t K5_NB_BITS = 9;    /* bucket sort: 512 buckets by the rank's top bits */
+constexpr uint32_t K5_GROUP_MAX = 48; /* larger buckets (skewed ranks): the radix path */
+constexpr uint32_t K5L_GROUP_MAX = 32; /* k_score_large: larger buckets (skewed ranks) take the radix path */
+constexpr int K5S_WG = 4;   /* k_score_small: waves per workgroup */
+#ifndef K5S_OCC
+#define K5S_OCC 6           /* k_score_small: workgroups per CU it is compiled for */
+#endif
 
 /* status bits (device word) */
 #define ST_VOCAB_FULL  1u

@@ -543,9 +543,12 @@ def _doc_with_terms(rng, n, vocab):
 
 def test_score_document_classes_vs_oracle(engine):
     """K5's document classes at their boundaries (finalize.hip k5_class): <= 128 pairs
-    (k_score_small), <= 64 / <= 1024 (wave kernel: bitonic, counting, bucket paths), > 1024
+    (k_score_small), 129..1024 (the wave kernel's bucket and radix paths), > 1024
     (k_score_large, both instances), and one > 4 MiB document (dense merge: a presorted run
-    over 4096 pairs, emitted by k_emit_split's chunk tasks), among many small documents."""
+    over 4096 pairs, emitted by k_emit_split's chunk tasks), among many small documents.
+    The wave kernel's bitonic (n <= 64) and counting (n <= 128) branches are not run here or
+    by any run: k5_class lists every document of at most 128 pairs for k_score_small, and
+    launch_score_order always passes the class list (tests/native/finalize_test.cpp)."""
     rng = np.random.default_rng(11)
     vocab = [b"t%05d" % i for i in range(30000)]
     sizes = [1, 2, 63, 64, 65, 127, 128, 129, 511, 512, 513, 1023, 1024, 1025, 2047, 2048, 2049, 4096, 4097, 9000]
