@@ -569,6 +569,102 @@ typedef struct tfidf_similar_info {
 } tfidf_similar_info;
 int tfidf_last_similar_info(const tfidf_ctx* ctx, tfidf_similar_info* info);
 
+/* ---------------------------------------------------------------- clusters -- */
+
+/* Spherical k-means over the resident result of the last run: which groups the documents fall
+ * into under the cosine similarity of their TF-IDF vectors, and what each group is about.
+ *
+ * All arithmetic is IEEE binary64, round to nearest; fl() marks every rounding and no product
+ * is fused into an add.  Documents are taken in output order (the "docN@" order, position j).
+ *   norm(d)      tfidf_similar's, the same bits as tfidf_neighbors.norm
+ *   unclustered  a document with norm(d) == 0 (no pairs, or every pair has df = N): label
+ *                TFIDF_NO_CLUSTER, sim +0.0; it takes part in nothing
+ *   u(d,t)       fl(s(d,t) / norm(d)) over d's pairs, s = the run's pair_score
+ *   seeds        K global document ids; centroid 0 is C[c][t] = u(seed_c, t) on the seed's
+ *                terms and +0.0 elsewhere, not renormalised.  An id this context does not hold,
+ *                a seed with norm 0 and a repeated id are TFIDF_E_INVAL; two different
+ *                documents with equal bytes are both valid.  seeds == NULL: the clusterable
+ *                documents at indices floor(c * M / K), c = 0..K-1, M = the number of clusterable
+ *                documents counted in output order.  K > M is TFIDF_E_INVAL.
+ *   sim(d,c)     ((+0.0 + fl(u(d,t1) * C[c][t1])) + fl(u(d,t2) * C[c][t2])) + .. over all of
+ *                d's pairs in pair order (a zero centroid entry adds +0.0)
+ *   label(d)     the c with the largest sim(d,c), the lowest c among equals
+ *   update       for a cluster c with at least one member:
+ *                S[t] = ((+0.0 + u(d1,t)) + u(d2,t)) + .. over the members holding t, in
+ *                ascending output position;
+ *                sq = ((+0.0 + fl(S[t1]*S[t1])) + fl(S[t2]*S[t2])) + .. over the terms with
+ *                S[t] != 0 in ascending term rank; nrm = sqrt(sq), correctly rounded;
+ *                C[c][t] = fl(S[t] / nrm).  A cluster without members keeps its centroid.
+ *   loop         pass it = 1..max_iter: assign against the current centroids; if it > 1 and
+ *                every label equals the pass before's, stop (converged = 1); if it == max_iter,
+ *                stop (converged = 0); otherwise update.  The reported centroids are the ones
+ *                the returned labels and sims were computed against; max_iter = 1 is nearest seed.
+ *   top terms    per cluster its nterms <= min(T, number of non-zero weights) best terms, by
+ *                weight descending, then term rank ascending
+ * Everything is >= +0.0 and finite, so bit patterns order like values.  The result does not
+ * depend on grid, launch shape or budget. */
+#define TFIDF_KMEANS_MAX_K      256u
+#define TFIDF_KMEANS_MAX_TERMS  64u
+#define TFIDF_KMEANS_DEFAULT_ITER 20u
+#define TFIDF_NO_CLUSTER        0xFFFFFFFFu
+/* `size` is set by the caller to sizeof(tfidf_kmeans_params); a smaller one is TFIDF_E_INVAL. */
+typedef struct tfidf_kmeans_params {
+    uint64_t size;
+    uint32_t k;              /* 1..TFIDF_KMEANS_MAX_K */
+    uint32_t max_iter;       /* >= 1; 0: TFIDF_KMEANS_DEFAULT_ITER */
+    uint32_t nterms;         /* T, 0..TFIDF_KMEANS_MAX_TERMS */
+    uint32_t nseeds;         /* with seeds: == k */
+    const uint32_t* seeds;   /* NULL: the default seeds */
+} tfidf_kmeans_params;
+/* Arrays are owned by the library and released by tfidf_clusters_free(). */
+typedef struct tfidf_clusters {
+    uint32_t  ndocs, k;
+    uint32_t  iterations;    /* passes (assignments) made */
+    uint32_t  converged;
+    uint32_t  t, reserved;   /* row stride of the term arrays (params.nterms) */
+    uint32_t* doc;           /* per output position: global document id */
+    uint32_t* label;         /* per output position: cluster, or TFIDF_NO_CLUSTER */
+    double*   sim;           /* per output position: sim to its own centroid */
+    uint32_t* size;          /* per cluster: members */
+    uint32_t* seed;          /* per cluster: the seed id used */
+    uint32_t* nterms;        /* per cluster: entries of its row below */
+    uint32_t* term;          /* k * t, cluster c at c * t: term rank; unused entries UINT32_MAX */
+    double*   weight;        /* C[c][term]; unused entries +0.0 */
+    uint64_t* word_off;      /* k * t + 1, laid out as in tfidf_doc_terms; unused entries empty */
+    uint8_t*  word_bytes;
+} tfidf_clusters;
+/* TFIDF_E_INVAL for a NULL ctx / params / out, a short params.size, k == 0 or above
+ * TFIDF_KMEANS_MAX_K, nterms above TFIDF_KMEANS_MAX_TERMS, seeds with nseeds != k, bad seeds, or
+ * k > M.  TFIDF_E_STATE before a successful tfidf_run and on a context that holds only an
+ * imported model.  The run's result is not disturbed; the run's corpus must still be valid
+ * (long terms' bytes are read from it); with a communicator attached the call is local to the
+ * shard.  The dense centroid matrix takes k * V * 8 bytes (the update's sums are built in it)
+ * and, with 24 bytes per document and the per-cluster words, must fit under TFIDF_KMEANS_MB MiB
+ * (read at tfidf_open, default 1024: a guess, nobody has measured what a caller needs); over it
+ * the call returns TFIDF_E_CAPACITY before any device work.  TFIDF_KMEANS_SPLIT (read at
+ * tfidf_open) sets the update's workgroups per cluster; the result does not depend on it.  All
+ * buffers belong to the context, so a repeated identical call allocates nothing
+ * (tfidf_alloc_stats).  On an error *out is zeroed. */
+int tfidf_kmeans(tfidf_ctx* ctx, const tfidf_kmeans_params* params, tfidf_clusters* out);
+void tfidf_clusters_free(tfidf_clusters* c);
+/* Counters of the last tfidf_kmeans (the caller sets `size` = sizeof, as tfidf_query_info). */
+typedef struct tfidf_kmeans_info {
+    uint64_t size;
+    uint32_t ndocs, k;
+    uint32_t passes;          /* assignments */
+    uint32_t updates;
+    uint32_t clusterable;     /* M */
+    uint32_t split;           /* update workgroups per cluster */
+    uint64_t matrix_bytes;    /* k * V * 8 */
+    uint64_t work_bytes;      /* the other buffers counted against the budget */
+    double   ms_norms;        /* device times (HIP events), summed over the passes; norms 0 when cached */
+    double   ms_assign;
+    double   ms_update;
+    double   ms_terms;
+    double   ms_total;        /* host wall time of the whole call */
+} tfidf_kmeans_info;
+int tfidf_last_kmeans_info(const tfidf_ctx* ctx, tfidf_kmeans_info* info);
+
 /* --------------------------------------------------------------- transform -- */
 
 /* Fit/transform: scores documents the run has not seen against the resident model of the last

@@ -186,6 +186,16 @@ __device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
     return (uint32_t)__builtin_amdgcn_readlane((int)wave_incl_scan(v), 63);
 }
 
+/* lane l's 64-bit value in every lane (l uniform): two v_readlane, no LDS */
+__device__ __forceinline__ uint64_t bcast_u64(uint64_t b, int l) {
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)b, l);
+    const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(b >> 32), l);
+    return ((uint64_t)hi << 32) | lo;
+}
+__device__ __forceinline__ double bcast_f64(double v, int l) {
+    return __longlong_as_double((long long)bcast_u64((uint64_t)__double_as_longlong(v), l));
+}
+
 /* Workgroup barrier that orders LDS only.  __syncthreads() is a release/acquire fence over
  * all address spaces, so it also waits for every outstanding global store of the wave
  * (vmcnt(0)); kernels whose barriers only publish LDS data use this one. */

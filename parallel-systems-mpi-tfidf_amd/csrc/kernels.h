@@ -707,4 +707,56 @@ int launch_model_build(const ModelBuild& a, hipStream_t s);
  * the lengths (scanned by the caller) that launch_terms_words gathers the whole table with */
 int launch_model_lens(const uint32_t* tlen, uint32_t n, uint32_t* term, uint64_t* wlen, hipStream_t s);
 
+/* ---- spherical k-means over the resident result (kmeans.hip, tfidf_kmeans) ---- */
+#define KM_MAX_K      256u          /* four accumulators per lane of the owner wave */
+#define KM_MAX_TERMS  64u
+#define KM_NO_CLUSTER 0xFFFFFFFFu
+#define KM_TOP_SLICES 64u           /* term slices of a round of the top-term selection */
+/* The centroid matrix C is dense, [V][K] (a term's K weights are one contiguous row), indexed
+ * with 64-bit offsets.  norm is launch_sim_norms's, by output position. */
+struct KmArgs {
+    const uint64_t* out_off;
+    const uint32_t* out_term;
+    const double* out_score;
+    const double* norm;
+    uint32_t ndocs;
+    uint64_t npairs;
+    uint32_t V;
+    uint32_t K;
+    double* C;
+    uint32_t* label;             /* [ndocs] this pass's labels (KM_NO_CLUSTER: norm 0) */
+    const uint32_t* prev;        /* [ndocs] the pass before's (null: the first pass) */
+    double* sim;                 /* [ndocs] similarity to the document's own centroid */
+    uint32_t* changed;           /* documents whose label differs from prev */
+    uint32_t* size;              /* [K] members per cluster */
+    uint32_t* moff;              /* [K + 1] exclusive scan of size */
+    uint32_t* members;           /* [ndocs] output positions by cluster, ascending inside a cluster */
+    const uint32_t* seedpos;     /* [K] output positions of the seeds */
+    double* cnorm;               /* [K] */
+};
+/* id[j] = the global id of the document at output position j */
+int launch_km_docs(const uint32_t* order, const uint32_t* doc_ids, uint32_t ndocs, uint32_t* id, hipStream_t s);
+/* C = 0, then column c = the unit vector of the document at seedpos[c] */
+int launch_km_seed(const KmArgs& a, hipStream_t s);
+/* one pass over the pairs: label, sim, size (zeroed here) and changed (zeroed here) */
+int launch_km_assign(const KmArgs& a, uint32_t ncu, hipStream_t s);
+/* the centroids of the clusters with members from label / size; `split` workgroups per cluster,
+ * each owning a range of term ranks (the result does not depend on it) */
+int launch_km_update(const KmArgs& a, uint32_t split, hipStream_t s);
+/* the T best (weight descending, term rank ascending) non-zero entries of every column:
+ * term / weight bits at [c * T, c * T + n[c]), the rest 0xFFFFFFFF / 0; wlen = the selected
+ * terms' byte lengths (T * K + 1 words, the last 0).  part: K * KM_TOP_SLICES * 16 bytes, prev: K * 16 */
+struct KmTopArgs {
+    const double* C;
+    uint32_t V, K, T;
+    const uint32_t* tlen;
+    uint64_t* part;
+    uint64_t* prev;
+    uint32_t* term;
+    uint64_t* weight;
+    uint32_t* n;
+    uint64_t* wlen;
+};
+int launch_km_top(const KmTopArgs& a, hipStream_t s);
+
 #endif

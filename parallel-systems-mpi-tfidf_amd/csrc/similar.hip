@@ -45,15 +45,6 @@ constexpr int NT = 256;
 inline unsigned grid_for(uint64_t n, int nt = NT) { return n ? (unsigned)((n + nt - 1) / nt) : 1u; }
 int ok() { return hipGetLastError() == hipSuccess ? 0 : -1; }
 
-__device__ __forceinline__ uint64_t bcast_u64(uint64_t b, int l) {
-    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)b, l);
-    const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(b >> 32), l);
-    return ((uint64_t)hi << 32) | lo;
-}
-__device__ __forceinline__ double bcast_f64(double v, int l) {
-    return __longlong_as_double((long long)bcast_u64((uint64_t)__double_as_longlong(v), l));
-}
-
 /* ------------------------------------------------------------------- norms -- */
 
 __global__ __launch_bounds__(NT) void k_sim_norms(const uint64_t* out_off, const double* out_score, uint32_t ndocs,

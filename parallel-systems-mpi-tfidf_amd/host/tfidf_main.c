@@ -54,6 +54,20 @@
  *   --similar-file FILE   the neighbours file (default similar.txt).
  * With several shards the result is the single-shard one (tfidf_group_similar).
  *
+ * Clusters (spherical k-means over the TF-IDF vectors, tfidf_kmeans):
+ *   --clusters K           after output.txt (and the files of --query, --keywords and --similar),
+ *                          K clusters, 1..TFIDF_KMEANS_MAX_K.  First one line per cluster,
+ *                          "c<i>\t<size>\t<word>:%.16f <word>:%.16f ..", its best terms by weight
+ *                          descending; then one line per document in "docN@" order,
+ *                          "doc<N>\tc<i>\t%.16f" (the similarity to its centroid), or
+ *                          "doc<N>\t-\t0.0000000000000000" for a document whose every score is 0;
+ *   --clusters-iter I      at most I passes (default 20);
+ *   --clusters-seeds FILE  the K seed document ids (one per line) instead of the default seeds;
+ *   --clusters-terms T     terms per cluster line, 0..TFIDF_KMEANS_MAX_TERMS (default 10);
+ *   --clusters-file FILE   the clusters file (default clusters.txt).
+ * One shard only: with --gpus or --shards above 1 the option is refused (the shards' term tables
+ * differ, so they share no centroid matrix).
+ *
  * Transform (documents the run has not seen, scored with the run's vocabulary, df, N and idf,
  * tfidf_transform):
  *   --transform DIR        after output.txt (and the other files), DIR/doc1..docM are read under
@@ -262,6 +276,69 @@ static int run_similar(tfidf_ctx* ctx, tfidf_group* g) {
     return rc;
 }
 
+/* --------------------------------------------------------------- clusters -- */
+
+static struct {
+    uint32_t k;         /* 0: no clustering, behaviour and bytes as without the option */
+    uint32_t iter, terms;
+    const char* seeds;  /* NULL: the default seeds */
+    const char* file;
+} g_clusters = {0, 0, 10, NULL, "clusters.txt"};
+
+/* --clusters: k-means over the documents of ctx */
+static int run_clusters(tfidf_ctx* ctx) {
+    if (!g_clusters.k) return TFIDF_OK;
+    uint32_t* ids = NULL;
+    uint32_t nids = 0;
+    if (g_clusters.seeds) {
+        FILE* f = fopen(g_clusters.seeds, "r");
+        if (!f) { printf("Error Opening File: %s\n", g_clusters.seeds); return TFIDF_OK; }
+        size_t cap = 256;
+        ids = (uint32_t*)malloc(cap * sizeof(uint32_t));
+        unsigned long long v;
+        while (ids && fscanf(f, "%llu", &v) == 1) {
+            if (nids == cap) { cap *= 2; ids = (uint32_t*)realloc(ids, cap * sizeof(uint32_t)); }
+            if (ids) ids[nids++] = v > 0xFFFFFFFFull ? 0u : (uint32_t)v;   /* no document has id 0 */
+        }
+        fclose(f);
+        if (!ids) return TFIDF_E_NOMEM;
+    }
+    tfidf_kmeans_params p;
+    memset(&p, 0, sizeof(p));
+    p.size = sizeof(p);
+    p.k = g_clusters.k;
+    p.max_iter = g_clusters.iter;
+    p.nterms = g_clusters.terms;
+    p.seeds = ids;
+    p.nseeds = nids;
+    tfidf_clusters c;
+    memset(&c, 0, sizeof(c));
+    int rc = tfidf_kmeans(ctx, &p, &c);
+    free(ids);
+    if (rc == TFIDF_E_INVAL)
+        fprintf(stderr, "tfidf: --clusters: K exceeds the documents with a non-zero vector, or a bad seed list\n");
+    if (rc) return rc;
+    FILE* f = fopen(g_clusters.file, "w");
+    if (!f) printf("Error Opening File: %s\n", g_clusters.file);
+    for (uint32_t i = 0; f && i < c.k; ++i) {
+        fprintf(f, "c%u\t%u\t", i, c.size[i]);
+        for (uint32_t j = 0; j < c.nterms[i]; ++j) {
+            const size_t e = (size_t)i * c.t + j;
+            if (j) fputc(' ', f);
+            fwrite(c.word_bytes + c.word_off[e], 1, (size_t)(c.word_off[e + 1] - c.word_off[e]), f);
+            fprintf(f, ":%.16f", c.weight[e]);
+        }
+        fputc('\n', f);
+    }
+    for (uint32_t j = 0; f && j < c.ndocs; ++j) {
+        if (c.label[j] == TFIDF_NO_CLUSTER) fprintf(f, "doc%u\t-\t%.16f\n", c.doc[j], 0.0);
+        else fprintf(f, "doc%u\tc%u\t%.16f\n", c.doc[j], c.label[j], c.sim[j]);
+    }
+    if (f && fclose(f) != 0) rc = TFIDF_E_OUTPUT;
+    tfidf_clusters_free(&c);
+    return rc;
+}
+
 /* -------------------------------------------------------------- transform -- */
 
 static struct {
@@ -386,6 +463,7 @@ static int run_single(int device, const char* indir, const char* outpath, int de
     rc = run_queries(ctx, NULL);
     if (!rc) rc = run_keywords(ctx, NULL);
     if (!rc) rc = run_similar(ctx, NULL);
+    if (!rc) rc = run_clusters(ctx);
     if (!rc) rc = run_transform(ctx, NULL);
     if (!rc) rc = save_model(ctx, NULL);
     tfidf_close(ctx);
@@ -541,6 +619,23 @@ int main(int argc, char** argv) {
         else if (!strcmp(argv[i], "--transform") && i + 1 < argc) g_transform.dir = argv[++i];
         else if (!strcmp(argv[i], "--save-model") && i + 1 < argc) g_model.save = argv[++i];
         else if (!strcmp(argv[i], "--model") && i + 1 < argc) g_model.load = argv[++i];
+        else if (!strcmp(argv[i], "--clusters-seeds") && i + 1 < argc) g_clusters.seeds = argv[++i];
+        else if (!strcmp(argv[i], "--clusters-file") && i + 1 < argc) g_clusters.file = argv[++i];
+        else if (!strcmp(argv[i], "--clusters-iter") && i + 1 < argc) {
+            const long v = atol(argv[++i]);
+            if (v < 1 || v > 1000000L) { fprintf(stderr, "tfidf: --clusters-iter takes 1..1000000\n"); return 2; }
+            g_clusters.iter = (uint32_t)v;
+        }
+        else if (!strcmp(argv[i], "--clusters-terms") && i + 1 < argc) {
+            const long v = atol(argv[++i]);
+            if (v < 0 || v > (long)TFIDF_KMEANS_MAX_TERMS) { fprintf(stderr, "tfidf: --clusters-terms takes 0..%u\n", TFIDF_KMEANS_MAX_TERMS); return 2; }
+            g_clusters.terms = (uint32_t)v;
+        }
+        else if (!strcmp(argv[i], "--clusters") && i + 1 < argc) {
+            const long k = atol(argv[++i]);
+            if (k < 1 || k > (long)TFIDF_KMEANS_MAX_K) { fprintf(stderr, "tfidf: --clusters takes 1..%u\n", TFIDF_KMEANS_MAX_K); return 2; }
+            g_clusters.k = (uint32_t)k;
+        }
         else if (!strcmp(argv[i], "--similar-docs") && i + 1 < argc) g_similar.docs = argv[++i];
         else if (!strcmp(argv[i], "--similar-file") && i + 1 < argc) g_similar.file = argv[++i];
         else if (!strcmp(argv[i], "--similar") && i + 1 < argc) {
@@ -553,6 +648,7 @@ int main(int argc, char** argv) {
                             "[--input DIR] [--output FILE] [--query FILE [--top K] [--hits FILE] [--bm25 [--bm25-k1 X] [--bm25-b Y]]] "
                             "[--keywords K [--keywords-file FILE]] "
                             "[--similar K [--similar-docs FILE] [--similar-file FILE]] "
+                            "[--clusters K [--clusters-iter I] [--clusters-seeds FILE] [--clusters-terms T] [--clusters-file FILE]] "
                             "[--transform DIR [--transform-file FILE]] [--save-model FILE]\n"
                             "       tfidf --model FILE --transform DIR [--transform-file FILE] [--device D]\n"
                             "  --similar K without --similar-docs searches for every document: "
@@ -567,8 +663,8 @@ int main(int argc, char** argv) {
             fprintf(stderr, "tfidf: --model needs --transform DIR\n");
             return 2;
         }
-        if (g_query.file || g_keywords.k || g_similar.k || g_model.save || debug) {
-            fprintf(stderr, "tfidf: --model cannot be combined with --query, --keywords, --similar, --save-model or "
+        if (g_query.file || g_keywords.k || g_similar.k || g_clusters.k || g_model.save || debug) {
+            fprintf(stderr, "tfidf: --model cannot be combined with --query, --keywords, --similar, --clusters, --save-model or "
                             "--debug-jobs: they need a run's pairs\n");
             return 2;
         }
@@ -591,6 +687,11 @@ int main(int argc, char** argv) {
     if (ngpus <= 0) ngpus = 1;
     if (ngpus > visible) ngpus = visible;
     if (nshards <= 0) nshards = ngpus;
+    if (g_clusters.k && nshards != 1) {
+        fprintf(stderr, "tfidf: --clusters runs on one shard only: the shards' term tables differ, so they share no "
+                        "centroid matrix (drop --gpus / --shards)\n");
+        return 2;
+    }
     if (nshards == 1) return run_single(device >= 0 ? device : 0, indir, outpath, debug, stats);
     if (device > 0) return fail(TFIDF_E_INVAL);   /* several shards use devices 0..N-1 */
     return run_sharded(ngpus, nshards, indir, outpath, debug, stats);

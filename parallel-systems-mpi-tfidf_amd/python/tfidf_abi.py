@@ -41,6 +41,7 @@ EXPORTS = [
     "tfidf_query", "tfidf_hits_free", "tfidf_group_query", "tfidf_last_query_info",
     "tfidf_top_terms", "tfidf_doc_terms_free", "tfidf_group_top_terms", "tfidf_last_terms_info",
     "tfidf_similar", "tfidf_neighbors_free", "tfidf_group_similar", "tfidf_last_similar_info",
+    "tfidf_kmeans", "tfidf_clusters_free", "tfidf_last_kmeans_info",
     "tfidf_query_bm25", "tfidf_group_query_bm25", "tfidf_last_bm25_info",
     "tfidf_transform", "tfidf_rows_free", "tfidf_group_transform", "tfidf_last_transform_info",
     "tfidf_model_check", "tfidf_model_export", "tfidf_group_model_export", "tfidf_model_import",
@@ -49,6 +50,9 @@ EXPORTS = [
 QUERY_MAX_K = 1024  # TFIDF_QUERY_MAX_K
 TERMS_MAX_K = 1024  # TFIDF_TERMS_MAX_K
 SIMILAR_MAX_K = 1024  # TFIDF_SIMILAR_MAX_K
+KMEANS_MAX_K = 256  # TFIDF_KMEANS_MAX_K
+KMEANS_MAX_TERMS = 64  # TFIDF_KMEANS_MAX_TERMS
+NO_CLUSTER = 0xFFFFFFFF  # TFIDF_NO_CLUSTER: tfidf_clusters.label of a document with norm 0
 NO_POS = 0xFFFFFFFF  # tfidf_doc_terms.pos of a document the shard does not hold
 E_INVAL = -1
 E_STATE = -10
@@ -161,6 +165,32 @@ class SimilarInfo(C.Structure):
         ("size", C.c_uint64), ("rows", C.c_uint32), ("k", C.c_uint32), ("ngroups", C.c_uint32),
         ("group_rows", C.c_uint32), ("acc_bytes", C.c_uint64), ("big_docs", C.c_uint32), ("reserved", C.c_uint32),
         ("ms_norms", C.c_double), ("ms_table", C.c_double), ("ms_score", C.c_double), ("ms_topk", C.c_double),
+        ("ms_total", C.c_double),
+    ]
+
+
+class KmeansParams(C.Structure):
+    _fields_ = [
+        ("size", C.c_uint64), ("k", C.c_uint32), ("max_iter", C.c_uint32), ("nterms", C.c_uint32),
+        ("nseeds", C.c_uint32), ("seeds", C.POINTER(C.c_uint32)),
+    ]
+
+
+class Clusters(C.Structure):
+    _fields_ = [
+        ("ndocs", C.c_uint32), ("k", C.c_uint32), ("iterations", C.c_uint32), ("converged", C.c_uint32),
+        ("t", C.c_uint32), ("reserved", C.c_uint32), ("doc", C.POINTER(C.c_uint32)), ("label", C.POINTER(C.c_uint32)),
+        ("sim", C.POINTER(C.c_double)), ("size", C.POINTER(C.c_uint32)), ("seed", C.POINTER(C.c_uint32)),
+        ("nterms", C.POINTER(C.c_uint32)), ("term", C.POINTER(C.c_uint32)), ("weight", C.POINTER(C.c_double)),
+        ("word_off", C.POINTER(C.c_uint64)), ("word_bytes", C.POINTER(C.c_uint8)),
+    ]
+
+
+class KmeansInfo(C.Structure):
+    _fields_ = [
+        ("size", C.c_uint64), ("ndocs", C.c_uint32), ("k", C.c_uint32), ("passes", C.c_uint32), ("updates", C.c_uint32),
+        ("clusterable", C.c_uint32), ("split", C.c_uint32), ("matrix_bytes", C.c_uint64), ("work_bytes", C.c_uint64),
+        ("ms_norms", C.c_double), ("ms_assign", C.c_double), ("ms_update", C.c_double), ("ms_terms", C.c_double),
         ("ms_total", C.c_double),
     ]
 
@@ -282,6 +312,10 @@ def lib() -> C.CDLL:
         L.tfidf_neighbors_free.argtypes = [C.POINTER(Neighbors)]
         L.tfidf_neighbors_free.restype = None
         L.tfidf_last_similar_info.argtypes = [C.c_void_p, C.POINTER(SimilarInfo)]
+        L.tfidf_kmeans.argtypes = [C.c_void_p, C.POINTER(KmeansParams), C.POINTER(Clusters)]
+        L.tfidf_clusters_free.argtypes = [C.POINTER(Clusters)]
+        L.tfidf_clusters_free.restype = None
+        L.tfidf_last_kmeans_info.argtypes = [C.c_void_p, C.POINTER(KmeansInfo)]
         L.tfidf_transform.argtypes = [C.c_void_p, C.POINTER(Corpus), C.POINTER(Rows)]
         L.tfidf_group_transform.argtypes = [C.c_void_p, C.POINTER(Corpus), C.POINTER(Rows)]
         L.tfidf_rows_free.argtypes = [C.POINTER(Rows)]
@@ -733,6 +767,50 @@ class Engine:
         t.size = C.sizeof(SimilarInfo)
         _chk(lib().tfidf_last_similar_info(self.h, C.byref(t)), "tfidf_last_similar_info")
         return {k: getattr(t, k) for k, _ in SimilarInfo._fields_ if k not in ("size", "reserved")}
+
+    def kmeans(self, k: int, max_iter: int = 0, nterms: int = 10, seeds=None) -> dict:
+        """Spherical k-means over this shard's documents (tfidf_kmeans).  seeds: None for the
+        default seeds or k global document ids; max_iter 0 is the default (20).  Returns
+        iterations, converged and numpy arrays doc[n], label[n] (NO_CLUSTER: norm 0), sim[n] in
+        output order, size[k], seed[k], nterms[k], term[k, nterms], weight[k, nterms] and
+        words (per cluster the list of its best terms' bytes)."""
+        sd = None if seeds is None else np.ascontiguousarray(seeds, dtype=np.uint32)
+        p = KmeansParams()
+        p.size = C.sizeof(KmeansParams)
+        p.k, p.max_iter, p.nterms = k, max_iter, nterms
+        p.nseeds = 0 if sd is None else len(sd)
+        if sd is not None and len(sd):
+            p.seeds = sd.ctypes.data_as(C.POINTER(C.c_uint32))
+        elif sd is not None:
+            p.seeds = np.zeros(1, dtype=np.uint32).ctypes.data_as(C.POINTER(C.c_uint32))   # an empty list is a list
+        t = Clusters()
+        _chk(lib().tfidf_kmeans(self.h, C.byref(p), C.byref(t)), "tfidf_kmeans")
+        try:
+            n, K, T = int(t.ndocs), int(t.k), int(t.t)
+
+            def arr(ptr, m, dt):
+                return np.ctypeslib.as_array(ptr, shape=(m,)).astype(dt, copy=True) if m else np.zeros(0, dtype=dt)
+
+            out = {
+                "k": K, "iterations": int(t.iterations), "converged": int(t.converged),
+                "doc": arr(t.doc, n, np.uint32), "label": arr(t.label, n, np.uint32), "sim": arr(t.sim, n, np.float64),
+                "size": arr(t.size, K, np.uint32), "seed": arr(t.seed, K, np.uint32), "nterms": arr(t.nterms, K, np.uint32),
+                "term": arr(t.term, K * T, np.uint32).reshape(K, T), "weight": arr(t.weight, K * T, np.float64).reshape(K, T),
+            }
+            woff = arr(t.word_off, K * T + 1, np.uint64).tolist()
+            wb = bytes(arr(t.word_bytes, woff[-1], np.uint8))
+            nt = out["nterms"].tolist()
+            out["words"] = [[wb[woff[c * T + i]:woff[c * T + i + 1]] for i in range(nt[c])] for c in range(K)]
+            return out
+        finally:
+            lib().tfidf_clusters_free(C.byref(t))
+
+    def kmeans_info(self) -> dict:
+        """Counters and device times of the last kmeans (tfidf_last_kmeans_info)."""
+        t = KmeansInfo()
+        t.size = C.sizeof(KmeansInfo)
+        _chk(lib().tfidf_last_kmeans_info(self.h, C.byref(t)), "tfidf_last_kmeans_info")
+        return {k: getattr(t, k) for k, _ in KmeansInfo._fields_ if k != "size"}
 
     def transform(self, data, doc_off) -> dict:
         """Scores a host batch of unseen documents against the resident model of the last run
