@@ -240,4 +240,27 @@ __device__ __forceinline__ uint32_t block_excl_scan(uint32_t v, uint32_t* wsum, 
     return base + inc - v;
 }
 
+/* ---- the resident result as its readers (query, BM25, terms, similar, kmeans) walk it ---- */
+
+/* the pair range of the document at output position j, clamped to the run's pair total */
+__device__ __forceinline__ void pair_range(const uint64_t* out_off, uint64_t npairs, uint32_t j, uint64_t& b, uint64_t& e) {
+    b = out_off[j];
+    e = out_off[j + 1];
+    if (e > npairs) e = npairs;
+    if (b > e) b = e;
+}
+
+/* the global id of the document at output position j (doc_ids null: index + 1) */
+__device__ __forceinline__ uint32_t doc_id_at(const uint32_t* order, const uint32_t* doc_ids, uint32_t j) {
+    const uint32_t d = order[j];
+    return doc_ids ? doc_ids[d] : d + 1u;
+}
+
+/* the elected lane or thread hands `value` (a document over QS_BIG pairs) to the second launch:
+ * big_list has `bound` entries, its readers clamp big_count to the same bound */
+__device__ __forceinline__ void hand_to_big(uint32_t* big_list, uint32_t* big_count, uint32_t bound, uint32_t value) {
+    const uint32_t at = atomicAdd(big_count, 1u);
+    if (at < bound) big_list[at] = value;
+}
+
 #endif

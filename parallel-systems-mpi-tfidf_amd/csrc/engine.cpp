@@ -2497,6 +2497,101 @@ int tfidf_bm25_params_check(const tfidf_bm25_params* p, Bm25Call* out) {
     return TFIDF_OK;
 }
 
+/* ---- what tfidf_query, tfidf_query_bm25 and tfidf_similar share on the host: the group
+ * budget, the top-k rounds over a group's dense accumulators, the read-back of the result ---- */
+static_assert(SG_MAX == QG_MAX, "queries and rows share one group budget");
+struct TopkPlan {
+    uint64_t nsl0;      /* slices of the first round */
+    uint64_t per_q;     /* bytes of accumulators and candidates per query (row) */
+    uint64_t G;         /* queries (rows) per group */
+    uint64_t cand_el;   /* entries of one candidate buffer */
+};
+static TopkPlan topk_plan(uint32_t N, uint32_t k, uint32_t rows, uint64_t acc_bytes) {
+    TopkPlan p{};
+    p.nsl0 = ((uint64_t)N + QT_SLICE - 1) / QT_SLICE;
+    p.per_q = (uint64_t)N * 12 + 2 * (p.nsl0 * k * 12 + p.nsl0 * 4) + 8;
+    p.G = acc_bytes / p.per_q;
+    p.G = p.G < 1 ? 1 : (p.G > QG_MAX ? QG_MAX : p.G);
+    if (p.G > rows) p.G = rows ? rows : 1;
+    p.cand_el = p.G * p.nsl0 * k;
+    return p;
+}
+/* the plan's buffers: apart from the budget, because a call with nothing to scan allocates nothing */
+static int topk_ensure(tfidf_ctx* ctx, const TopkPlan& p, uint32_t N) {
+    ENSURE(ctx->q_acc, p.G * N * 8);
+    ENSURE(ctx->q_cnt, p.G * N * 4);
+    ENSURE(ctx->q_big, (size_t)N * 4 + 4);
+    ENSURE(ctx->q_cand0, p.cand_el * 12 + p.G * p.nsl0 * 4);
+    ENSURE(ctx->q_cand1, p.cand_el * 12 + p.G * p.nsl0 * 4);
+    ENSURE(ctx->q_misc, p.G * 8 + 16);
+    return TFIDF_OK;
+}
+/* a candidate buffer: cand_el score bits, cand_el ids, then the lists' lengths */
+struct TopkCand {
+    uint64_t* s;
+    uint32_t* id;
+    uint32_t* n;
+};
+static TopkCand topk_cand(tfidf_ctx* ctx, const TopkPlan& p, int c) {
+    uint64_t* s = (c ? ctx->q_cand1 : ctx->q_cand0).as<uint64_t>();
+    uint32_t* id = (uint32_t*)(s + p.cand_el);
+    return TopkCand{s, id, id + p.cand_el};
+}
+/* the top-k rounds of a group of gn queries (rows): the accumulators' slices, then the slices'
+ * lists until one is left per query: row q = entries [q * k, q * k + n[q]) of *res */
+static int topk_rounds(tfidf_ctx* ctx, const TopkPlan& p, const double* acc, const uint32_t* cnt, uint32_t N, uint32_t k,
+                       uint32_t gn, unsigned long long* d_nm, TopkCand* res) {
+    hipStream_t s = ctx->stream;
+    int cur = 0;
+    TopkCand o = topk_cand(ctx, p, cur);
+    QTopkArgs ta{};
+    ta.acc = acc;
+    ta.cnt = cnt;
+    ta.order = ctx->order;
+    ta.doc_ids = ctx->dev_ids;
+    ta.n_in = N;
+    ta.kk = k;
+    ta.out_s = o.s;
+    ta.out_id = o.id;
+    ta.out_n = o.n;
+    ta.out_slices = (uint32_t)p.nsl0;
+    ta.nmatch = d_nm;
+    if (launch_query_topk(ta, gn, s)) { HIPCHK(hipGetLastError()); return TFIDF_E_HIP; }
+    uint64_t nsl = p.nsl0;
+    while (nsl > 1) {
+        const TopkCand in = o;
+        QTopkArgs tb{};
+        tb.in_s = in.s;
+        tb.in_id = in.id;
+        tb.in_n = in.n;
+        tb.in_slices = (uint32_t)nsl;
+        tb.n_in = nsl * k;
+        tb.kk = k;
+        nsl = (tb.n_in + QT_SLICE - 1) / QT_SLICE;
+        cur ^= 1;
+        o = topk_cand(ctx, p, cur);
+        tb.out_s = o.s;
+        tb.out_id = o.id;
+        tb.out_n = o.n;
+        tb.out_slices = (uint32_t)nsl;
+        tb.nmatch = d_nm;
+        if (launch_query_topk(tb, gn, s)) { HIPCHK(hipGetLastError()); return TFIDF_E_HIP; }
+    }
+    *res = o;
+    return TFIDF_OK;
+}
+/* the result of topk_rounds and the match counts on the host; waits for the stream */
+static int topk_read_back(tfidf_ctx* ctx, const TopkCand& res, const unsigned long long* d_nm, uint32_t gn, uint32_t k,
+                          uint64_t* h_s, uint32_t* h_id, uint32_t* h_n, uint64_t* h_nm) {
+    hipStream_t s = ctx->stream;
+    HIPCHK(hipMemcpyAsync(h_s, res.s, (size_t)gn * k * 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(h_id, res.id, (size_t)gn * k * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(h_n, res.n, (size_t)gn * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(h_nm, d_nm, (size_t)gn * 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return TFIDF_OK;
+}
+
 int tfidf_ctx_query(tfidf_ctx* ctx, const tfidf_queries* qs, uint32_t k, tfidf_hits* out, std::vector<uint8_t>* found_out,
                     std::vector<uint64_t>* found_off_out, const Bm25Call* bm) {
     if (!ctx || !qs || !out) return TFIDF_E_INVAL;
@@ -2637,21 +2732,13 @@ int tfidf_ctx_query(tfidf_ctx* ctx, const tfidf_queries* qs, uint32_t k, tfidf_h
     /* BM25 with avgdl 0 (L = 0: no document of the context has a token, so there are no pairs):
      * N = 0 turns every group below off and the rows stay empty, as the header defines */
     const uint32_t N = bm && !(avgdl > 0.0) ? 0u : ctx->ndocs;
-    const uint64_t nsl0 = ((uint64_t)N + QT_SLICE - 1) / QT_SLICE;
-    const uint64_t per_q = (uint64_t)N * 12 + 2 * (nsl0 * k * 12 + nsl0 * 4) + 8;
-    uint64_t G = ctx->query_acc_bytes / per_q;
-    G = G < 1 ? 1 : (G > QG_MAX ? QG_MAX : G);
-    if (G > nq) G = nq ? nq : 1;
+    const TopkPlan plan = topk_plan(N, k, nq, ctx->query_acc_bytes);
+    const uint64_t G = plan.G;
     qi.group_queries = (uint32_t)G;
-    qi.acc_bytes = G * per_q;
-    const uint64_t cand_el = G * nsl0 * k;   /* entries of one candidate buffer */
+    qi.acc_bytes = G * plan.per_q;
     if (N && nq) {
-        ENSURE(ctx->q_acc, G * N * 8);
-        ENSURE(ctx->q_cnt, G * N * 4);
-        ENSURE(ctx->q_big, (size_t)N * 4 + 4);
-        ENSURE(ctx->q_cand0, cand_el * 12 + G * nsl0 * 4);
-        ENSURE(ctx->q_cand1, cand_el * 12 + G * nsl0 * 4);
-        ENSURE(ctx->q_misc, G * 8 + 16);
+        const int rc = topk_ensure(ctx, plan, N);
+        if (rc) return rc;
     }
     std::vector<uint64_t> h_s((size_t)G * k), h_nm(G);
     std::vector<uint32_t> h_id((size_t)G * k), h_n(G);
@@ -2694,10 +2781,9 @@ int tfidf_ctx_query(tfidf_ctx* ctx, const tfidf_queries* qs, uint32_t k, tfidf_h
         HIPCHK(hipMemcpyAsync(ctx->q_tab.p, tab.data(), tab.size() * 4, hipMemcpyHostToDevice, s));
         unsigned long long* d_nm = ctx->q_misc.as<unsigned long long>();
         HIPCHK(hipMemsetAsync(d_nm, 0, (size_t)G * 8, s));
-        QScoreArgs sa{};
+        DocScanArgs sa{};
         sa.out_off = ctx->out_off.as<uint64_t>();
         sa.out_term = ctx->out_term.as<uint32_t>();
-        sa.out_score = ctx->out_score.as<double>();
         sa.ndocs = N;
         sa.npairs = ctx->npairs;
         sa.gterm = ctx->q_tab.as<uint32_t>();
@@ -2712,81 +2798,31 @@ int tfidf_ctx_query(tfidf_ctx* ctx, const tfidf_queries* qs, uint32_t k, tfidf_h
         sa.big_list = ctx->q_big.as<uint32_t>();
         sa.big_count = (uint32_t*)(d_nm + G);
         HIPCHK(hipEventRecord(ctx->ev_q[0], s));
+        int lrc;
         if (bm) {
-            BScoreArgs ba{};
-            ba.out_off = sa.out_off;
-            ba.out_term = sa.out_term;
+            BScoreArgs ba{sa};
             ba.out_cnt = ctx->out_cnt.as<uint32_t>();
             ba.order = ctx->order;
             ba.doc_size = ctx->doc_size.as<uint32_t>();
-            ba.ndocs = N;
-            ba.npairs = sa.npairs;
-            ba.gterm = sa.gterm;
-            ba.ngterm = nG;
-            ba.post_off = sa.post_off;
-            ba.post_q = sa.post_q;
-            ba.post_w = (const double*)(sa.gterm + w_at);
-            ba.tab_words = sa.tab_words;
-            ba.nq = gn;
             ba.k1 = bm->k1;
             ba.b = bm->b;
             ba.avgdl = avgdl;
             ba.k1_plus_1 = bm->k1 + 1.0;
             ba.one_minus_b = 1.0 - bm->b;
-            ba.acc = sa.acc;
-            ba.cnt = sa.cnt;
-            ba.big_list = sa.big_list;
-            ba.big_count = sa.big_count;
-            if (launch_bm25_score(ba, ctx->ncu, s)) { HIPCHK(hipGetLastError()); return TFIDF_E_HIP; }
-        } else if (launch_query_score(sa, ctx->ncu, s)) {
-            HIPCHK(hipGetLastError());
-            return TFIDF_E_HIP;
+            lrc = launch_bm25_score(ba, ctx->ncu, s);
+        } else {
+            QScoreArgs ta{sa};
+            ta.out_score = ctx->out_score.as<double>();
+            lrc = launch_query_score(ta, ctx->ncu, s);
         }
+        if (lrc) { HIPCHK(hipGetLastError()); return TFIDF_E_HIP; }
         HIPCHK(hipEventRecord(ctx->ev_q[1], s));
-        /* top-k rounds: the accumulators' slices, then the slices' lists until one is left */
-        DevBuf* cand[2] = {&ctx->q_cand0, &ctx->q_cand1};
-        auto cs = [&](int c) { return cand[c]->as<uint64_t>(); };
-        auto cid = [&](int c) { return (uint32_t*)(cs(c) + cand_el); };
-        auto cn = [&](int c) { return cid(c) + cand_el; };
-        int cur = 0;
-        QTopkArgs ta{};
-        ta.acc = sa.acc;
-        ta.cnt = sa.cnt;
-        ta.order = ctx->order;
-        ta.doc_ids = ctx->dev_ids;
-        ta.n_in = N;
-        ta.kk = k;
-        ta.out_s = cs(0);
-        ta.out_id = cid(0);
-        ta.out_n = cn(0);
-        ta.out_slices = (uint32_t)nsl0;
-        ta.nmatch = d_nm;
-        if (launch_query_topk(ta, gn, s)) { HIPCHK(hipGetLastError()); return TFIDF_E_HIP; }
-        uint64_t nsl = nsl0;
-        while (nsl > 1) {
-            QTopkArgs tb{};
-            tb.in_s = cs(cur);
-            tb.in_id = cid(cur);
-            tb.in_n = cn(cur);
-            tb.in_slices = (uint32_t)nsl;
-            tb.n_in = nsl * k;
-            tb.kk = k;
-            nsl = (tb.n_in + QT_SLICE - 1) / QT_SLICE;
-            cur ^= 1;
-            tb.out_s = cs(cur);
-            tb.out_id = cid(cur);
-            tb.out_n = cn(cur);
-            tb.out_slices = (uint32_t)nsl;
-            tb.nmatch = d_nm;
-            if (launch_query_topk(tb, gn, s)) { HIPCHK(hipGetLastError()); return TFIDF_E_HIP; }
-        }
+        TopkCand res{};
+        int rc = topk_rounds(ctx, plan, sa.acc, sa.cnt, N, k, gn, d_nm, &res);
+        if (rc) return rc;
         HIPCHK(hipEventRecord(ctx->ev_q[2], s));
-        /* one slice per query is left: row q = entries [q * k, q * k + n[q]) */
-        HIPCHK(hipMemcpyAsync(h_s.data(), cs(cur), (size_t)gn * k * 8, hipMemcpyDeviceToHost, s));
-        HIPCHK(hipMemcpyAsync(h_id.data(), cid(cur), (size_t)gn * k * 4, hipMemcpyDeviceToHost, s));
-        HIPCHK(hipMemcpyAsync(h_n.data(), cn(cur), (size_t)gn * 4, hipMemcpyDeviceToHost, s));
-        HIPCHK(hipMemcpyAsync(h_nm.data(), d_nm, (size_t)gn * 8, hipMemcpyDeviceToHost, s));
-        HIPCHK(hipStreamSynchronize(s));
+        rc = topk_read_back(ctx, res, d_nm, gn, k, h_s.data(), h_id.data(), h_n.data(), h_nm.data());
+        if (rc) return rc;
         float ms = 0;
         (void)hipEventElapsedTime(&ms, ctx->ev_q[0], ctx->ev_q[1]);
         qi.ms_score += ms;
@@ -3756,13 +3792,10 @@ static int similar_groups(tfidf_ctx* ctx, const SimCall& c, uint32_t k, const ui
                           tfidf_similar_info& si) {
     hipStream_t s = ctx->stream;
     const uint32_t N = ctx->ndocs, V = ctx->V, R = c.R;
-    const uint64_t nsl0 = ((uint64_t)N + QT_SLICE - 1) / QT_SLICE;
-    const uint64_t per_q = (uint64_t)N * 12 + 2 * (nsl0 * k * 12 + nsl0 * 4) + 8;
-    uint64_t G = ctx->query_acc_bytes / per_q;
-    G = G < 1 ? 1 : (G > SG_MAX ? SG_MAX : G);
-    if (G > R) G = R ? R : 1;
+    const TopkPlan plan = topk_plan(N, k, R, ctx->query_acc_bytes);
+    const uint64_t G = plan.G;
     si.group_rows = (uint32_t)G;
-    si.acc_bytes = G * per_q;
+    si.acc_bytes = G * plan.per_q;
     if (!N || !V || !R) return TFIDF_OK;
     uint64_t maxP = 0;   /* the largest group's postings */
     for (uint32_t g0 = 0; g0 < R; g0 += (uint32_t)G) {
@@ -3772,13 +3805,8 @@ static int similar_groups(tfidf_ctx* ctx, const SimCall& c, uint32_t k, const ui
     }
     if (maxP > 0x7FFFFFFFull) return TFIDF_E_CAPACITY;
     if (!maxP) return TFIDF_OK;   /* every row is empty */
-    const uint64_t cand_el = G * nsl0 * k;   /* entries of one candidate buffer */
-    ENSURE(ctx->q_acc, G * N * 8);
-    ENSURE(ctx->q_cnt, G * N * 4);
-    ENSURE(ctx->q_big, (size_t)N * 4 + 4);
-    ENSURE(ctx->q_cand0, cand_el * 12 + G * nsl0 * 4);
-    ENSURE(ctx->q_cand1, cand_el * 12 + G * nsl0 * 4);
-    ENSURE(ctx->q_misc, G * 8 + 16);
+    const int erc = topk_ensure(ctx, plan, N);
+    if (erc) return erc;
     ENSURE(ctx->sm_mask, ((size_t)V + 2) * 8);
     ENSURE(ctx->sm_cnt, ((size_t)V + 2) * 4);
     ENSURE(ctx->sm_off, ((size_t)V + 2) * 4);
@@ -3840,56 +3868,20 @@ static int similar_groups(tfidf_ctx* ctx, const SimCall& c, uint32_t k, const ui
         sa.big_count = (uint32_t*)(d_nm + G);
         if (launch_sim_score(sa, ctx->ncu, s)) { HIPCHK(hipGetLastError()); return TFIDF_E_HIP; }
         HIPCHK(hipEventRecord(ctx->ev_s[2], s));
-        /* ---- top-k rounds (tfidf_query's): the accumulators' slices, then the slices' lists ---- */
-        DevBuf* cand[2] = {&ctx->q_cand0, &ctx->q_cand1};
-        auto cs = [&](int x) { return cand[x]->as<uint64_t>(); };
-        auto cid = [&](int x) { return (uint32_t*)(cs(x) + cand_el); };
-        auto cn = [&](int x) { return cid(x) + cand_el; };
-        int cur = 0;
-        QTopkArgs t0{};
-        t0.acc = sa.acc;
-        t0.cnt = sa.cnt;
-        t0.order = ctx->order;
-        t0.doc_ids = ctx->dev_ids;
-        t0.n_in = N;
-        t0.kk = k;
-        t0.out_s = cs(0);
-        t0.out_id = cid(0);
-        t0.out_n = cn(0);
-        t0.out_slices = (uint32_t)nsl0;
-        t0.nmatch = d_nm;
-        if (launch_query_topk(t0, gn, s)) { HIPCHK(hipGetLastError()); return TFIDF_E_HIP; }
-        uint64_t nsl = nsl0;
-        while (nsl > 1) {
-            QTopkArgs tb{};
-            tb.in_s = cs(cur);
-            tb.in_id = cid(cur);
-            tb.in_n = cn(cur);
-            tb.in_slices = (uint32_t)nsl;
-            tb.n_in = nsl * k;
-            tb.kk = k;
-            nsl = (tb.n_in + QT_SLICE - 1) / QT_SLICE;
-            cur ^= 1;
-            tb.out_s = cs(cur);
-            tb.out_id = cid(cur);
-            tb.out_n = cn(cur);
-            tb.out_slices = (uint32_t)nsl;
-            tb.nmatch = d_nm;
-            if (launch_query_topk(tb, gn, s)) { HIPCHK(hipGetLastError()); return TFIDF_E_HIP; }
-        }
+        /* ---- top-k rounds (tfidf_query's) ---- */
+        TopkCand res{};
+        int rc = topk_rounds(ctx, plan, sa.acc, sa.cnt, N, k, gn, d_nm, &res);
+        if (rc) return rc;
         /* ---- the neighbours' positions and shared-term counts ---- */
-        TLookupArgs la{cid(cur), gn * k, ctx->order, ctx->dev_ids, N, res_pos};
+        TLookupArgs la{res.id, gn * k, ctx->order, ctx->dev_ids, N, res_pos};
         if (launch_terms_lookup(la, s)) { HIPCHK(hipGetLastError()); return TFIDF_E_HIP; }
-        if (launch_sim_shared(sa.cnt, res_pos, cn(cur), gn, k, N, res_sh, s)) { HIPCHK(hipGetLastError()); return TFIDF_E_HIP; }
+        if (launch_sim_shared(sa.cnt, res_pos, res.n, gn, k, N, res_sh, s)) { HIPCHK(hipGetLastError()); return TFIDF_E_HIP; }
         HIPCHK(hipEventRecord(ctx->ev_s[3], s));
         uint32_t nbig = 0;
-        HIPCHK(hipMemcpyAsync(h_s.data(), cs(cur), (size_t)gn * k * 8, hipMemcpyDeviceToHost, s));
-        HIPCHK(hipMemcpyAsync(h_id.data(), cid(cur), (size_t)gn * k * 4, hipMemcpyDeviceToHost, s));
         HIPCHK(hipMemcpyAsync(h_sh.data(), res_sh, (size_t)gn * k * 4, hipMemcpyDeviceToHost, s));
-        HIPCHK(hipMemcpyAsync(h_n.data(), cn(cur), (size_t)gn * 4, hipMemcpyDeviceToHost, s));
-        HIPCHK(hipMemcpyAsync(h_nm.data(), d_nm, (size_t)gn * 8, hipMemcpyDeviceToHost, s));
         HIPCHK(hipMemcpyAsync(&nbig, sa.big_count, 4, hipMemcpyDeviceToHost, s));
-        HIPCHK(hipStreamSynchronize(s));
+        rc = topk_read_back(ctx, res, d_nm, gn, k, h_s.data(), h_id.data(), h_n.data(), h_nm.data());
+        if (rc) return rc;
         float ms = 0;
         (void)hipEventElapsedTime(&ms, ctx->ev_s[0], ctx->ev_s[1]);
         si.ms_table += ms;

@@ -375,26 +375,32 @@ struct QLookupArgs {
     uint32_t* rank_out;
 };
 int launch_query_lookup(const QLookupArgs& a, hipStream_t s);
-/* one group of nq <= QG_MAX queries: gterm = the group's sorted distinct term ranks, term i's
- * postings (query in the group, weight) at [post_off[i], post_off[i + 1]); acc / cnt are
- * written for every (query, output position): [nq][ndocs] */
-struct QScoreArgs {
+/* One scan of the resident pairs for a group of nq <= QG_MAX queries (docscan.h), the part every
+ * ranking function shares: gterm = the group's sorted distinct term ranks, term i's postings
+ * (query in the group, weight) at [post_off[i], post_off[i + 1]); acc / cnt are written for
+ * every (query, output position): [nq][ndocs].  The table is one block from gterm on: gterm,
+ * post_off, post_q as u32 words, then the weights in the ranking function's type (u32, or
+ * binary64 at an even word). */
+struct DocScanArgs {
     const uint64_t* out_off;
     const uint32_t* out_term;
-    const double* out_score;
     uint32_t ndocs;
     uint64_t npairs;
     const uint32_t* gterm;
     uint32_t ngterm;
     const uint32_t* post_off;
     const uint32_t* post_q;
-    const uint32_t* post_w;
-    uint32_t tab_words;          /* words of the table when it is one block from gterm on (0: it is not) */
+    const uint32_t* post_w;      /* the weights' first word */
+    uint32_t tab_words;          /* u32 words of the whole block (0: do not stage it in LDS) */
     uint32_t nq;
     double* acc;
     uint32_t* cnt;
     uint32_t* big_list;          /* [ndocs] scratch: output positions of documents over QS_BIG pairs */
     uint32_t* big_count;
+};
+/* TF-IDF: u32 weights (the term's count in the query), a match reads the pair's score */
+struct QScoreArgs : DocScanArgs {
+    const double* out_score;
 };
 int launch_query_score(const QScoreArgs& a, uint32_t ncu, hipStream_t s);
 /* one top-k round: per (query, slice of QT_SLICE inputs) the best kk in order.  First round
@@ -423,31 +429,15 @@ int launch_query_topk(const QTopkArgs& a, uint32_t nq, hipStream_t s);
 /* ---- BM25 scoring over the resident result (bm25.hip, tfidf_query_bm25) ---- */
 /* out[i] = df[rank[i]] (0 where rank[i] is QUERY_NO_TERM): the found terms' global df */
 int launch_bm25_df(const uint32_t* rank, uint32_t n, const uint32_t* df, uint32_t V, uint32_t* out, hipStream_t s);
-/* one group of nq <= QG_MAX queries, as QScoreArgs, with binary64 weights W(q,t): the table is
- * one block from gterm on (gterm, post_off, post_q as u32 words, then post_w at an even word).
- * A match reads out_cnt; the document's normaliser comes from doc_size through order. */
-struct BScoreArgs {
-    const uint64_t* out_off;
-    const uint32_t* out_term;
+/* BM25: binary64 weights W(q,t).  A match reads the pair's count (out_cnt); the document's
+ * normaliser comes from doc_size through order. */
+struct BScoreArgs : DocScanArgs {
     const uint32_t* out_cnt;
     const uint32_t* order;       /* output position -> document index */
     const uint32_t* doc_size;    /* by document index */
-    uint32_t ndocs;
-    uint64_t npairs;
-    const uint32_t* gterm;
-    uint32_t ngterm;
-    const uint32_t* post_off;
-    const uint32_t* post_q;
-    const double* post_w;
-    uint32_t tab_words;          /* u32 words of the whole block (0: do not stage it) */
-    uint32_t nq;
     double k1, b, avgdl;         /* avgdl > 0 */
     double k1_plus_1;            /* fl(k1 + 1.0) */
     double one_minus_b;          /* fl(1.0 - b) */
-    double* acc;
-    uint32_t* cnt;
-    uint32_t* big_list;          /* [ndocs] scratch: output positions of documents over QS_BIG pairs */
-    uint32_t* big_count;
 };
 int launch_bm25_score(const BScoreArgs& a, uint32_t ncu, hipStream_t s);
 

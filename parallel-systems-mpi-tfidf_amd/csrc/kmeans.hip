@@ -33,27 +33,18 @@
  * No product may be fused into an add in this file (similar.hip). */
 #include "kernels.h"
 #include "dev_common.h"
+#include "launch_util.h"
 
 #pragma clang fp contract(off)
 
 namespace {
 
 constexpr int NT = 256;
-inline unsigned grid_for(uint64_t n, int nt = NT) { return n ? (unsigned)((n + nt - 1) / nt) : 1u; }
-int ok() { return hipGetLastError() == hipSuccess ? 0 : -1; }
-
-__device__ __forceinline__ void doc_range(const KmArgs& a, uint32_t j, uint64_t& b, uint64_t& e) {
-    b = a.out_off[j];
-    e = a.out_off[j + 1];
-    if (e > a.npairs) e = a.npairs;
-    if (b > e) b = e;
-}
 
 __global__ void k_km_docs(const uint32_t* order, const uint32_t* doc_ids, uint32_t ndocs, uint32_t* id) {
     const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
     if (j >= ndocs) return;
-    const uint32_t d = order[j];
-    id[j] = doc_ids ? doc_ids[d] : d + 1u;
+    id[j] = doc_id_at(order, doc_ids, j);
 }
 
 /* -------------------------------------------------------------------- seed -- */
@@ -66,7 +57,7 @@ __global__ __launch_bounds__(NT) void k_km_seed(const KmArgs a) {
     const uint32_t j = a.seedpos[c];
     if (j >= a.ndocs) return;
     uint64_t b, e;
-    doc_range(a, j, b, e);
+    pair_range(a.out_off, a.npairs, j, b, e);
     const double nrm = a.norm[j];
     if (!(nrm > 0.0)) return;
     for (uint64_t p = b + threadIdx.x; p < e; p += NT) {
@@ -88,7 +79,7 @@ __global__ __launch_bounds__(NT) void k_km_assign(const KmArgs a) {
     const uint32_t nwaves = gridDim.x * (NT / 64);
     for (uint32_t j = blockIdx.x * (NT / 64) + wv; j < a.ndocs; j += nwaves) {
         uint64_t b, e;
-        doc_range(a, j, b, e);
+        pair_range(a.out_off, a.npairs, j, b, e);
         const double nrm = a.norm[j];
         uint32_t lab = KM_NO_CLUSTER;
         uint64_t best = 0ull;
@@ -202,7 +193,7 @@ __global__ __launch_bounds__(NT) void k_km_accum(const KmArgs a) {
         const uint32_t j = a.members[m0 + m];
         if (j < a.ndocs) {
             uint64_t b, e;
-            doc_range(a, j, b, e);
+            pair_range(a.out_off, a.npairs, j, b, e);
             const double nrm = a.norm[j];
             if (G > 1u && e - b > 4u * NT) {   /* a long document: start at the range's first pair */
                 uint64_t lo = b, hi = e;

@@ -26,24 +26,23 @@
  *            operations, whatever the grid, and no accumulator is shared between lanes (no
  *            LDS, no atomics).  Documents over QS_BIG pairs are handed to a second launch, one
  *            workgroup each, which compacts every tile of 256 pairs in pair order into LDS
- *            (query.hip's scheme) for wave 0 to add.  The owner turns the sums into
+ *            (docscan.h's scheme) for wave 0 to add.  The owner turns the sums into
  *            similarities as it writes them: dot / (norm * norm), +0.0 for a zero
  *            denominator, and the row's own position gets count 0.
  *   top-k    k_query_topk over the dense (row, output position) arrays, then the neighbours'
  *            positions (k_terms_lookup) and their shared-term counts.
  *
  * No product may be fused into an add in this file (hipcc contracts a * b + c by default, and
- * through __dmul_rn / __dadd_rn as well: query.hip). */
+ * through __dmul_rn / __dadd_rn as well: docscan.h). */
 #include "kernels.h"
 #include "dev_common.h"
+#include "launch_util.h"
 
 #pragma clang fp contract(off)
 
 namespace {
 
 constexpr int NT = 256;
-inline unsigned grid_for(uint64_t n, int nt = NT) { return n ? (unsigned)((n + nt - 1) / nt) : 1u; }
-int ok() { return hipGetLastError() == hipSuccess ? 0 : -1; }
 
 /* ------------------------------------------------------------------- norms -- */
 
@@ -53,9 +52,8 @@ __global__ __launch_bounds__(NT) void k_sim_norms(const uint64_t* out_off, const
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t j = blockIdx.x * (NT / 64) + (threadIdx.x >> 6);
     if (j >= ndocs) return;   /* wave-uniform */
-    uint64_t b = out_off[j], e = out_off[j + 1];
-    if (e > npairs) e = npairs;
-    if (b > e) b = e;
+    uint64_t b, e;
+    pair_range(out_off, npairs, j, b, e);
     double sum = 0.0;
     for (uint64_t p = b; p < e; p += 64u) {
         const uint64_t pp = p + lane;
@@ -80,14 +78,10 @@ __global__ void k_sim_rows(const SimRowArgs a) {
     double n = 0.0, q = 0.0;
     uint32_t id = 0;
     if (j < a.ndocs) {
-        b = a.out_off[j];
-        e = a.out_off[j + 1];
-        if (e > a.npairs) e = a.npairs;
-        if (b > e) b = e;
+        pair_range(a.out_off, a.npairs, j, b, e);
         n = a.norm[j];
         q = a.sq[j];
-        const uint32_t d = a.order[j];
-        id = a.doc_ids ? a.doc_ids[d] : d + 1u;
+        id = doc_id_at(a.order, a.doc_ids, j);
     }
     a.rb[i] = b;
     a.re[i] = e;
@@ -147,13 +141,6 @@ __device__ __forceinline__ double weight_of(const SimScoreArgs& a, uint64_t M, u
     return x < a.post_cap ? gload(a.post_w + x) : 0.0;
 }
 
-__device__ __forceinline__ void doc_range(const SimScoreArgs& a, uint32_t j, uint64_t& b, uint64_t& e) {
-    b = a.out_off[j];
-    e = a.out_off[j + 1];
-    if (e > a.npairs) e = a.npairs;
-    if (b > e) b = e;
-}
-
 /* lane r's sum -> the similarity of row r and the document at position j */
 __device__ __forceinline__ void write_doc(const SimScoreArgs& a, uint32_t j, double dot, uint32_t c, uint32_t lane) {
 #pragma clang fp contract(off)
@@ -174,12 +161,9 @@ __global__ __launch_bounds__(NT) void k_sim_score(const SimScoreArgs a) {
     const uint32_t nwaves = gridDim.x * (NT / 64);
     for (uint32_t j = blockIdx.x * (NT / 64) + wv; j < a.ndocs; j += nwaves) {
         uint64_t b, e;
-        doc_range(a, j, b, e);
+        pair_range(a.out_off, a.npairs, j, b, e);
         if (e - b > QS_BIG) {   /* the second launch's: one workgroup per such document */
-            if (lane == 0) {
-                const uint32_t at = atomicAdd(a.big_count, 1u);
-                if (at < a.ndocs) a.big_list[at] = j;
-            }
+            if (lane == 0) hand_to_big(a.big_list, a.big_count, a.ndocs, j);
             continue;
         }
         double acc = 0.0;
@@ -248,7 +232,7 @@ __global__ __launch_bounds__(NT) void k_sim_score_big(const SimScoreArgs a) {
         const uint32_t j = a.big_list[k];
         if (j >= a.ndocs) continue;
         uint64_t b, e;
-        doc_range(a, j, b, e);
+        pair_range(a.out_off, a.npairs, j, b, e);
         double acc = 0.0;      /* wave 0's lanes: row r's sum */
         uint32_t cnt = 0u;
         for (uint64_t p = b; p < e; p += NT) {

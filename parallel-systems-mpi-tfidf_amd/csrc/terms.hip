@@ -23,12 +23,11 @@
  */
 #include "kernels.h"
 #include "dev_common.h"
+#include "launch_util.h"
 
 namespace {
 
 constexpr int NT = 256;
-inline unsigned grid_for(uint64_t n, int nt = NT) { return n ? (unsigned)((n + nt - 1) / nt) : 1u; }
-int ok() { return hipGetLastError() == hipSuccess ? 0 : -1; }
 
 /* ------------------------------------------------------------------ lookup -- */
 
@@ -42,11 +41,6 @@ __device__ __forceinline__ uint64_t doc_name_key(uint32_t id) {
     return key;
 }
 
-__device__ __forceinline__ uint32_t id_at(const uint32_t* order, const uint32_t* doc_ids, uint32_t j) {
-    const uint32_t d = order[j];
-    return doc_ids ? doc_ids[d] : d + 1u;
-}
-
 __global__ void k_terms_lookup(const TLookupArgs a) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= a.nids) return;
@@ -55,10 +49,10 @@ __global__ void k_terms_lookup(const TLookupArgs a) {
     uint32_t lo = 0, hi = a.ndocs;
     while (lo < hi) {
         const uint32_t mid = lo + ((hi - lo) >> 1);
-        if (doc_name_key(id_at(a.order, a.doc_ids, mid)) < key) lo = mid + 1;
+        if (doc_name_key(doc_id_at(a.order, a.doc_ids, mid)) < key) lo = mid + 1;
         else hi = mid;
     }
-    a.pos[i] = (lo < a.ndocs && id_at(a.order, a.doc_ids, lo) == id) ? lo : TERMS_NO_POS;
+    a.pos[i] = (lo < a.ndocs && doc_id_at(a.order, a.doc_ids, lo) == id) ? lo : TERMS_NO_POS;
 }
 
 /* ------------------------------------------------------------------ select -- */
@@ -120,19 +114,8 @@ __device__ __forceinline__ void row_doc(const TSelArgs& a, uint32_t row, uint64_
     b = e = 0;
     id = 0;
     if (j < a.ndocs) {
-        b = a.out_off[j];
-        e = a.out_off[j + 1];
-        if (e > a.npairs) e = a.npairs;
-        if (b > e) b = e;
-        id = id_at(a.order, a.doc_ids, j);
-    }
-}
-
-/* the big documents' list, appended by the first launch */
-__device__ __forceinline__ void hand_to_big(const TSelArgs& a, uint32_t row) {
-    if (threadIdx.x == 0) {
-        const uint32_t at = atomicAdd(a.big_count, 1u);
-        if (at < a.nrows) a.big_list[at] = row;
+        pair_range(a.out_off, a.npairs, j, b, e);
+        id = doc_id_at(a.order, a.doc_ids, j);
     }
 }
 
@@ -175,7 +158,10 @@ __global__ __launch_bounds__(64) void k_terms_select_list(const TSelArgs a) {
         uint32_t id;
         row_doc(a, row, b, e, id);
         const uint64_t np = e - b;
-        if (np > QS_BIG) { hand_to_big(a, row); continue; }
+        if (np > QS_BIG) {   /* the second launch's */
+            if (threadIdx.x == 0) hand_to_big(a.big_list, a.big_count, a.nrows, row);
+            continue;
+        }
         uint64_t ms = 0ull;                    /* this lane's entry: a pad until the first round */
         uint32_t mi = 0xFFFFFFC0u + lane;
         uint64_t ts = 0ull;                    /* entry k - 1 */
@@ -259,7 +245,10 @@ __global__ __launch_bounds__(TNT) void k_terms_select(const TSelArgs a) {
         uint32_t id;
         row_doc(a, row, b, e, id);
         const uint64_t np = e - b;
-        if (!BIG && np > QS_BIG) { hand_to_big(a, row); continue; }   /* the second launch's */
+        if (!BIG && np > QS_BIG) {   /* the second launch's */
+            if (threadIdx.x == 0) hand_to_big(a.big_list, a.big_count, a.nrows, row);
+            continue;
+        }
         uint32_t n = 0;          /* candidates in the buffer (uniform) */
         bool have = false;       /* the buffer has been cut: (ts, ti) is the k-th best key so far */
         uint64_t ts = 0;
