@@ -831,6 +831,103 @@ typedef struct tfidf_model_info {
 } tfidf_model_info;
 int tfidf_last_model_info(const tfidf_ctx* ctx, tfidf_model_info* info);
 
+/* ---------------------------------------------------------------- analyzer -- */
+
+/* A byte-to-byte analyzer in front of the counter: case folding, punctuation stripping, a
+ * minimum token length and a stop-word list.  The reference tokenises with fscanf("%s") and
+ * compares with strcmp (TFIDF.c:141-152): "The", "the", "the," and "(the" are four terms.  The
+ * analyzer rewrites a corpus (or a batch, or the lines of a query batch: bytes plus offsets)
+ * into one of the same length with the same offsets, so tfidf_run and everything after it stay
+ * as they are.  Everything is byte-exact.
+ *
+ * For every document window [off[i], off[i + 1]):
+ *   1. byte map, each byte on its own
+ *        TFIDF_AN_LOWER   0x41..0x5A become b + 0x20
+ *        TFIDF_AN_PUNCT   every ASCII byte that is not a letter, a digit or one of the six
+ *                         separators {0x20,0x09..0x0D} becomes 0x20: 0x00..0x08, 0x0E..0x1F,
+ *                         0x21..0x2F, 0x3A..0x40, 0x5B..0x60, 0x7B..0x7F (60 values, NUL among
+ *                         them: with this flag a token equals its term)
+ *        everything else is unchanged: bytes >= 0x80 (UTF-8 passes through) and the separators
+ *        themselves ('\n' stays '\n')
+ *   2. token filter, on the mapped bytes: tokens are the maximal runs of non-separator bytes
+ *      inside the document (a document boundary ends a token, as for tfidf_corpus).  A token is
+ *      blanked (every one of its bytes becomes 0x20) when its length in bytes is < min_len, or
+ *      when its bytes equal a stop word.  The comparison takes the whole token, not the term cut
+ *      at a NUL: stop words hold no NUL, so without TFIDF_AN_PUNCT a token that contains a NUL
+ *      never matches.  Stop words are compared verbatim with the mapped tokens: the caller
+ *      supplies them already folded.
+ * Bytes of [0, nbytes) outside [off[0], off[n]) are copied unchanged.
+ * Consequences: the analyzer is idempotent; with flags = 0, min_len <= 1 and no stop words the
+ * output equals the input; a token longer than TFIDF_AN_MAX_WORD bytes is never blanked (it
+ * matches no stop word and is not shorter than min_len).
+ * The analyzer is not part of a model (tfidf_model, the model file): whoever scores batches
+ * against a saved model passes the same analyzer again. */
+#define TFIDF_AN_LOWER 1u
+#define TFIDF_AN_PUNCT 2u
+#define TFIDF_AN_MAX_WORD 64u            /* longest stop word, largest min_len */
+#define TFIDF_AN_MAX_STOP 4096u          /* stop words */
+#define TFIDF_AN_MAX_STOP_BYTES 32768u   /* all stop words together */
+typedef struct tfidf_analyzer {
+    uint64_t size;               /* sizeof(tfidf_analyzer), set by the caller */
+    uint32_t flags;              /* TFIDF_AN_* */
+    uint32_t min_len;
+    const uint8_t*  stop_bytes;  /* stop word i = stop_bytes[stop_off[i], stop_off[i + 1]) */
+    const uint64_t* stop_off;    /* nstop + 1 */
+    uint32_t nstop, reserved;
+} tfidf_analyzer;
+/* Host only.  TFIDF_E_INVAL for: NULL; size < sizeof(tfidf_analyzer); unknown flag bits;
+ * min_len > TFIDF_AN_MAX_WORD; nstop > TFIDF_AN_MAX_STOP; nstop > 0 with a NULL stop_bytes or
+ * stop_off; a non-monotone stop_off; more than TFIDF_AN_MAX_STOP_BYTES bytes of stop words; a
+ * stop word that is empty, longer than TFIDF_AN_MAX_WORD, or holds a NUL or a separator.
+ * Duplicates in the list are allowed. */
+int tfidf_analyzer_check(const tfidf_analyzer* an);
+/* Host only, plain C: the definition above.  Document i is bytes[off[i], off[i + 1]); out
+ * receives nbytes bytes and may equal bytes (in place).  TFIDF_E_INVAL for an analyzer that
+ * fails the check, a NULL bytes or out with nbytes > 0, a NULL off with n > 0, a non-monotone
+ * off or off[n] > nbytes.  Stop words are looked up in the same open-addressed table the device
+ * kernel probes (csrc/analyze_tab.h). */
+int tfidf_analyze_host(const tfidf_analyzer* an, const uint8_t* bytes, uint64_t nbytes,
+                       const uint64_t* off, uint32_t n, uint8_t* out);
+
+/* The same on the device (analyze.hip), where tfidf_ingest_dir_device leaves the bytes.
+ * in: a host corpus (staged in a context buffer first) or a TFIDF_CORPUS_DEVICE corpus at any
+ * alignment of bytes, windows allowed: the context's own ingest or synth buffer, or a caller's.
+ * *out: a device corpus in buffers owned by the context (slot `slot`), valid until the next
+ * tfidf_analyze with the same slot on this context or tfidf_close; out->bytes is 16-byte aligned
+ * whatever the input's alignment (a run takes its default kernel), doc_off and doc_ids are the
+ * context's own device copies, nbytes / ndocs / ndocs_total are the input's.
+ * Two slots, because a run's corpus must stay valid while batches are analyzed (emission,
+ * keywords, query and transform read long terms from it): the corpus goes to slot 0, batches
+ * to slot 1.
+ * TFIDF_E_INVAL: a NULL argument, slot > 1, an analyzer that fails the check, bad offsets (the
+ * rules of tfidf_transform), in->bytes inside the same slot's buffer.  ndocs == 0, nbytes == 0
+ * and empty documents are valid.  The kernels read no byte outside in->bytes[0, nbytes) and
+ * write none outside the slot's [0, nbytes).  The result does not depend on grid, tile or list
+ * order.  All buffers belong to the context: a repeated identical call allocates nothing
+ * (tfidf_alloc_stats).  The call neither needs nor disturbs a run's result and works before any
+ * tfidf_run.  There is no group entry point: analyze each shard on tfidf_group_ctx(g, r) before
+ * tfidf_group_run. */
+#define TFIDF_AN_SLOT_CORPUS 0u
+#define TFIDF_AN_SLOT_BATCH  1u
+int tfidf_analyze(tfidf_ctx* ctx, const tfidf_analyzer* an, const tfidf_corpus* in,
+                  uint32_t slot, tfidf_corpus* out);
+/* Counters of the last tfidf_analyze (the caller sets `size` = sizeof, as tfidf_query_info). */
+typedef struct tfidf_analyze_info {
+    uint64_t size;
+    uint64_t nbytes;
+    uint32_t ndocs;
+    uint32_t nstop;           /* stop words of the list, duplicates included */
+    uint32_t table_slots;     /* slots of the stop-word table (0: no list) */
+    uint32_t lds_bytes;       /* LDS of a workgroup: table, word bytes, tile and halos (0: the
+                                 pure byte map, which uses none) */
+    uint32_t tile_bytes;      /* bytes a workgroup owns per step */
+    uint32_t reserved;
+    uint64_t blanked_tokens;  /* tokens blanked (an integer atomic counter, one add per workgroup) */
+    double   ms_kernel;       /* device time of the kernels (HIP events) */
+    double   ms_total;        /* host wall time of the whole call */
+} tfidf_analyze_info;
+int tfidf_last_analyze_info(const tfidf_ctx* ctx, tfidf_analyze_info* info);
+
 /* ---------------------------------------------------------------- ingest ---- */
 
 /* Reference input contract (TFIDF.c:98-110,130-147): N = number of entries of `dir`

@@ -1,0 +1,297 @@
+/*
+ * analyze.hip — the analyzer on the device (include/tfidf.h, section "analyzer"): case folding,
+ * punctuation stripping, a minimum token length and a stop-word list, bytes to bytes of the same
+ * length, in front of tfidf_run.  The reference has no such stage: it counts what fscanf("%s")
+ * returns (TFIDF.c:141-152).
+ *
+ *   map      the pure byte map (no stop words, min_len <= 1): one 16-byte group per lane, SWAR
+ *            range compares on 32-bit words (the form of dev_common.h's ws_mask4), no LDS.
+ *   filter   persistent workgroups of 256 lanes, one tile of AN_TILE bytes per step.  The
+ *            stop-word table (analyze_tab.h) is copied to LDS once per workgroup.  Per tile:
+ *              1. every lane loads its 16 bytes (lanes 0..9 also one group of the AN_HALO bytes
+ *                 on either side), maps them and stores them to LDS with two 16-bit masks:
+ *                 token bytes, and token bytes that continue a token (no document starts there)
+ *              2. a lane that owns a token start (a token byte whose predecessor is none, or a
+ *                 document's first byte: transform.hip's scheme) gets the token's length from
+ *                 the continuation bits (64 bits, one count-trailing-ones), and for a token of
+ *                 at most 64 bytes hashes it four bytes at a time from the aligned LDS words,
+ *                 probes the table and marks the token's bytes in a blank bitmap in LDS
+ *                 (atomicOr: lanes of one workgroup share the bitmap's words; the held bytes
+ *                 themselves are not written in this phase)
+ *              3. every lane blanks the marked bytes of its 16 and stores them
+ *            A workgroup decides the fate of its own tile's bytes only: a token that began
+ *            before the left halo is longer than 64 bytes when it reaches the tile and is never
+ *            blanked, and a token that starts in the tile ends inside the right halo or is too
+ *            long as well.  So no two workgroups write the same byte and the pass is out of
+ *            place.  Tokens blanked are counted where they start: one integer atomic add per
+ *            workgroup.
+ * The input may have any alignment: groups are cut at multiples of 16 of the OUTPUT, an
+ * unaligned input is read as two aligned 16-byte loads and a byte shift, and byte by byte where
+ * that would leave in[0, nbytes).
+ */
+#include "kernels.h"
+#include "dev_common.h"
+#include "analyze_tab.h"
+
+namespace {
+
+constexpr int NT = 256;
+constexpr uint32_t HG = AN_HALO / 16u;         /* halo groups on each side */
+constexpr uint32_t NG = NT + 2u * HG;          /* groups held in LDS */
+constexpr uint32_t AN_FLAG_LOWER = 1u, AN_FLAG_PUNCT = 2u;   /* TFIDF_AN_* of include/tfidf.h */
+constexpr uint32_t AN_MAX_WORD = 64u;
+static_assert(AN_TILE == NT * 16u, "one 16-byte group per lane");
+static_assert(AN_HALO % 16u == 0 && AN_HALO > AN_MAX_WORD + 1u, "the halo argument");
+constexpr uint32_t BM_WORDS = (NG * 16u / 32u + 4u) & ~3u;   /* a bit per held byte, whole 16-byte rows */
+constexpr uint32_t AN_STATIC_LDS = NG * 16u + 3u * BM_WORDS * 4u + 16u;
+
+int ok() { return hipGetLastError() == hipSuccess ? 0 : -1; }
+
+/* bit 7 of every byte of lo7 (bytes <= 0x7F) that lies in [a, b], 1 <= a <= b <= 0x7F: both
+ * per-byte sums stay inside their byte */
+__device__ __forceinline__ uint32_t in_range(uint32_t lo7, uint32_t a, uint32_t b) {
+    return (lo7 + (0x80u - a) * 0x01010101u) & ~(lo7 + (0x7Fu - b) * 0x01010101u) & 0x80808080u;
+}
+
+/* the byte map on four bytes */
+__device__ __forceinline__ uint32_t map_word(uint32_t x, uint32_t flags) {
+    const uint32_t ascii = ~x & 0x80808080u, lo7 = x & 0x7F7F7F7Fu;
+    const uint32_t upper = in_range(lo7, 0x41u, 0x5Au) & ascii;
+    if (flags & AN_FLAG_PUNCT) {
+        const uint32_t keep = upper | in_range(lo7, 0x61u, 0x7Au) | in_range(lo7, 0x30u, 0x39u) |
+                              in_range(lo7, 0x09u, 0x0Du) | in_range(lo7, 0x20u, 0x20u);
+        const uint32_t m = ((ascii & ~keep) >> 7) * 0xFFu;   /* 0xFF in every punctuation byte */
+        x = (x & ~m) | (0x20202020u & m);
+    }
+    if (flags & AN_FLAG_LOWER) x |= upper >> 2;              /* + 0x20: bit 5 of 0x41..0x5A is clear */
+    return x;
+}
+
+/* 0xFF in byte j for every set bit j of the low four */
+__device__ __forceinline__ uint32_t expand4(uint32_t b) { return (((b & 0xFu) * 0x00204081u) & 0x01010101u) * 0xFFu; }
+
+/* the byte map on the bytes of a group whose bit in win is set */
+__device__ __forceinline__ uint4 map_group(uint4 v, uint32_t win, uint32_t flags) {
+    if (win == 0u || flags == 0u) return v;
+    uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const uint32_t m = map_word(w[k], flags);
+        if (win == 0xFFFFu) w[k] = m;
+        else {
+            const uint32_t bm = expand4(win >> (4 * k));
+            w[k] = (w[k] & ~bm) | (m & bm);
+        }
+    }
+    return make_uint4(w[0], w[1], w[2], w[3]);
+}
+
+/* bit j = byte p + j lies in [lo, hi) */
+__device__ __forceinline__ uint32_t range16(long long p, uint64_t lo, uint64_t hi) {
+    long long b = (long long)lo - p, e = (long long)hi - p;
+    b = b < 0 ? 0 : (b > 16 ? 16 : b);
+    e = e < 0 ? 0 : (e > 16 ? 16 : e);
+    return e > b ? ((1u << e) - 1u) & ~((1u << b) - 1u) : 0u;
+}
+
+/* in[p, p + 16) with 0x20 for the bytes outside in[0, nbytes); phase = the input base's low four
+ * address bits (p is a multiple of 16, so it is the group's phase too) */
+__device__ __forceinline__ uint4 load16(const AnArgs& a, long long p, uint32_t phase) {
+    if (p >= 0 && (uint64_t)p + 16u <= a.nbytes) {
+        if (phase == 0u) return gload((const uint4*)(a.in + p));
+        if ((uint64_t)p >= phase && (uint64_t)p - phase + 32u <= a.nbytes) {
+            const uint4* q = (const uint4*)(a.in + p - phase);
+            const uint4 u = gload(q), v = gload(q + 1);
+            const uint32_t w[8] = {u.x, u.y, u.z, u.w, v.x, v.y, v.z, v.w};
+            const uint32_t k = phase >> 2, sh = phase & 3u;
+            uint32_t r[4] = {0, 0, 0, 0};
+#pragma unroll
+            for (int kk = 0; kk < 4; ++kk) {
+                if (k == (uint32_t)kk) {
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) r[j] = __builtin_amdgcn_alignbyte(w[kk + j + 1], w[kk + j], sh);
+                }
+            }
+            return make_uint4(r[0], r[1], r[2], r[3]);
+        }
+    }
+    uint64_t lo = 0x2020202020202020ull, hi = lo;   /* the edges: a rolled loop, few registers */
+#pragma unroll 1
+    for (int j = 0; j < 16; ++j) {
+        const long long q = p + j;
+        if (q >= 0 && (uint64_t)q < a.nbytes) {
+            const uint64_t c = (uint64_t)(gload(a.in + q) ^ 0x20u) << (8 * (j & 7));
+            if (j < 8) lo ^= c;
+            else hi ^= c;
+        }
+    }
+    return make_uint4((uint32_t)lo, (uint32_t)(lo >> 32), (uint32_t)hi, (uint32_t)(hi >> 32));
+}
+
+/* out[p, p + 16), p a multiple of 16 below nbytes: whole, or byte by byte up to nbytes */
+__device__ __forceinline__ void store16(const AnArgs& a, uint64_t p, uint4 v) {
+    if (p + 16u <= a.nbytes) {
+        g_u32x4 r;
+        r.x = v.x; r.y = v.y; r.z = v.z; r.w = v.w;
+        *(GLOBAL_AS g_u32x4*)(a.out + p) = r;
+        return;
+    }
+    const uint64_t lo = v.x | ((uint64_t)v.y << 32), hi = v.z | ((uint64_t)v.w << 32);
+#pragma unroll 1
+    for (int j = 0; j < 16 && p + (uint64_t)j < a.nbytes; ++j)
+        gstore(a.out + p + j, (uint8_t)((j < 8 ? lo : hi) >> (8 * (j & 7))));
+}
+
+__global__ __launch_bounds__(NT) void k_an_docstarts(const AnArgs a) {
+    const uint64_t d = (uint64_t)blockIdx.x * NT + threadIdx.x + 1u;
+    if (d >= a.ndocs) return;
+    const uint64_t pos = a.doc_off[d];
+    if (pos <= a.lo || pos >= a.hi || pos >= a.nbytes) return;   /* the window's own edges are boundaries already */
+    atomicOr(&a.dstart[pos >> 5], 1u << (pos & 31u));
+}
+
+__global__ __launch_bounds__(NT) void k_an_map(const AnArgs a, uint64_t ngroups) {
+    const uint64_t g = (uint64_t)blockIdx.x * NT + threadIdx.x;
+    if (g >= ngroups) return;
+    const uint32_t phase = (uint32_t)((uintptr_t)a.in & 15u);
+    const long long p = (long long)(g * 16u);
+    const uint4 v = load16(a, p, phase);
+    store16(a, (uint64_t)p, map_group(v, range16(p, a.lo, a.hi), a.flags));
+}
+
+struct Group {
+    uint32_t tk, ds;
+};
+
+/* loads, maps and publishes group gi of the tile whose first group lies at byte p0 */
+__device__ __forceinline__ Group an_stage(const AnArgs& a, long long p0, uint32_t gi, uint32_t phase, uint32_t* s_buf,
+                                          uint32_t* s_tk, uint32_t* s_cont) {
+    const long long p = p0 + (long long)(gi * 16u);
+    const uint32_t win = range16(p, a.lo, a.hi);
+    const uint4 v = map_group(load16(a, p, phase), win, a.flags);
+    Group g;
+    g.tk = ~ws_mask16_swar(v) & win;
+    g.ds = 0u;
+    if (p >= 0 && (uint64_t)p < a.nbytes) g.ds = (gload(a.dstart + ((uint64_t)p >> 5)) >> ((uint32_t)p & 16u)) & 0xFFFFu;
+    *(uint4*)(s_buf + gi * 4u) = v;
+    ((uint16_t*)s_tk)[gi] = (uint16_t)g.tk;
+    ((uint16_t*)s_cont)[gi] = (uint16_t)(g.tk & ~g.ds);
+    return g;
+}
+
+/* the tokens that start in group gi: their bits set in s_blank when short or a stop word.
+ * s_buf, s_cont and s_blank are indexed by the byte's position in the held range: bit b of the
+ * two bitmaps is byte b of s_buf.  Returns the tokens blanked that start inside the tile. */
+__device__ __forceinline__ uint32_t an_filter(const AnArgs& a, uint32_t gi, Group g, const uint32_t* s_buf, const uint32_t* s_tk,
+                                              const uint32_t* s_cont, uint32_t* s_blank, const uint32_t* slots,
+                                              uint32_t nslots, const uint32_t* words) {
+    /* group 0's predecessor is not held: a token that runs into the halo from before it is
+     * longer than 64 bytes when it reaches the tile, so it need not be seen as one */
+    const uint32_t prev = gi ? (uint32_t)((const uint16_t*)s_tk)[gi - 1u] >> 15 : 1u;
+    uint32_t nblank = 0;
+    for (uint32_t m = g.tk & (~((g.tk << 1) | prev) | g.ds) & 0xFFFFu; m; m &= m - 1u) {
+        const uint32_t pos = gi * 16u + (uint32_t)__builtin_ctz(m);
+        /* the continuation bits behind the start: di + 2 <= (NG * 16 - 1) / 32 for every start this lane owns */
+        const uint32_t q = pos + 1u, di = q >> 5, sh = q & 31u;
+        const uint64_t c01 = (uint64_t)s_cont[di] | ((uint64_t)s_cont[di + 1u] << 32);
+        const uint64_t x = sh ? (c01 >> sh) | ((uint64_t)s_cont[di + 2u] << (64u - sh)) : c01;
+        const uint32_t len = 1u + (x == ~0ull ? 64u : (uint32_t)__builtin_ctzll(~x));
+        if (len > AN_MAX_WORD || pos + len <= AN_HALO) continue;   /* never blanked, or it ends before the tile */
+        bool blank = len < a.min_len;
+        if (!blank && nslots) {
+            const uint32_t* aw = s_buf + (pos >> 2);
+            blank = an_tab_find(slots, nslots, words, aw, pos & 3u, len, an_hash(aw, pos & 3u, len)) != 0;
+        }
+        if (blank) {
+            for (uint32_t b = pos, e = pos + len; b < e;) {   /* at most three words */
+                const uint32_t w = b >> 5, n = (e < ((w + 1u) << 5) ? e : ((w + 1u) << 5)) - b;
+                atomicOr(&s_blank[w], (n == 32u ? ~0u : (1u << n) - 1u) << (b & 31u));
+                b += n;
+            }
+            nblank += pos >= AN_HALO ? 1u : 0u;
+        }
+    }
+    return nblank;
+}
+
+__global__ __launch_bounds__(NT, 8) void k_an_filter(const AnArgs a, uint64_t ntiles) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t s_tab[];
+    __shared__ __attribute__((aligned(16))) uint32_t s_buf[NG * 4u];
+    __shared__ __attribute__((aligned(16))) uint32_t s_tk[BM_WORDS], s_cont[BM_WORDS], s_blank[BM_WORDS];
+    __shared__ uint32_t s_red[NT / 64];
+    const uint32_t tid = threadIdx.x;
+    for (uint32_t i = tid; i < a.tab_bytes / 16u; i += NT) ((uint4*)s_tab)[i] = gload((const uint4*)a.tab + i);
+    if (tid < BM_WORDS) s_blank[tid] = 0u;
+    __syncthreads();
+    const uint32_t nslots = s_tab[0];
+    const uint32_t* slots = s_tab + AN_HDR_WORDS;
+    const uint32_t* words = s_tab + s_tab[2] / 4u;
+    const uint32_t phase = (uint32_t)((uintptr_t)a.in & 15u);
+    const uint32_t hgi = tid < HG ? tid : HG + NT + (tid - HG);   /* lanes 0..2 HG - 1: a halo group too */
+    uint32_t nblank = 0;
+    /* no barrier between steps: after the second barrier a lane reads only its own group of
+     * s_buf and its own 16 bits of s_blank (which it clears for the next step; the halo groups'
+     * bits are set but never read), and the next step's first phase rewrites both from that
+     * lane alone */
+    for (uint64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+        const long long p0 = (long long)(tile * AN_TILE) - (long long)AN_HALO;
+        const Group gm = an_stage(a, p0, HG + tid, phase, s_buf, s_tk, s_cont);
+        Group gh{0u, 0u};
+        if (tid < 2u * HG) gh = an_stage(a, p0, hgi, phase, s_buf, s_tk, s_cont);
+        __syncthreads();
+        nblank += an_filter(a, HG + tid, gm, s_buf, s_tk, s_cont, s_blank, slots, nslots, words);
+        if (tid < HG) nblank += an_filter(a, tid, gh, s_buf, s_tk, s_cont, s_blank, slots, nslots, words);
+        __syncthreads();
+        uint4 v = *(const uint4*)(s_buf + (HG + tid) * 4u);
+        const uint32_t bl = ((uint16_t*)s_blank)[HG + tid];
+        if (bl) {
+            ((uint16_t*)s_blank)[HG + tid] = 0u;
+            uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const uint32_t bm = expand4(bl >> (4 * k));
+                w[k] = (w[k] & ~bm) | (0x20202020u & bm);
+            }
+            v = make_uint4(w[0], w[1], w[2], w[3]);
+        }
+        store16(a, tile * AN_TILE + tid * 16u, v);
+    }
+    const uint32_t wsum = wave_sum(nblank);
+    if ((tid & 63u) == 0u) s_red[tid >> 6] = wsum;
+    __syncthreads();
+    if (tid == 0) {
+        uint32_t tot = 0;
+        for (int k = 0; k < NT / 64; ++k) tot += s_red[k];
+        if (tot) (void)gatomic_add(a.blanked, (unsigned long long)tot);
+    }
+}
+
+}  // namespace
+
+int launch_an_docstarts(const AnArgs& a, hipStream_t s) {
+    if (hipMemsetAsync(a.dstart, 0, (size_t)(a.nbytes / 32u + 2u) * 4u, s) != hipSuccess) return -1;
+    if (a.ndocs < 2u) return 0;
+    k_an_docstarts<<<(unsigned)(((uint64_t)a.ndocs - 1u + NT - 1u) / NT), NT, 0, s>>>(a);
+    return ok();
+}
+
+uint32_t an_lds_bytes(const AnArgs& a, uint32_t nstop) {
+    return (nstop == 0u && a.min_len <= 1u) ? 0u : a.tab_bytes + AN_STATIC_LDS;
+}
+
+int launch_analyze(const AnArgs& a, uint32_t nstop, uint32_t ncu, hipStream_t s) {
+    if (!a.nbytes) return 0;
+    const uint32_t lds = an_lds_bytes(a, nstop);
+    if (!lds) {
+        const uint64_t ngroups = (a.nbytes + 15u) / 16u, nblocks = (ngroups + NT - 1u) / NT;
+        if (nblocks > 0x7FFFFFFFull) return -1;
+        k_an_map<<<(unsigned)nblocks, NT, 0, s>>>(a, ngroups);
+        return ok();
+    }
+    const uint64_t ntiles = (a.nbytes + AN_TILE - 1u) / AN_TILE;
+    uint32_t per_cu = 163840u / lds;   /* LDS of a CU; 2048 lanes of a CU are eight workgroups */
+    per_cu = per_cu > 8u ? 8u : (per_cu ? per_cu : 1u);
+    const uint64_t slots = (uint64_t)(ncu ? ncu : 256u) * per_cu;
+    k_an_filter<<<(unsigned)(ntiles < slots ? ntiles : slots), NT, a.tab_bytes, s>>>(a, ntiles);
+    return ok();
+}

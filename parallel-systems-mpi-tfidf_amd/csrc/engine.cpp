@@ -39,6 +39,7 @@
 
 #include "../../include/tfidf.h"
 #include "kernels.h"
+#include "analyze_tab.h"
 #include "synth.h"
 #include "xport.h"
 
@@ -293,6 +294,12 @@ struct tfidf_ctx {
     uint64_t m_blob_bytes = 0;
     hipEvent_t ev_m[2] = {};                    /* clear + build bounds (created by the first import) */
     tfidf_model_info minfo{};
+    /* the analyzer (tfidf_analyze, analyze.hip): a host input's staged bytes; per slot the
+     * analyzed bytes and the context's copies of the offsets and ids; the document-start bitmap,
+     * the stop-word table and the blanked-token counter of the call in flight */
+    DevBuf an_in, an_bytes[2], an_off[2], an_ids[2], an_dstart, an_tab, an_cnt;
+    hipEvent_t ev_an[2] = {};                   /* the kernels' bounds (created by the first call) */
+    tfidf_analyze_info aninfo{};
 #define WR_NBUF 8
 #define WR_BUF (16ull << 20)
 #define WR_GROUPS 8
@@ -592,6 +599,11 @@ void tfidf_close(tfidf_ctx* ctx) {
     for (hipEvent_t e : ctx->ev_m)
         if (e) (void)hipEventDestroy(e);
     for (DevBuf* b : {&ctx->m_off, &ctx->m_blob, &ctx->m_stat}) b->release();
+    for (hipEvent_t e : ctx->ev_an)
+        if (e) (void)hipEventDestroy(e);
+    for (DevBuf* b : {&ctx->an_in, &ctx->an_bytes[0], &ctx->an_bytes[1], &ctx->an_off[0], &ctx->an_off[1], &ctx->an_ids[0],
+                      &ctx->an_ids[1], &ctx->an_dstart, &ctx->an_tab, &ctx->an_cnt})
+        b->release();
     DevBuf* bufs[] = {&ctx->arena_buf, &ctx->in_bytes, &ctx->in_off, &ctx->in_ids, &ctx->syn_bytes, &ctx->syn_off,
                       &ctx->syn_ids, &ctx->syn_ntok, &ctx->syn_blkfirst, &ctx->syn_blkbytes, &ctx->syn_cdf,
                       &ctx->chunk_start, &ctx->chunk_doc, &ctx->vkeys, &ctx->vrep, &ctx->rec_slot, &ctx->rec_cnt,
@@ -3167,6 +3179,127 @@ extern "C" int tfidf_last_transform_info(const tfidf_ctx* ctx, tfidf_transform_i
     if (!ctx || !info || info->size < sizeof(uint64_t)) return TFIDF_E_INVAL;
     const uint64_t n = info->size < sizeof(tfidf_transform_info) ? info->size : sizeof(tfidf_transform_info);
     tfidf_transform_info o = ctx->trinfo;
+    o.size = n;
+    memcpy(info, &o, (size_t)n);
+    return TFIDF_OK;
+}
+
+/* ---------------------------------------------------------------- analyzer ----
+ * include/tfidf.h, section "analyzer"; analyze.hip.  The check, the table build and the host
+ * definition are analyze_host.c.  The call stands beside a run: it reads and writes buffers of
+ * its own and none of the run's state. */
+extern "C" int tfidf_analyze(tfidf_ctx* ctx, const tfidf_analyzer* an, const tfidf_corpus* in_, uint32_t slot,
+                             tfidf_corpus* out) {
+    if (!ctx || !an || !in_ || !out || slot > 1u) return TFIDF_E_INVAL;
+    const int arc = tfidf_analyzer_check(an);
+    if (arc) return arc;
+    const tfidf_corpus in = *in_;   /* out may be the same struct */
+    const uint32_t N = in.ndocs;
+    if (N && !in.doc_off) return TFIDF_E_INVAL;
+    if (in.nbytes && !in.bytes) return TFIDF_E_INVAL;
+    const bool dev = (in.flags & TFIDF_CORPUS_DEVICE) != 0;
+    DevBuf& ob = ctx->an_bytes[slot];
+    if (dev && ob.p && in.bytes >= ob.as<uint8_t>() && in.bytes < ob.as<uint8_t>() + ob.cap) return TFIDF_E_INVAL;
+    const auto wall0 = std::chrono::steady_clock::now();
+    HIPCHK(hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    /* the offsets on the host: checked here, by tfidf_transform's rules */
+    std::vector<uint64_t> off_copy;
+    const uint64_t* off = in.doc_off;
+    if (dev && N) {
+        off_copy.resize((size_t)N + 1);
+        HIPCHK(hipMemcpyAsync(off_copy.data(), in.doc_off, ((size_t)N + 1) * 8, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        off = off_copy.data();
+    }
+    for (uint32_t d = 0; d < N; ++d)
+        if (off[d] > off[d + 1]) return TFIDF_E_INVAL;
+    if (N && off[N] > in.nbytes) return TFIDF_E_INVAL;
+    for (hipEvent_t& e : ctx->ev_an)
+        if (!e) HIPCHK(hipEventCreate(&e));
+    if (!ctx->ncu) {
+        int n = 0;
+        if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, ctx->device) != hipSuccess || n <= 0) n = 256;
+        ctx->ncu = (uint32_t)n;
+    }
+    const hipMemcpyKind up = dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+    ENSURE(ctx->an_bytes[slot], in.nbytes + 64);
+    ENSURE(ctx->an_off[slot], ((size_t)N + 1) * 8);
+    if (in.doc_off) HIPCHK(hipMemcpyAsync(ctx->an_off[slot].p, in.doc_off, ((size_t)N + 1) * 8, up, s));
+    else HIPCHK(hipMemsetAsync(ctx->an_off[slot].p, 0, 8, s));
+    if (in.doc_ids && N) {
+        ENSURE(ctx->an_ids[slot], (size_t)N * 4);
+        HIPCHK(hipMemcpyAsync(ctx->an_ids[slot].p, in.doc_ids, (size_t)N * 4, up, s));
+    }
+    const uint8_t* d_in = in.bytes;
+    if (!dev && in.nbytes) {
+        ENSURE(ctx->an_in, in.nbytes + 64);
+        HIPCHK(hipMemcpyAsync(ctx->an_in.p, in.bytes, in.nbytes, hipMemcpyHostToDevice, s));
+        d_in = ctx->an_in.as<uint8_t>();
+    }
+    std::vector<uint32_t> blob(tfidf_an_table_bytes(an) / 4u);
+    const uint32_t tab_bytes = tfidf_an_table_build(an, blob.data());
+    ENSURE(ctx->an_tab, tab_bytes);
+    ENSURE(ctx->an_cnt, 256);
+    HIPCHK(hipMemcpyAsync(ctx->an_tab.p, blob.data(), tab_bytes, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemsetAsync(ctx->an_cnt.p, 0, 8, s));
+
+    AnArgs a{};
+    a.in = d_in;
+    a.out = ctx->an_bytes[slot].as<uint8_t>();
+    a.nbytes = in.nbytes;
+    a.lo = N ? off[0] : 0;
+    a.hi = N ? off[N] : 0;
+    a.doc_off = ctx->an_off[slot].as<uint64_t>();
+    a.ndocs = N;
+    a.flags = an->flags;
+    a.min_len = an->min_len;
+    a.tab = ctx->an_tab.as<uint32_t>();
+    a.tab_bytes = tab_bytes;
+    a.blanked = ctx->an_cnt.as<unsigned long long>();
+    const uint32_t lds = an_lds_bytes(a, an->nstop);
+    if (lds) {
+        ENSURE(ctx->an_dstart, (size_t)(in.nbytes / 32u + 2u) * 4u);
+        a.dstart = ctx->an_dstart.as<uint32_t>();
+    }
+    HIPCHK(hipEventRecord(ctx->ev_an[0], s));
+    if ((lds && launch_an_docstarts(a, s)) || launch_analyze(a, an->nstop, ctx->ncu, s)) {
+        HIPCHK(hipGetLastError());
+        return TFIDF_E_HIP;
+    }
+    HIPCHK(hipEventRecord(ctx->ev_an[1], s));
+    unsigned long long blanked = 0;
+    HIPCHK(hipMemcpyAsync(&blanked, ctx->an_cnt.p, 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+
+    out->bytes = a.out;
+    out->nbytes = in.nbytes;
+    out->doc_off = a.doc_off;
+    out->doc_ids = (in.doc_ids && N) ? ctx->an_ids[slot].as<uint32_t>() : nullptr;
+    out->ndocs = N;
+    out->flags = TFIDF_CORPUS_DEVICE;
+    out->ndocs_total = in.ndocs_total;
+
+    tfidf_analyze_info ai{};
+    ai.nbytes = in.nbytes;
+    ai.ndocs = N;
+    ai.nstop = an->nstop;
+    ai.table_slots = blob[0];
+    ai.lds_bytes = lds;
+    ai.tile_bytes = AN_TILE;
+    ai.blanked_tokens = blanked;
+    float ms = 0;
+    (void)hipEventElapsedTime(&ms, ctx->ev_an[0], ctx->ev_an[1]);
+    ai.ms_kernel = ms;
+    ai.ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - wall0).count();
+    ctx->aninfo = ai;
+    return TFIDF_OK;
+}
+
+extern "C" int tfidf_last_analyze_info(const tfidf_ctx* ctx, tfidf_analyze_info* info) {
+    if (!ctx || !info || info->size < sizeof(uint64_t)) return TFIDF_E_INVAL;
+    const uint64_t n = info->size < sizeof(tfidf_analyze_info) ? info->size : sizeof(tfidf_analyze_info);
+    tfidf_analyze_info o = ctx->aninfo;
     o.size = n;
     memcpy(info, &o, (size_t)n);
     return TFIDF_OK;

@@ -749,4 +749,31 @@ struct KmTopArgs {
 };
 int launch_km_top(const KmTopArgs& a, hipStream_t s);
 
+/* ---- the analyzer (analyze.hip, tfidf_analyze) ---- */
+#define AN_TILE 4096u   /* bytes a workgroup owns per step: 256 lanes x 16 */
+#define AN_HALO 80u     /* mapped bytes held on each side of the tile (a multiple of 16, > TFIDF_AN_MAX_WORD + 1) */
+/* out[i] = the analyzed in[i] for i in [0, nbytes): the byte map inside [lo, hi) = the documents'
+ * window, the token filter on the mapped bytes, everything else copied.  out is 16-byte
+ * aligned, in has any alignment; no byte outside in[0, nbytes) is read and none outside
+ * out[0, nbytes) written.  dstart: bit i = a document starts at byte i, lo < i < hi
+ * (launch_an_docstarts), read by the filtering form only.  tab: the stop-word blob of
+ * analyze_tab.h in device memory (a header alone when the list is empty). */
+struct AnArgs {
+    const uint8_t* in;
+    uint8_t* out;
+    uint64_t nbytes, lo, hi;
+    const uint64_t* doc_off;
+    uint32_t ndocs;
+    uint32_t flags, min_len;
+    uint32_t* dstart;            /* nbytes / 32 + 2 words */
+    const uint32_t* tab;
+    uint32_t tab_bytes;
+    unsigned long long* blanked; /* zeroed by the caller */
+};
+/* zeroes dstart and sets the documents' start bits */
+int launch_an_docstarts(const AnArgs& a, hipStream_t s);
+/* LDS of a workgroup of the filtering form; 0: the call is a pure byte map */
+uint32_t an_lds_bytes(const AnArgs& a, uint32_t nstop);
+int launch_analyze(const AnArgs& a, uint32_t nstop, uint32_t ncu, hipStream_t s);
+
 #endif

@@ -88,6 +88,20 @@
  *                          which must be given, is scored against it on one GPU.  With an option
  *                          that needs the run's pairs (--query, --keywords, --similar,
  *                          --save-model, --debug-jobs) it is a usage error (exit 2).
+ *
+ * Analyzer (case folding, punctuation, short tokens and stop words, applied to the bytes before
+ * they are counted: tfidf_analyze on the GPU for input/, tfidf_analyze_host for the rest):
+ *   --lower                0x41..0x5A become lower case;
+ *   --strip-punct          every ASCII byte that is no letter, digit or separator becomes a blank;
+ *   --min-token N          tokens shorter than N bytes are blanked, N is 0..TFIDF_AN_MAX_WORD;
+ *   --stopwords FILE       the words of FILE (split at separators, passed through the same
+ *                          --lower / --strip-punct first, so "The" in the file works with
+ *                          --lower) are blanked; at most TFIDF_AN_MAX_STOP words.
+ * With any of the four, input/ is analyzed in HBM between ingest and run (every shard on its own
+ * GPU), and the lines of --query FILE and the documents of --transform DIR pass through the same
+ * analyzer on the host, also under --model FILE.  The model file does not record the analyzer:
+ * whoever serves from it passes the same flags again.  Without any of them nothing new is
+ * called and every byte of every output is as before.
  */
 #include <dirent.h>
 #include <pthread.h>
@@ -123,6 +137,71 @@ static int debug_jobs(tfidf_ctx* ctx) {
     tfidf_print_jobs(&r);
     tfidf_result_free(&r);
     return TFIDF_OK;
+}
+
+/* --------------------------------------------------------------- analyzer -- */
+
+static struct {
+    int on;             /* 0: none of the analyzer's options, behaviour and bytes as without them */
+    const char* stopfile;
+    tfidf_analyzer an;
+} g_an;
+
+/* --stopwords: FILE through the analyzer's own byte map, split at separators.  A word longer than
+ * TFIDF_AN_MAX_WORD bytes or one that holds a NUL equals no token that can be blanked: dropped. */
+static int load_stopwords(void) {
+    g_an.an.size = sizeof(g_an.an);
+    if (!g_an.stopfile) return TFIDF_OK;
+    FILE* f = fopen(g_an.stopfile, "rb");
+    if (!f) { fprintf(stderr, "tfidf: --stopwords: cannot open %s\n", g_an.stopfile); return TFIDF_E_INVAL; }
+    size_t cap = 1 << 16, n = 0;
+    uint8_t* b = (uint8_t*)malloc(cap);
+    for (;;) {
+        if (!b) { fclose(f); return TFIDF_E_NOMEM; }
+        const size_t got = fread(b + n, 1, cap - n, f);
+        n += got;
+        if (got == 0) break;
+        if (n == cap) { cap *= 2; b = (uint8_t*)realloc(b, cap); }
+    }
+    fclose(f);
+    tfidf_analyzer map = g_an.an;   /* the same flags, no list, every token kept */
+    map.min_len = 0;
+    const uint64_t whole[2] = {0, n};
+    int rc = tfidf_analyze_host(&map, b, n, whole, 1, b);
+    uint64_t* off = (uint64_t*)malloc(((size_t)TFIDF_AN_MAX_STOP + 1) * sizeof(uint64_t));
+    if (!rc && !off) rc = TFIDF_E_NOMEM;
+    uint32_t nw = 0;
+    size_t w = 0;   /* the kept words, packed at the buffer's front */
+    if (off) off[0] = 0;
+    for (size_t i = 0; !rc && i < n;) {
+        const uint8_t c = b[i];
+        if (c == 0x20 || (c >= 0x09 && c <= 0x0D)) { ++i; continue; }
+        size_t j = i;
+        int nul = 0;
+        while (j < n && !(b[j] == 0x20 || (b[j] >= 0x09 && b[j] <= 0x0D))) nul |= b[j++] == 0;
+        if (!nul && j - i <= TFIDF_AN_MAX_WORD) {
+            if (nw == TFIDF_AN_MAX_STOP || w + (j - i) > TFIDF_AN_MAX_STOP_BYTES) {
+                fprintf(stderr, "tfidf: --stopwords takes at most %u words and %u bytes\n", TFIDF_AN_MAX_STOP,
+                        TFIDF_AN_MAX_STOP_BYTES);
+                rc = TFIDF_E_INVAL;
+                break;
+            }
+            memmove(b + w, b + i, j - i);
+            w += j - i;
+            off[++nw] = w;
+        }
+        i = j;
+    }
+    if (rc) { free(b); free(off); return rc; }
+    g_an.an.stop_bytes = b;
+    g_an.an.stop_off = off;
+    g_an.an.nstop = nw;
+    return TFIDF_OK;
+}
+
+/* the analyzer on host bytes in place (query lines, transform batches); a no-op without its options */
+static int analyze_host_batch(uint8_t* bytes, uint64_t nbytes, const uint64_t* off, uint32_t n) {
+    return g_an.on ? tfidf_analyze_host(&g_an.an, bytes, nbytes, off, n, bytes) : TFIDF_OK;
 }
 
 /* ---------------------------------------------------------------- queries -- */
@@ -176,7 +255,8 @@ static int run_queries(tfidf_ctx* ctx, tfidf_group* g) {
     memset(&qs, 0, sizeof(qs));
     int rc = load_queries(&bytes, &qs.nbytes, &off, &qs.nqueries);
     if (rc == TFIDF_E_NOINPUT) { printf("Error Opening File: %s\n", g_query.file); return TFIDF_OK; }
-    if (rc) return rc;
+    if (!rc) rc = analyze_host_batch(bytes, qs.nbytes, off, qs.nqueries);
+    if (rc) { free(bytes); free(off); return rc; }
     qs.bytes = bytes;
     qs.q_off = off;
     tfidf_hits h;
@@ -357,7 +437,8 @@ static int run_transform(tfidf_ctx* ctx, tfidf_group* g) {
     int rc = tfidf_ingest_dir(g_transform.dir, &bytes, &b.nbytes, &off, &b.ndocs, &bad);
     if (rc == TFIDF_E_NOINPUT) { printf("Directory failed to open\n"); return TFIDF_OK; }
     if (rc == TFIDF_E_NODOC) { (void)missing_doc(g_transform.dir, bad, b.ndocs); return TFIDF_OK; }
-    if (rc) return rc;
+    if (!rc) rc = analyze_host_batch(bytes, b.nbytes, off, b.ndocs);
+    if (rc) { tfidf_free(bytes); tfidf_free(off); return rc; }
     b.bytes = bytes;
     b.doc_off = off;
     tfidf_rows t;
@@ -434,7 +515,8 @@ static int run_single(int device, const char* indir, const char* outpath, int de
     if (rc == TFIDF_E_NODOC) { tfidf_close(ctx); return missing_doc(indir, bad, c.ndocs); }
     if (rc) { tfidf_close(ctx); return fail(rc); }
     if (c.ndocs == 0) { printf("More workers than input files! Exiting.\n"); tfidf_close(ctx); return 0; }
-    rc = tfidf_run(ctx, &c);
+    if (g_an.on) rc = tfidf_analyze(ctx, &g_an.an, &c, TFIDF_AN_SLOT_CORPUS, &c);   /* in HBM, where the ingest left it */
+    if (!rc) rc = tfidf_run(ctx, &c);
     if (!rc && debug) rc = debug_jobs(ctx);
     if (rc) { tfidf_close(ctx); return fail(rc); }
     tfidf_run_info ri;
@@ -490,6 +572,8 @@ static void* ingest_job(void* arg) {
     const int threads = 4;
     j->rc = tfidf_ingest_shard_device(tfidf_group_ctx(j->g, (int)j->shard), j->indir, j->plan, j->shard, threads,
                                       &j->corpus, &j->bad, NULL);
+    if (!j->rc && g_an.on)
+        j->rc = tfidf_analyze(tfidf_group_ctx(j->g, (int)j->shard), &g_an.an, &j->corpus, TFIDF_AN_SLOT_CORPUS, &j->corpus);
     return NULL;
 }
 
@@ -615,6 +699,15 @@ int main(int argc, char** argv) {
             if (k < 1 || k > (long)TFIDF_TERMS_MAX_K) { fprintf(stderr, "tfidf: --keywords takes 1..%u\n", TFIDF_TERMS_MAX_K); return 2; }
             g_keywords.k = (uint32_t)k;
         }
+        else if (!strcmp(argv[i], "--lower")) { g_an.an.flags |= TFIDF_AN_LOWER; g_an.on = 1; }
+        else if (!strcmp(argv[i], "--strip-punct")) { g_an.an.flags |= TFIDF_AN_PUNCT; g_an.on = 1; }
+        else if (!strcmp(argv[i], "--stopwords") && i + 1 < argc) { g_an.stopfile = argv[++i]; g_an.on = 1; }
+        else if (!strcmp(argv[i], "--min-token") && i + 1 < argc) {
+            const long v = atol(argv[++i]);
+            if (v < 0 || v > (long)TFIDF_AN_MAX_WORD) { fprintf(stderr, "tfidf: --min-token takes 0..%u\n", TFIDF_AN_MAX_WORD); return 2; }
+            g_an.an.min_len = (uint32_t)v;
+            g_an.on = 1;
+        }
         else if (!strcmp(argv[i], "--transform-file") && i + 1 < argc) g_transform.file = argv[++i];
         else if (!strcmp(argv[i], "--transform") && i + 1 < argc) g_transform.dir = argv[++i];
         else if (!strcmp(argv[i], "--save-model") && i + 1 < argc) g_model.save = argv[++i];
@@ -649,15 +742,21 @@ int main(int argc, char** argv) {
                             "[--keywords K [--keywords-file FILE]] "
                             "[--similar K [--similar-docs FILE] [--similar-file FILE]] "
                             "[--clusters K [--clusters-iter I] [--clusters-seeds FILE] [--clusters-terms T] [--clusters-file FILE]] "
-                            "[--transform DIR [--transform-file FILE]] [--save-model FILE]\n"
-                            "       tfidf --model FILE --transform DIR [--transform-file FILE] [--device D]\n"
+                            "[--transform DIR [--transform-file FILE]] [--save-model FILE] "
+                            "[--lower] [--strip-punct] [--min-token N] [--stopwords FILE]\n"
+                            "       tfidf --model FILE --transform DIR [--transform-file FILE] [--device D] "
+                            "[--lower] [--strip-punct] [--min-token N] [--stopwords FILE]\n"
                             "  --similar K without --similar-docs searches for every document: "
                             "ceil(N / group) scans of the scored pairs, group <= 64\n"
                             "  --save-model FILE writes the run's term table, df and N; --model FILE scores "
-                            "--transform DIR against such a file without input/ or output.txt\n");
+                            "--transform DIR against such a file without input/ or output.txt\n"
+                            "  --lower, --strip-punct, --min-token N and --stopwords FILE analyze input/, the query "
+                            "lines and the --transform documents before they are counted; the model file does not "
+                            "record them\n");
             return 2;
         }
     }
+    if (g_an.on && load_stopwords() != TFIDF_OK) return 2;
     if (g_model.load) {   /* a model holds no pairs: nothing to rank, list or print */
         if (!g_transform.dir) {
             fprintf(stderr, "tfidf: --model needs --transform DIR\n");

@@ -46,6 +46,7 @@ EXPORTS = [
     "tfidf_transform", "tfidf_rows_free", "tfidf_group_transform", "tfidf_last_transform_info",
     "tfidf_model_check", "tfidf_model_export", "tfidf_group_model_export", "tfidf_model_import",
     "tfidf_model_save", "tfidf_model_load", "tfidf_model_free", "tfidf_last_model_info",
+    "tfidf_analyzer_check", "tfidf_analyze_host", "tfidf_analyze", "tfidf_last_analyze_info",
 ]
 QUERY_MAX_K = 1024  # TFIDF_QUERY_MAX_K
 TERMS_MAX_K = 1024  # TFIDF_TERMS_MAX_K
@@ -61,6 +62,13 @@ E_PEER = -11
 E_CAPACITY = -9
 E_OUTPUT = -8
 E_MODEL = -12
+AN_LOWER = 1  # TFIDF_AN_LOWER
+AN_PUNCT = 2  # TFIDF_AN_PUNCT
+AN_MAX_WORD = 64  # TFIDF_AN_MAX_WORD
+AN_MAX_STOP = 4096  # TFIDF_AN_MAX_STOP
+AN_MAX_STOP_BYTES = 32768  # TFIDF_AN_MAX_STOP_BYTES
+AN_SLOT_CORPUS = 0  # TFIDF_AN_SLOT_CORPUS
+AN_SLOT_BATCH = 1  # TFIDF_AN_SLOT_BATCH
 
 
 class Corpus(C.Structure):
@@ -226,6 +234,21 @@ class ModelInfo(C.Structure):
     ]
 
 
+class Analyzer(C.Structure):
+    _fields_ = [
+        ("size", C.c_uint64), ("flags", C.c_uint32), ("min_len", C.c_uint32), ("stop_bytes", C.c_void_p),
+        ("stop_off", C.c_void_p), ("nstop", C.c_uint32), ("reserved", C.c_uint32),
+    ]
+
+
+class AnalyzeInfo(C.Structure):
+    _fields_ = [
+        ("size", C.c_uint64), ("nbytes", C.c_uint64), ("ndocs", C.c_uint32), ("nstop", C.c_uint32),
+        ("table_slots", C.c_uint32), ("lds_bytes", C.c_uint32), ("tile_bytes", C.c_uint32), ("reserved", C.c_uint32),
+        ("blanked_tokens", C.c_uint64), ("ms_kernel", C.c_double), ("ms_total", C.c_double),
+    ]
+
+
 class DirPlan(C.Structure):
     _fields_ = [
         ("ndocs", C.c_uint32), ("nshards", C.c_uint32), ("doc_ids", C.POINTER(C.c_uint32)),
@@ -330,6 +353,10 @@ def lib() -> C.CDLL:
         L.tfidf_model_free.argtypes = [C.POINTER(Model)]
         L.tfidf_model_free.restype = None
         L.tfidf_last_model_info.argtypes = [C.c_void_p, C.POINTER(ModelInfo)]
+        L.tfidf_analyzer_check.argtypes = [C.POINTER(Analyzer)]
+        L.tfidf_analyze_host.argtypes = [C.POINTER(Analyzer), C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p]
+        L.tfidf_analyze.argtypes = [C.c_void_p, C.POINTER(Analyzer), C.POINTER(Corpus), C.c_uint32, C.POINTER(Corpus)]
+        L.tfidf_last_analyze_info.argtypes = [C.c_void_p, C.POINTER(AnalyzeInfo)]
         if L.tfidf_abi_version() != ABI_VERSION:
             raise RuntimeError(f"{LIB_PATH}: ABI version {L.tfidf_abi_version()}, binding expects {ABI_VERSION} "
                                f"(stale build: rebuild with __graft_entry__.build())")
@@ -551,6 +578,43 @@ def model_load(path: str) -> dict:
         return _model_dict(m)
     finally:
         lib().tfidf_model_free(C.byref(m))
+
+
+def analyzer(lower: bool = False, punct: bool = False, min_len: int = 0, stop=()):
+    """A tfidf_analyzer over a list of stop words (bytes objects, already folded); returns
+    (struct, arrays to keep alive)."""
+    stop = [bytes(w) for w in stop]
+    sb = np.frombuffer(b"".join(stop), dtype=np.uint8)
+    so = np.zeros(len(stop) + 1, dtype=np.uint64)
+    if stop:
+        so[1:] = np.cumsum([len(w) for w in stop], dtype=np.uint64)
+    a = Analyzer()
+    a.size = C.sizeof(Analyzer)
+    a.flags = (AN_LOWER if lower else 0) | (AN_PUNCT if punct else 0)
+    a.min_len = min_len
+    a.stop_bytes = sb.ctypes.data if len(sb) else None
+    a.stop_off = so.ctypes.data if stop else None
+    a.nstop = len(stop)
+    return a, (sb, so)
+
+
+def analyzer_check(a: Analyzer) -> int:
+    """tfidf_analyzer_check (host only): 0, or E_INVAL."""
+    return int(lib().tfidf_analyzer_check(C.byref(a)))
+
+
+def analyze_host(data, off, lower: bool = False, punct: bool = False, min_len: int = 0, stop=(), in_place: bool = False):
+    """tfidf_analyze_host (host only): the analyzed bytes of the documents data[off[i]:off[i + 1]]
+    as a new array (in_place: computed in a copy that is both input and output)."""
+    a, keep = analyzer(lower, punct, min_len, stop)
+    data = np.ascontiguousarray(data, dtype=np.uint8)
+    off = np.ascontiguousarray(off, dtype=np.uint64)
+    out = data.copy() if in_place else np.empty(len(data), dtype=np.uint8)
+    src = out if in_place else data
+    _chk(lib().tfidf_analyze_host(C.byref(a), src.ctypes.data if len(src) else None, len(data),
+                                  off.ctypes.data if len(off) > 1 else None, max(len(off) - 1, 0),
+                                  out.ctypes.data if len(out) else None), "tfidf_analyze_host")
+    return out
 
 
 def synth_host(seed: int, V: int, mode: int, cdf, doc_ids, ntok):
@@ -835,6 +899,31 @@ class Engine:
         t.size = C.sizeof(TransformInfo)
         _chk(lib().tfidf_last_transform_info(self.h, C.byref(t)), "tfidf_last_transform_info")
         return {k: getattr(t, k) for k, _ in TransformInfo._fields_ if k != "size"}
+
+    def analyze(self, corpus, off=None, lower: bool = False, punct: bool = False, min_len: int = 0, stop=(),
+                slot: int = AN_SLOT_CORPUS, doc_ids=None, ndocs_total: int = 0) -> Corpus:
+        """tfidf_analyze: corpus is a Corpus (host or device), or host bytes with their offsets
+        `off`.  Returns the analyzed device Corpus in the context's slot buffers, valid until
+        the next analyze with the same slot."""
+        a, keep = analyzer(lower, punct, min_len, stop)
+        if isinstance(corpus, Corpus):
+            c = corpus
+        else:
+            c, keep2 = _host_corpus(corpus, off)
+            ids = None if doc_ids is None else np.ascontiguousarray(doc_ids, dtype=np.uint32)
+            c.doc_ids = None if ids is None else ids.ctypes.data
+            c.ndocs_total = ndocs_total
+            keep = (keep, keep2, ids)
+        out = Corpus()
+        _chk(lib().tfidf_analyze(self.h, C.byref(a), C.byref(c), slot, C.byref(out)), "tfidf_analyze")
+        return out
+
+    def analyze_info(self) -> dict:
+        """Counters and device time of the last analyze (tfidf_last_analyze_info)."""
+        t = AnalyzeInfo()
+        t.size = C.sizeof(AnalyzeInfo)
+        _chk(lib().tfidf_last_analyze_info(self.h, C.byref(t)), "tfidf_last_analyze_info")
+        return {k: getattr(t, k) for k, _ in AnalyzeInfo._fields_ if k not in ("size", "reserved")}
 
     def model_export(self) -> dict:
         """The context's model (tfidf_model_export): N, terms (list of bytes in term-table order),
