@@ -834,9 +834,9 @@ int tfidf_last_model_info(const tfidf_ctx* ctx, tfidf_model_info* info);
 /* ---------------------------------------------------------------- analyzer -- */
 
 /* A byte-to-byte analyzer in front of the counter: case folding, punctuation stripping, a
- * minimum token length and a stop-word list.  The reference tokenises with fscanf("%s") and
- * compares with strcmp (TFIDF.c:141-152): "The", "the", "the," and "(the" are four terms.  The
- * analyzer rewrites a corpus (or a batch, or the lines of a query batch: bytes plus offsets)
+ * minimum token length, a stop-word list and a Porter stemmer.  The reference tokenises with
+ * fscanf("%s") and compares with strcmp (TFIDF.c:141-152): "The", "the", "the," and "(the" are
+ * four terms.  The analyzer rewrites a corpus (or a batch, or the lines of a query batch: bytes plus offsets)
  * into one of the same length with the same offsets, so tfidf_run and everything after it stay
  * as they are.  Everything is byte-exact.
  *
@@ -856,14 +856,53 @@ int tfidf_last_model_info(const tfidf_ctx* ctx, tfidf_model_info* info);
  *      at a NUL: stop words hold no NUL, so without TFIDF_AN_PUNCT a token that contains a NUL
  *      never matches.  Stop words are compared verbatim with the mapped tokens: the caller
  *      supplies them already folded.
+ *   3. stemmer (stemmer = TFIDF_STEM_PORTER), on the bytes that 1 and 2 produced.  A token that
+ *      survived the filter is stemmed when its length L is 3..TFIDF_AN_MAX_WORD and every one of
+ *      its bytes is in 0x61..0x7A.  Every other token is unchanged: one with a digit, a byte
+ *      >= 0x80, an upper-case letter (without TFIDF_AN_LOWER) or a NUL, and one of 1, 2 or more
+ *      than 64 bytes.  Leaving tokens of 1 or 2 bytes alone is the one departure from the paper;
+ *      it is the guard Porter's own C implementation has.  With S the stem's length,
+ *      1 <= S <= L, bytes [0, S) of the token become the stem and bytes [S, L) become 0x20.
+ *      min_len and the stop list see the UNSTEMMED token (the order of Lucene's stop filter and
+ *      stem filter): with "running" in the list, "running" is blanked and "run" is not; with
+ *      "run" in the list, "running" becomes "run" and stays.  A document boundary ends a token
+ *      as before: "runn|ing" split by off is two tokens, "runn" and "ing".
+ *
+ *      The algorithm is Porter 1980 exactly as published (no logi -> log; abli -> able, not
+ *      bli -> ble).  A consonant is a letter other than a, e, i, o, u and other than a y
+ *      preceded by a consonant; a y at the start or after a vowel is a consonant.  m is the
+ *      number of VC sequences in [C](VC)^m[V].  *v*: the stem contains a vowel.  *d: the stem
+ *      ends in a double consonant.  *o: the stem ends consonant-vowel-consonant with the last
+ *      letter not w, x or y.  Conditions apply to the stem in front of the suffix.  In every
+ *      step the longest matching suffix is chosen; if its condition fails, the step does
+ *      nothing ("feed" matches EED, has m = 0 and is left alone; ED is not tried).
+ *        1a  SSES -> SS, IES -> I, SS -> SS, S -> ""
+ *        1b  (m>0) EED -> EE; (*v*) ED -> ""; (*v*) ING -> "".  After the second or third rule
+ *            fired, the first of these that applies: AT -> ATE, BL -> BLE, IZ -> IZE; *d and
+ *            not ending in l, s or z -> drop the last letter; m=1 and *o -> append E
+ *        1c  (*v*) Y -> I
+ *        2   (m>0) ATIONAL -> ATE, TIONAL -> TION, ENCI -> ENCE, ANCI -> ANCE, IZER -> IZE,
+ *            ABLI -> ABLE, ALLI -> AL, ENTLI -> ENT, ELI -> E, OUSLI -> OUS, IZATION -> IZE,
+ *            ATION -> ATE, ATOR -> ATE, ALISM -> AL, IVENESS -> IVE, FULNESS -> FUL,
+ *            OUSNESS -> OUS, ALITI -> AL, IVITI -> IVE, BILITI -> BLE
+ *        3   (m>0) ICATE -> IC, ATIVE -> "", ALIZE -> AL, ICITI -> IC, ICAL -> IC, FUL -> "",
+ *            NESS -> ""
+ *        4   (m>1) removed: AL, ANCE, ENCE, ER, IC, ABLE, IBLE, ANT, EMENT, MENT, ENT, ION (only
+ *            when the stem ends in s or t), OU, ISM, ATE, ITI, OUS, IVE, IZE
+ *        5a  (m>1) E -> ""; (m=1 and not *o) E -> ""
+ *        5b  (m>1 and *d and ending in l) -> drop the last letter
  * Bytes of [0, nbytes) outside [off[0], off[n]) are copied unchanged.
- * Consequences: the analyzer is idempotent; with flags = 0, min_len <= 1 and no stop words the
- * output equals the input; a token longer than TFIDF_AN_MAX_WORD bytes is never blanked (it
- * matches no stop word and is not shorter than min_len).
- * The analyzer is not part of a model (tfidf_model, the model file): whoever scores batches
- * against a saved model passes the same analyzer again. */
+ * Consequences: without a stemmer the analyzer is idempotent, with one it is not (Porter is
+ * not: "agreed" -> "agre" -> "agr"); stemming is independent of TFIDF_AN_LOWER (an upper-case
+ * letter that was not folded makes its token ineligible); with flags = 0, min_len <= 1, no stop
+ * words and no stemmer the output equals the input; a token longer than TFIDF_AN_MAX_WORD bytes
+ * is never blanked or stemmed (it matches no stop word and is not shorter than min_len).
+ * The analyzer is not part of a model (tfidf_model, the model file), its stemmer included:
+ * whoever scores batches against a saved model passes the same analyzer again. */
 #define TFIDF_AN_LOWER 1u
 #define TFIDF_AN_PUNCT 2u
+#define TFIDF_STEM_NONE   0u
+#define TFIDF_STEM_PORTER 1u
 #define TFIDF_AN_MAX_WORD 64u            /* longest stop word, largest min_len */
 #define TFIDF_AN_MAX_STOP 4096u          /* stop words */
 #define TFIDF_AN_MAX_STOP_BYTES 32768u   /* all stop words together */
@@ -873,10 +912,13 @@ typedef struct tfidf_analyzer {
     uint32_t min_len;
     const uint8_t*  stop_bytes;  /* stop word i = stop_bytes[stop_off[i], stop_off[i + 1]) */
     const uint64_t* stop_off;    /* nstop + 1 */
-    uint32_t nstop, reserved;
+    uint32_t nstop;
+    uint32_t stemmer;            /* TFIDF_STEM_*.  This was `reserved` and unchecked until the stemmer
+                                    came; same offset and size, and every in-tree caller zeroed it */
 } tfidf_analyzer;
 /* Host only.  TFIDF_E_INVAL for: NULL; size < sizeof(tfidf_analyzer); unknown flag bits;
- * min_len > TFIDF_AN_MAX_WORD; nstop > TFIDF_AN_MAX_STOP; nstop > 0 with a NULL stop_bytes or
+ * a stemmer other than TFIDF_STEM_NONE and TFIDF_STEM_PORTER; min_len > TFIDF_AN_MAX_WORD;
+ * nstop > TFIDF_AN_MAX_STOP; nstop > 0 with a NULL stop_bytes or
  * stop_off; a non-monotone stop_off; more than TFIDF_AN_MAX_STOP_BYTES bytes of stop words; a
  * stop word that is empty, longer than TFIDF_AN_MAX_WORD, or holds a NUL or a separator.
  * Duplicates in the list are allowed. */
@@ -888,6 +930,11 @@ int tfidf_analyzer_check(const tfidf_analyzer* an);
  * kernel probes (csrc/analyze_tab.h). */
 int tfidf_analyze_host(const tfidf_analyzer* an, const uint8_t* bytes, uint64_t nbytes,
                        const uint64_t* off, uint32_t n, uint8_t* out);
+/* Host only, plain C: step 3 on one word, byte by byte, for a stop list or a query term.
+ * Returns the stem's length S and rewrites word[0, S); word[S, len) is left as it is.  Returns
+ * len and writes nothing for an ineligible word (len < 3, len > TFIDF_AN_MAX_WORD, a byte
+ * outside 0x61..0x7A); TFIDF_E_INVAL for NULL with len > 0. */
+int tfidf_stem_porter(uint8_t* word, uint32_t len);
 
 /* The same on the device (analyze.hip), where tfidf_ingest_dir_device leaves the bytes.
  * in: a host corpus (staged in a context buffer first) or a TFIDF_CORPUS_DEVICE corpus at any
@@ -921,10 +968,13 @@ typedef struct tfidf_analyze_info {
     uint32_t lds_bytes;       /* LDS of a workgroup: table, word bytes, tile and halos (0: the
                                  pure byte map, which uses none) */
     uint32_t tile_bytes;      /* bytes a workgroup owns per step */
-    uint32_t reserved;
+    uint32_t grid;            /* persistent workgroups of the tile kernel (0: the pure byte map);
+                                 env TFIDF_AN_GRID, read at tfidf_open, caps it (0 or unset: the
+                                 GPU's resident workgroups).  The result does not depend on it */
     uint64_t blanked_tokens;  /* tokens blanked (an integer atomic counter, one add per workgroup) */
     double   ms_kernel;       /* device time of the kernels (HIP events) */
     double   ms_total;        /* host wall time of the whole call */
+    uint64_t stemmed_tokens;  /* tokens whose bytes the stemmer changed, counted like blanked_tokens */
 } tfidf_analyze_info;
 int tfidf_last_analyze_info(const tfidf_ctx* ctx, tfidf_analyze_info* info);
 

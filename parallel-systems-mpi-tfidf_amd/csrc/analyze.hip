@@ -19,6 +19,14 @@
  *                 (atomicOr: lanes of one workgroup share the bitmap's words; the held bytes
  *                 themselves are not written in this phase)
  *              3. every lane blanks the marked bytes of its 16 and stores them
+ *            With a stemmer (the instantiation k_an_filter<true>; calls without one launch
+ *            k_an_filter<false>, the kernel as it was) a token that phase 2 keeps is stemmed by
+ *            the same lane (analyze_stem.h: the word's vowel mask and its last 8 letters in
+ *            registers).  The tail [S, len) goes into the blank bitmap.  The letters of the
+ *            stem's last 8 that differ from the token's go to a byte array of their own in LDS,
+ *            s_patch, with their bits in a third bitmap, s_pm; phase 3 merges them.  s_buf is
+ *            still not written in phase 2: other lanes read its words, masked, for their own
+ *            tokens.  Distinct lanes store distinct bytes of s_patch, and a token has one owner.
  *            A workgroup decides the fate of its own tile's bytes only: a token that began
  *            before the left halo is longer than 64 bytes when it reaches the tile and is never
  *            blanked, and a token that starts in the tile ends inside the right halo or is too
@@ -32,6 +40,7 @@
 #include "kernels.h"
 #include "dev_common.h"
 #include "analyze_tab.h"
+#include "analyze_stem.h"
 
 namespace {
 
@@ -44,6 +53,7 @@ static_assert(AN_TILE == NT * 16u, "one 16-byte group per lane");
 static_assert(AN_HALO % 16u == 0 && AN_HALO > AN_MAX_WORD + 1u, "the halo argument");
 constexpr uint32_t BM_WORDS = (NG * 16u / 32u + 4u) & ~3u;   /* a bit per held byte, whole 16-byte rows */
 constexpr uint32_t AN_STATIC_LDS = NG * 16u + 3u * BM_WORDS * 4u + 16u;
+constexpr uint32_t AN_STEM_LDS = NG * 16u + BM_WORDS * 4u;   /* s_patch and s_pm, behind the table */
 
 int ok() { return hipGetLastError() == hipSuccess ? 0 : -1; }
 
@@ -179,12 +189,25 @@ __device__ __forceinline__ Group an_stage(const AnArgs& a, long long p0, uint32_
     return g;
 }
 
+/* sets bits [b, e) of an LDS bitmap whose words the workgroup's lanes share: at most three words */
+__device__ __forceinline__ void an_mark(uint32_t* bm, uint32_t b, uint32_t e) {
+    while (b < e) {
+        const uint32_t w = b >> 5, n = (e < ((w + 1u) << 5) ? e : ((w + 1u) << 5)) - b;
+        atomicOr(&bm[w], (n == 32u ? ~0u : (1u << n) - 1u) << (b & 31u));
+        b += n;
+    }
+}
+
 /* the tokens that start in group gi: their bits set in s_blank when short or a stop word.
  * s_buf, s_cont and s_blank are indexed by the byte's position in the held range: bit b of the
- * two bitmaps is byte b of s_buf.  Returns the tokens blanked that start inside the tile. */
+ * bitmaps is byte b of s_buf.  Returns the tokens blanked that start inside the tile.  With STEM
+ * a token that is kept is stemmed: its tail into s_blank, the changed letters of its head into
+ * s_patch and s_pm, and nstem counts the tokens changed that start inside the tile. */
+template <bool STEM>
 __device__ __forceinline__ uint32_t an_filter(const AnArgs& a, uint32_t gi, Group g, const uint32_t* s_buf, const uint32_t* s_tk,
                                               const uint32_t* s_cont, uint32_t* s_blank, const uint32_t* slots,
-                                              uint32_t nslots, const uint32_t* words) {
+                                              uint32_t nslots, const uint32_t* words, uint8_t* s_patch, uint32_t* s_pm,
+                                              uint32_t& nstem) {
     /* group 0's predecessor is not held: a token that runs into the halo from before it is
      * longer than 64 bytes when it reaches the tile, so it need not be seen as one */
     const uint32_t prev = gi ? (uint32_t)((const uint16_t*)s_tk)[gi - 1u] >> 15 : 1u;
@@ -203,46 +226,77 @@ __device__ __forceinline__ uint32_t an_filter(const AnArgs& a, uint32_t gi, Grou
             blank = an_tab_find(slots, nslots, words, aw, pos & 3u, len, an_hash(aw, pos & 3u, len)) != 0;
         }
         if (blank) {
-            for (uint32_t b = pos, e = pos + len; b < e;) {   /* at most three words */
-                const uint32_t w = b >> 5, n = (e < ((w + 1u) << 5) ? e : ((w + 1u) << 5)) - b;
-                atomicOr(&s_blank[w], (n == 32u ? ~0u : (1u << n) - 1u) << (b & 31u));
-                b += n;
-            }
+            an_mark(s_blank, pos, pos + len);
             nblank += pos >= AN_HALO ? 1u : 0u;
+        } else if (STEM && len >= 3u) {
+            const uint32_t* aw = s_buf + (pos >> 2);
+            uint64_t t;
+            const uint32_t S = an_stem(aw, pos & 3u, len, &t);
+            /* the stem's last 8 letters against the token's: S <= len is all this relies on */
+            uint64_t x = (t ^ an_tail8(aw, pos & 3u, S)) & ~an_low(S < 8u ? 64u - 8u * S : 0u);
+            if (S < len) an_mark(s_blank, pos + S, pos + len);
+            nstem += (pos >= AN_HALO && (S < len || x)) ? 1u : 0u;
+            for (; x; x &= ~(0xFFull << (8u * ((uint32_t)__builtin_ctzll(x) >> 3)))) {
+                const uint32_t j = (uint32_t)__builtin_ctzll(x) >> 3, p = pos + S - 8u + j;   /* byte j of t is letter S - 8 + j */
+                s_patch[p] = (uint8_t)(t >> (8u * j));
+                atomicOr(&s_pm[p >> 5], 1u << (p & 31u));
+            }
         }
     }
     return nblank;
 }
 
-__global__ __launch_bounds__(NT, 8) void k_an_filter(const AnArgs a, uint64_t ntiles) {
-    extern __shared__ __attribute__((aligned(16))) uint32_t s_tab[];
+template <bool STEM>
+__global__ __launch_bounds__(NT, STEM ? 4 : 8) void k_an_filter(const AnArgs a, uint64_t ntiles) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t s_tab[];   /* with STEM: s_patch and s_pm behind the table */
     __shared__ __attribute__((aligned(16))) uint32_t s_buf[NG * 4u];
     __shared__ __attribute__((aligned(16))) uint32_t s_tk[BM_WORDS], s_cont[BM_WORDS], s_blank[BM_WORDS];
     __shared__ uint32_t s_red[NT / 64];
     const uint32_t tid = threadIdx.x;
     for (uint32_t i = tid; i < a.tab_bytes / 16u; i += NT) ((uint4*)s_tab)[i] = gload((const uint4*)a.tab + i);
     if (tid < BM_WORDS) s_blank[tid] = 0u;
+    uint8_t* s_patch = (uint8_t*)s_tab + a.tab_bytes;   /* NG * 16 bytes: a byte per held byte */
+    uint32_t* s_pm = (uint32_t*)(s_patch + NG * 16u);   /* BM_WORDS: the bytes of s_patch that count */
+    if (STEM && tid < BM_WORDS) s_pm[tid] = 0u;
     __syncthreads();
     const uint32_t nslots = s_tab[0];
     const uint32_t* slots = s_tab + AN_HDR_WORDS;
     const uint32_t* words = s_tab + s_tab[2] / 4u;
     const uint32_t phase = (uint32_t)((uintptr_t)a.in & 15u);
     const uint32_t hgi = tid < HG ? tid : HG + NT + (tid - HG);   /* lanes 0..2 HG - 1: a halo group too */
-    uint32_t nblank = 0;
+    uint32_t nblank = 0, nstem = 0;
     /* no barrier between steps: after the second barrier a lane reads only its own group of
      * s_buf and its own 16 bits of s_blank (which it clears for the next step; the halo groups'
      * bits are set but never read), and the next step's first phase rewrites both from that
-     * lane alone */
+     * lane alone.  The same holds for s_patch and s_pm: after the second barrier a lane reads
+     * its own group and its own 16 bits of them and clears the bits, the next step's first phase
+     * touches neither, and other lanes write them again only behind the next step's first
+     * barrier, which this lane reaches after its reads. */
     for (uint64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
         const long long p0 = (long long)(tile * AN_TILE) - (long long)AN_HALO;
         const Group gm = an_stage(a, p0, HG + tid, phase, s_buf, s_tk, s_cont);
         Group gh{0u, 0u};
         if (tid < 2u * HG) gh = an_stage(a, p0, hgi, phase, s_buf, s_tk, s_cont);
         __syncthreads();
-        nblank += an_filter(a, HG + tid, gm, s_buf, s_tk, s_cont, s_blank, slots, nslots, words);
-        if (tid < HG) nblank += an_filter(a, tid, gh, s_buf, s_tk, s_cont, s_blank, slots, nslots, words);
+        nblank += an_filter<STEM>(a, HG + tid, gm, s_buf, s_tk, s_cont, s_blank, slots, nslots, words, s_patch, s_pm, nstem);
+        if (tid < HG) nblank += an_filter<STEM>(a, tid, gh, s_buf, s_tk, s_cont, s_blank, slots, nslots, words, s_patch, s_pm, nstem);
         __syncthreads();
         uint4 v = *(const uint4*)(s_buf + (HG + tid) * 4u);
+        if (STEM) {
+            const uint32_t pm = ((uint16_t*)s_pm)[HG + tid];
+            if (pm) {
+                ((uint16_t*)s_pm)[HG + tid] = 0u;
+                const uint4 pv = *(const uint4*)(s_patch + (HG + tid) * 16u);
+                uint32_t w[4] = {v.x, v.y, v.z, v.w};
+                const uint32_t pw[4] = {pv.x, pv.y, pv.z, pv.w};
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const uint32_t bm = expand4(pm >> (4 * k));
+                    w[k] = (w[k] & ~bm) | (pw[k] & bm);
+                }
+                v = make_uint4(w[0], w[1], w[2], w[3]);
+            }
+        }
         const uint32_t bl = ((uint16_t*)s_blank)[HG + tid];
         if (bl) {
             ((uint16_t*)s_blank)[HG + tid] = 0u;
@@ -264,6 +318,17 @@ __global__ __launch_bounds__(NT, 8) void k_an_filter(const AnArgs a, uint64_t nt
         for (int k = 0; k < NT / 64; ++k) tot += s_red[k];
         if (tot) (void)gatomic_add(a.blanked, (unsigned long long)tot);
     }
+    if (STEM) {
+        __syncthreads();
+        const uint32_t ssum = wave_sum(nstem);
+        if ((tid & 63u) == 0u) s_red[tid >> 6] = ssum;
+        __syncthreads();
+        if (tid == 0) {
+            uint32_t tot = 0;
+            for (int k = 0; k < NT / 64; ++k) tot += s_red[k];
+            if (tot) (void)gatomic_add(a.blanked + 1, (unsigned long long)tot);
+        }
+    }
 }
 
 }  // namespace
@@ -276,10 +341,12 @@ int launch_an_docstarts(const AnArgs& a, hipStream_t s) {
 }
 
 uint32_t an_lds_bytes(const AnArgs& a, uint32_t nstop) {
+    if (a.stemmer) return a.tab_bytes + AN_STATIC_LDS + AN_STEM_LDS;   /* the pure byte map cannot stem */
     return (nstop == 0u && a.min_len <= 1u) ? 0u : a.tab_bytes + AN_STATIC_LDS;
 }
 
-int launch_analyze(const AnArgs& a, uint32_t nstop, uint32_t ncu, hipStream_t s) {
+int launch_analyze(const AnArgs& a, uint32_t nstop, uint32_t ncu, uint32_t grid_cap, uint32_t* grid, hipStream_t s) {
+    *grid = 0u;
     if (!a.nbytes) return 0;
     const uint32_t lds = an_lds_bytes(a, nstop);
     if (!lds) {
@@ -290,8 +357,12 @@ int launch_analyze(const AnArgs& a, uint32_t nstop, uint32_t ncu, hipStream_t s)
     }
     const uint64_t ntiles = (a.nbytes + AN_TILE - 1u) / AN_TILE;
     uint32_t per_cu = 163840u / lds;   /* LDS of a CU; 2048 lanes of a CU are eight workgroups */
-    per_cu = per_cu > 8u ? 8u : (per_cu ? per_cu : 1u);
-    const uint64_t slots = (uint64_t)(ncu ? ncu : 256u) * per_cu;
-    k_an_filter<<<(unsigned)(ntiles < slots ? ntiles : slots), NT, a.tab_bytes, s>>>(a, ntiles);
+    const uint32_t fit = a.stemmer ? 6u : 8u;   /* the stemming instantiation holds 74 VGPRs: six waves per SIMD */
+    per_cu = per_cu > fit ? fit : (per_cu ? per_cu : 1u);
+    uint64_t slots = (uint64_t)(ncu ? ncu : 256u) * per_cu;
+    if (grid_cap && grid_cap < slots) slots = grid_cap;
+    *grid = (uint32_t)(ntiles < slots ? ntiles : slots);
+    if (a.stemmer) k_an_filter<true><<<*grid, NT, a.tab_bytes + AN_STEM_LDS, s>>>(a, ntiles);
+    else k_an_filter<false><<<*grid, NT, a.tab_bytes, s>>>(a, ntiles);
     return ok();
 }

@@ -1,8 +1,9 @@
 /*
  * analyze_host.c — the analyzer on the host (include/tfidf.h, section "analyzer"): the check
  * of a tfidf_analyzer, the build of its stop-word table (analyze_tab.h: the blob the device
- * kernel copies into LDS) and tfidf_analyze_host, the definition in plain C.  No HIP here: the
- * file also links into a stand-alone test program.
+ * kernel copies into LDS), tfidf_stem_porter, the Porter stemmer byte by byte, and
+ * tfidf_analyze_host, the definition in plain C.  No HIP here: the file also links into a
+ * stand-alone test program.
  */
 #include <stdlib.h>
 #include <string.h>
@@ -15,6 +16,7 @@ int tfidf_analyzer_check(const tfidf_analyzer* an) {
     if (an->flags & ~(TFIDF_AN_LOWER | TFIDF_AN_PUNCT)) return TFIDF_E_INVAL;
     if (an->min_len > TFIDF_AN_MAX_WORD) return TFIDF_E_INVAL;
     if (an->nstop > TFIDF_AN_MAX_STOP) return TFIDF_E_INVAL;
+    if (an->stemmer > TFIDF_STEM_PORTER) return TFIDF_E_INVAL;
     if (!an->nstop) return TFIDF_OK;
     if (!an->stop_bytes || !an->stop_off) return TFIDF_E_INVAL;
     const uint64_t base = an->stop_off[0];
@@ -78,6 +80,144 @@ uint32_t tfidf_an_table_build(const tfidf_analyzer* an, uint32_t* blob) {
     return total;
 }
 
+/* ------------------------------------------------------------ Porter 1980 ----
+ * The paper's rules on a word b[0, n), one byte at a time: the second opinion on the kernel's
+ * bit-mask form (analyze_stem.h).  A step works on (b, n) and returns the new n. */
+
+/* b[i] is a consonant: a letter other than a, e, i, o, u and other than a y behind a consonant */
+static int st_cons(const uint8_t* b, uint32_t i) {
+    switch (b[i]) {
+        case 'a': case 'e': case 'i': case 'o': case 'u': return 0;
+        case 'y': return i == 0 || !st_cons(b, i - 1u);
+        default: return 1;
+    }
+}
+
+/* m of b[0, n) = [C](VC)^m[V] */
+static uint32_t st_m(const uint8_t* b, uint32_t n) {
+    uint32_t m = 0;
+    for (uint32_t i = 1; i < n; ++i) m += st_cons(b, i) && !st_cons(b, i - 1u);
+    return m;
+}
+
+/* *v*: b[0, n) contains a vowel */
+static int st_vowel(const uint8_t* b, uint32_t n) {
+    for (uint32_t i = 0; i < n; ++i)
+        if (!st_cons(b, i)) return 1;
+    return 0;
+}
+
+/* *d: b[0, n) ends in a double consonant */
+static int st_double(const uint8_t* b, uint32_t n) { return n >= 2u && b[n - 1u] == b[n - 2u] && st_cons(b, n - 1u); }
+
+/* *o: b[0, n) ends consonant, vowel, consonant and the last is not w, x or y */
+static int st_cvc(const uint8_t* b, uint32_t n) {
+    if (n < 3u || !st_cons(b, n - 3u) || st_cons(b, n - 2u) || !st_cons(b, n - 1u)) return 0;
+    return b[n - 1u] != 'w' && b[n - 1u] != 'x' && b[n - 1u] != 'y';
+}
+
+static int st_ends(const uint8_t* b, uint32_t n, const char* s) {
+    const uint32_t k = (uint32_t)strlen(s);
+    return k <= n && !memcmp(b + n - k, s, k);
+}
+
+/* b[0, stem) followed by r */
+static uint32_t st_set(uint8_t* b, uint32_t stem, const char* r) {
+    const uint32_t k = (uint32_t)strlen(r);
+    memcpy(b + stem, r, k);
+    return stem + k;
+}
+
+typedef struct { const char *suffix, *to; } st_rule;
+
+/* the longest suffix of the list that b[0, n) ends in, or NULL */
+static const st_rule* st_longest(const uint8_t* b, uint32_t n, const st_rule* rules, uint32_t nrules) {
+    const st_rule* best = NULL;
+    for (uint32_t i = 0; i < nrules; ++i)
+        if (st_ends(b, n, rules[i].suffix) && (!best || strlen(rules[i].suffix) > strlen(best->suffix))) best = rules + i;
+    return best;
+}
+
+static uint32_t st_step1a(uint8_t* b, uint32_t n) {
+    if (st_ends(b, n, "sses") || st_ends(b, n, "ies")) return n - 2u;
+    if (st_ends(b, n, "ss")) return n;
+    return st_ends(b, n, "s") ? n - 1u : n;
+}
+
+static uint32_t st_step1b(uint8_t* b, uint32_t n) {
+    if (st_ends(b, n, "eed")) return st_m(b, n - 3u) > 0 ? n - 1u : n;
+    uint32_t stem;
+    if (st_ends(b, n, "ed")) stem = n - 2u;
+    else if (st_ends(b, n, "ing")) stem = n - 3u;
+    else return n;
+    if (!st_vowel(b, stem)) return n;
+    if (st_ends(b, stem, "at") || st_ends(b, stem, "bl") || st_ends(b, stem, "iz")) return st_set(b, stem, "e");
+    if (st_double(b, stem) && b[stem - 1u] != 'l' && b[stem - 1u] != 's' && b[stem - 1u] != 'z') return stem - 1u;
+    if (st_m(b, stem) == 1u && st_cvc(b, stem)) return st_set(b, stem, "e");
+    return stem;
+}
+
+static uint32_t st_step1c(uint8_t* b, uint32_t n) {
+    if (st_ends(b, n, "y") && st_vowel(b, n - 1u)) b[n - 1u] = 'i';
+    return n;
+}
+
+static const st_rule ST_STEP2[] = {
+    {"ational", "ate"}, {"tional", "tion"}, {"enci", "ence"}, {"anci", "ance"}, {"izer", "ize"}, {"abli", "able"},
+    {"alli", "al"}, {"entli", "ent"}, {"eli", "e"}, {"ousli", "ous"}, {"ization", "ize"}, {"ation", "ate"},
+    {"ator", "ate"}, {"alism", "al"}, {"iveness", "ive"}, {"fulness", "ful"}, {"ousness", "ous"}, {"aliti", "al"},
+    {"iviti", "ive"}, {"biliti", "ble"}};
+static const st_rule ST_STEP3[] = {{"icate", "ic"}, {"ative", ""}, {"alize", "al"}, {"iciti", "ic"},
+                                   {"ical", "ic"},  {"ful", ""},   {"ness", ""}};
+static const st_rule ST_STEP4[] = {{"al", ""},  {"ance", ""}, {"ence", ""}, {"er", ""},  {"ic", ""},  {"able", ""}, {"ible", ""},
+                                   {"ant", ""}, {"ement", ""}, {"ment", ""}, {"ent", ""}, {"ion", ""}, {"ou", ""},   {"ism", ""},
+                                   {"ate", ""}, {"iti", ""},  {"ous", ""},  {"ive", ""}, {"ize", ""}};
+#define ST_COUNT(a) ((uint32_t)(sizeof(a) / sizeof((a)[0])))
+
+/* steps 2 to 4: the longest suffix of the list, replaced when m of the stem in front of it is > min_m */
+static uint32_t st_replace(uint8_t* b, uint32_t n, const st_rule* rules, uint32_t nrules, uint32_t min_m) {
+    const st_rule* r = st_longest(b, n, rules, nrules);
+    if (!r) return n;
+    const uint32_t stem = n - (uint32_t)strlen(r->suffix);
+    if (st_m(b, stem) <= min_m) return n;
+    if (!strcmp(r->suffix, "ion") && min_m == 1u && !(stem && (b[stem - 1u] == 's' || b[stem - 1u] == 't'))) return n;
+    return st_set(b, stem, r->to);
+}
+
+static uint32_t st_step5a(uint8_t* b, uint32_t n) {
+    if (!st_ends(b, n, "e")) return n;
+    const uint32_t m = st_m(b, n - 1u);
+    return (m > 1u || (m == 1u && !st_cvc(b, n - 1u))) ? n - 1u : n;
+}
+
+static uint32_t st_step5b(uint8_t* b, uint32_t n) {
+    return (st_m(b, n) > 1u && st_double(b, n) && b[n - 1u] == 'l') ? n - 1u : n;
+}
+
+int tfidf_stem_porter(uint8_t* word, uint32_t len) {
+    if (!word) return len ? TFIDF_E_INVAL : 0;
+    if (len < 3u || len > TFIDF_AN_MAX_WORD) return (int)len;
+    for (uint32_t i = 0; i < len; ++i)
+        if (word[i] < 0x61u || word[i] > 0x7Au) return (int)len;
+    uint8_t b[TFIDF_AN_MAX_WORD + 1u];   /* step 1b may append an e to a shortened word: never past len */
+    memcpy(b, word, len);
+    uint32_t n = len;
+    n = st_step1a(b, n);
+    n = st_step1b(b, n);
+    n = st_step1c(b, n);
+    n = st_replace(b, n, ST_STEP2, ST_COUNT(ST_STEP2), 0u);
+    n = st_replace(b, n, ST_STEP3, ST_COUNT(ST_STEP3), 0u);
+    n = st_replace(b, n, ST_STEP4, ST_COUNT(ST_STEP4), 1u);
+    n = st_step5a(b, n);
+    n = st_step5b(b, n);
+    /* 1 <= n <= len by the rules: no replacement is longer than its suffix, 1b's e follows a
+     * removal of two or more letters, and every removal leaves a vowel (1b), m > 0 (2 to 5) or,
+     * in 1a with len >= 3, a letter.  The check guards the copy all the same. */
+    if (n < 1u || n > len) return TFIDF_E_INVAL;
+    memcpy(word, b, n);
+    return (int)n;
+}
+
 int tfidf_analyze_host(const tfidf_analyzer* an, const uint8_t* bytes, uint64_t nbytes, const uint64_t* off, uint32_t n,
                        uint8_t* out) {
     const int rc = tfidf_analyzer_check(an);
@@ -125,6 +265,11 @@ int tfidf_analyze_host(const tfidf_analyzer* an, const uint8_t* bytes, uint64_t 
                     blank = an_tab_find(slots, nslots, words, aw, 0u, (uint32_t)len, an_hash(aw, 0u, (uint32_t)len));
                 }
                 if (blank) memset(out + i, 0x20, (size_t)len);
+                else if (an->stemmer == TFIDF_STEM_PORTER) {
+                    const int st = tfidf_stem_porter(out + i, (uint32_t)len);   /* ineligible: len, nothing written */
+                    if (st < 0) { free(blob); return st; }
+                    memset(out + i + st, 0x20, (size_t)(len - (uint64_t)st));
+                }
             }
             i = j;
         }

@@ -275,6 +275,7 @@ struct tfidf_ctx {
     DevBuf km_C, km_work, km_top, km_words;
     uint64_t kmeans_bytes = 1024ull << 20;      /* env TFIDF_KMEANS_MB: budget of km_C + km_work */
     uint32_t kmeans_split = 0;                  /* env TFIDF_KMEANS_SPLIT: update workgroups per cluster (0: fill the GPU) */
+    uint32_t an_grid = 0;                       /* env TFIDF_AN_GRID: at most that many workgroups of the analyzer's tile kernel (0: the resident ones) */
     hipEvent_t ev_k[4] = {};                    /* assign / update / top-term bounds (created by the first call) */
     tfidf_kmeans_info kinfo{};
     /* unseen documents against the resident model (tfidf_transform, transform.hip): a host
@@ -503,6 +504,11 @@ int tfidf_open(int device, tfidf_ctx** out) {
     if (kks) {
         const unsigned long sp = strtoul(kks, nullptr, 0);
         if (sp >= 1 && sp <= 1024) ctx->kmeans_split = (uint32_t)sp;
+    }
+    const char* kag = getenv("TFIDF_AN_GRID");
+    if (kag) {
+        const unsigned long ag = strtoul(kag, nullptr, 0);
+        if (ag >= 1 && ag <= 65536) ctx->an_grid = (uint32_t)ag;
     }
     const char* kn = getenv("TFIDF_TEST_XNOMEM_RANK");
     ctx->xnomem_rank = kn ? atoi(kn) : -1;
@@ -3242,7 +3248,7 @@ extern "C" int tfidf_analyze(tfidf_ctx* ctx, const tfidf_analyzer* an, const tfi
     ENSURE(ctx->an_tab, tab_bytes);
     ENSURE(ctx->an_cnt, 256);
     HIPCHK(hipMemcpyAsync(ctx->an_tab.p, blob.data(), tab_bytes, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemsetAsync(ctx->an_cnt.p, 0, 8, s));
+    HIPCHK(hipMemsetAsync(ctx->an_cnt.p, 0, 16, s));
 
     AnArgs a{};
     a.in = d_in;
@@ -3257,19 +3263,21 @@ extern "C" int tfidf_analyze(tfidf_ctx* ctx, const tfidf_analyzer* an, const tfi
     a.tab = ctx->an_tab.as<uint32_t>();
     a.tab_bytes = tab_bytes;
     a.blanked = ctx->an_cnt.as<unsigned long long>();
+    a.stemmer = an->stemmer;
     const uint32_t lds = an_lds_bytes(a, an->nstop);
     if (lds) {
         ENSURE(ctx->an_dstart, (size_t)(in.nbytes / 32u + 2u) * 4u);
         a.dstart = ctx->an_dstart.as<uint32_t>();
     }
     HIPCHK(hipEventRecord(ctx->ev_an[0], s));
-    if ((lds && launch_an_docstarts(a, s)) || launch_analyze(a, an->nstop, ctx->ncu, s)) {
+    uint32_t grid = 0;
+    if ((lds && launch_an_docstarts(a, s)) || launch_analyze(a, an->nstop, ctx->ncu, ctx->an_grid, &grid, s)) {
         HIPCHK(hipGetLastError());
         return TFIDF_E_HIP;
     }
     HIPCHK(hipEventRecord(ctx->ev_an[1], s));
-    unsigned long long blanked = 0;
-    HIPCHK(hipMemcpyAsync(&blanked, ctx->an_cnt.p, 8, hipMemcpyDeviceToHost, s));
+    unsigned long long counts[2] = {0, 0};   /* tokens blanked, tokens stemmed */
+    HIPCHK(hipMemcpyAsync(counts, ctx->an_cnt.p, 16, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
 
     out->bytes = a.out;
@@ -3287,7 +3295,9 @@ extern "C" int tfidf_analyze(tfidf_ctx* ctx, const tfidf_analyzer* an, const tfi
     ai.table_slots = blob[0];
     ai.lds_bytes = lds;
     ai.tile_bytes = AN_TILE;
-    ai.blanked_tokens = blanked;
+    ai.grid = grid;
+    ai.blanked_tokens = counts[0];
+    ai.stemmed_tokens = counts[1];
     float ms = 0;
     (void)hipEventElapsedTime(&ms, ctx->ev_an[0], ctx->ev_an[1]);
     ai.ms_kernel = ms;

@@ -768,12 +768,15 @@ struct AnArgs {
     uint32_t* dstart;            /* nbytes / 32 + 2 words */
     const uint32_t* tab;
     uint32_t tab_bytes;
-    unsigned long long* blanked; /* zeroed by the caller */
+    unsigned long long* blanked; /* two counters zeroed by the caller: tokens blanked, tokens stemmed */
+    uint32_t stemmer;            /* TFIDF_STEM_*: != 0 selects the stemming instantiation of the tile kernel */
 };
 /* zeroes dstart and sets the documents' start bits */
 int launch_an_docstarts(const AnArgs& a, hipStream_t s);
-/* LDS of a workgroup of the filtering form; 0: the call is a pure byte map */
+/* LDS of a workgroup of the filtering form; 0: the call is a pure byte map (never with a stemmer) */
 uint32_t an_lds_bytes(const AnArgs& a, uint32_t nstop);
-int launch_analyze(const AnArgs& a, uint32_t nstop, uint32_t ncu, hipStream_t s);
+/* grid_cap: at most that many persistent workgroups of the tile kernel (0: the resident ones);
+ * *grid receives the workgroups launched (0: the byte map, or no bytes) */
+int launch_analyze(const AnArgs& a, uint32_t nstop, uint32_t ncu, uint32_t grid_cap, uint32_t* grid, hipStream_t s);
 
 #endif

@@ -97,7 +97,12 @@
  *   --stopwords FILE       the words of FILE (split at separators, passed through the same
  *                          --lower / --strip-punct first, so "The" in the file works with
  *                          --lower) are blanked; at most TFIDF_AN_MAX_STOP words.
- * With any of the four, input/ is analyzed in HBM between ingest and run (every shard on its own
+ *   --stem                 the tokens that are left, when they are 3..64 lower-case ASCII
+ *                          letters, are replaced by their Porter stems (TFIDF_STEM_PORTER).  It
+ *                          does not imply --lower: "Running" stays without it.  The words of
+ *                          --stopwords FILE are not stemmed: they are compared with the
+ *                          unstemmed tokens.
+ * With any of the five, input/ is analyzed in HBM between ingest and run (every shard on its own
  * GPU), and the lines of --query FILE and the documents of --transform DIR pass through the same
  * analyzer on the host, also under --model FILE.  The model file does not record the analyzer:
  * whoever serves from it passes the same flags again.  Without any of them nothing new is
@@ -164,8 +169,9 @@ static int load_stopwords(void) {
         if (n == cap) { cap *= 2; b = (uint8_t*)realloc(b, cap); }
     }
     fclose(f);
-    tfidf_analyzer map = g_an.an;   /* the same flags, no list, every token kept */
+    tfidf_analyzer map = g_an.an;   /* the same flags, no list, every token kept, no stemmer */
     map.min_len = 0;
+    map.stemmer = TFIDF_STEM_NONE;
     const uint64_t whole[2] = {0, n};
     int rc = tfidf_analyze_host(&map, b, n, whole, 1, b);
     uint64_t* off = (uint64_t*)malloc(((size_t)TFIDF_AN_MAX_STOP + 1) * sizeof(uint64_t));
@@ -701,6 +707,7 @@ int main(int argc, char** argv) {
         }
         else if (!strcmp(argv[i], "--lower")) { g_an.an.flags |= TFIDF_AN_LOWER; g_an.on = 1; }
         else if (!strcmp(argv[i], "--strip-punct")) { g_an.an.flags |= TFIDF_AN_PUNCT; g_an.on = 1; }
+        else if (!strcmp(argv[i], "--stem")) { g_an.an.stemmer = TFIDF_STEM_PORTER; g_an.on = 1; }
         else if (!strcmp(argv[i], "--stopwords") && i + 1 < argc) { g_an.stopfile = argv[++i]; g_an.on = 1; }
         else if (!strcmp(argv[i], "--min-token") && i + 1 < argc) {
             const long v = atol(argv[++i]);
@@ -743,16 +750,18 @@ int main(int argc, char** argv) {
                             "[--similar K [--similar-docs FILE] [--similar-file FILE]] "
                             "[--clusters K [--clusters-iter I] [--clusters-seeds FILE] [--clusters-terms T] [--clusters-file FILE]] "
                             "[--transform DIR [--transform-file FILE]] [--save-model FILE] "
-                            "[--lower] [--strip-punct] [--min-token N] [--stopwords FILE]\n"
+                            "[--lower] [--strip-punct] [--min-token N] [--stopwords FILE] [--stem]\n"
                             "       tfidf --model FILE --transform DIR [--transform-file FILE] [--device D] "
-                            "[--lower] [--strip-punct] [--min-token N] [--stopwords FILE]\n"
+                            "[--lower] [--strip-punct] [--min-token N] [--stopwords FILE] [--stem]\n"
                             "  --similar K without --similar-docs searches for every document: "
                             "ceil(N / group) scans of the scored pairs, group <= 64\n"
                             "  --save-model FILE writes the run's term table, df and N; --model FILE scores "
                             "--transform DIR against such a file without input/ or output.txt\n"
-                            "  --lower, --strip-punct, --min-token N and --stopwords FILE analyze input/, the query "
-                            "lines and the --transform documents before they are counted; the model file does not "
-                            "record them\n");
+                            "  --lower, --strip-punct, --min-token N, --stopwords FILE and --stem analyze input/, the "
+                            "query lines and the --transform documents before they are counted; the model file does "
+                            "not record them\n"
+                            "  --stem replaces tokens of 3..64 lower-case ASCII letters by their Porter stems; it does "
+                            "not imply --lower, and the words of --stopwords FILE are not stemmed\n");
             return 2;
         }
     }

@@ -47,6 +47,7 @@ EXPORTS = [
     "tfidf_model_check", "tfidf_model_export", "tfidf_group_model_export", "tfidf_model_import",
     "tfidf_model_save", "tfidf_model_load", "tfidf_model_free", "tfidf_last_model_info",
     "tfidf_analyzer_check", "tfidf_analyze_host", "tfidf_analyze", "tfidf_last_analyze_info",
+    "tfidf_stem_porter",
 ]
 QUERY_MAX_K = 1024  # TFIDF_QUERY_MAX_K
 TERMS_MAX_K = 1024  # TFIDF_TERMS_MAX_K
@@ -64,6 +65,8 @@ E_OUTPUT = -8
 E_MODEL = -12
 AN_LOWER = 1  # TFIDF_AN_LOWER
 AN_PUNCT = 2  # TFIDF_AN_PUNCT
+STEM_NONE = 0  # TFIDF_STEM_NONE
+STEM_PORTER = 1  # TFIDF_STEM_PORTER
 AN_MAX_WORD = 64  # TFIDF_AN_MAX_WORD
 AN_MAX_STOP = 4096  # TFIDF_AN_MAX_STOP
 AN_MAX_STOP_BYTES = 32768  # TFIDF_AN_MAX_STOP_BYTES
@@ -237,15 +240,16 @@ class ModelInfo(C.Structure):
 class Analyzer(C.Structure):
     _fields_ = [
         ("size", C.c_uint64), ("flags", C.c_uint32), ("min_len", C.c_uint32), ("stop_bytes", C.c_void_p),
-        ("stop_off", C.c_void_p), ("nstop", C.c_uint32), ("reserved", C.c_uint32),
+        ("stop_off", C.c_void_p), ("nstop", C.c_uint32), ("stemmer", C.c_uint32),
     ]
 
 
 class AnalyzeInfo(C.Structure):
     _fields_ = [
         ("size", C.c_uint64), ("nbytes", C.c_uint64), ("ndocs", C.c_uint32), ("nstop", C.c_uint32),
-        ("table_slots", C.c_uint32), ("lds_bytes", C.c_uint32), ("tile_bytes", C.c_uint32), ("reserved", C.c_uint32),
+        ("table_slots", C.c_uint32), ("lds_bytes", C.c_uint32), ("tile_bytes", C.c_uint32), ("grid", C.c_uint32),
         ("blanked_tokens", C.c_uint64), ("ms_kernel", C.c_double), ("ms_total", C.c_double),
+        ("stemmed_tokens", C.c_uint64),
     ]
 
 
@@ -355,6 +359,7 @@ def lib() -> C.CDLL:
         L.tfidf_last_model_info.argtypes = [C.c_void_p, C.POINTER(ModelInfo)]
         L.tfidf_analyzer_check.argtypes = [C.POINTER(Analyzer)]
         L.tfidf_analyze_host.argtypes = [C.POINTER(Analyzer), C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p]
+        L.tfidf_stem_porter.argtypes = [C.c_void_p, C.c_uint32]
         L.tfidf_analyze.argtypes = [C.c_void_p, C.POINTER(Analyzer), C.POINTER(Corpus), C.c_uint32, C.POINTER(Corpus)]
         L.tfidf_last_analyze_info.argtypes = [C.c_void_p, C.POINTER(AnalyzeInfo)]
         if L.tfidf_abi_version() != ABI_VERSION:
@@ -580,8 +585,9 @@ def model_load(path: str) -> dict:
         lib().tfidf_model_free(C.byref(m))
 
 
-def analyzer(lower: bool = False, punct: bool = False, min_len: int = 0, stop=()):
-    """A tfidf_analyzer over a list of stop words (bytes objects, already folded); returns
+def analyzer(lower: bool = False, punct: bool = False, min_len: int = 0, stop=(), stem: bool = False):
+    """A tfidf_analyzer over a list of stop words (bytes objects, already folded; they are
+    compared with the unstemmed tokens), with the Porter stemmer when `stem`; returns
     (struct, arrays to keep alive)."""
     stop = [bytes(w) for w in stop]
     sb = np.frombuffer(b"".join(stop), dtype=np.uint8)
@@ -595,6 +601,7 @@ def analyzer(lower: bool = False, punct: bool = False, min_len: int = 0, stop=()
     a.stop_bytes = sb.ctypes.data if len(sb) else None
     a.stop_off = so.ctypes.data if stop else None
     a.nstop = len(stop)
+    a.stemmer = STEM_PORTER if stem else STEM_NONE
     return a, (sb, so)
 
 
@@ -603,10 +610,21 @@ def analyzer_check(a: Analyzer) -> int:
     return int(lib().tfidf_analyzer_check(C.byref(a)))
 
 
-def analyze_host(data, off, lower: bool = False, punct: bool = False, min_len: int = 0, stop=(), in_place: bool = False):
+def stem_porter(word: bytes) -> bytes:
+    """tfidf_stem_porter (host only): the Porter stem of one word; an ineligible word (shorter
+    than 3 or longer than 64 bytes, a byte outside a..z) is returned as it is."""
+    buf = np.frombuffer(bytes(word), dtype=np.uint8).copy()
+    n = int(lib().tfidf_stem_porter(buf.ctypes.data if len(buf) else None, len(buf)))
+    if n < 0:
+        _chk(n, "tfidf_stem_porter")
+    return bytes(buf[:n])
+
+
+def analyze_host(data, off, lower: bool = False, punct: bool = False, min_len: int = 0, stop=(), in_place: bool = False,
+                 stem: bool = False):
     """tfidf_analyze_host (host only): the analyzed bytes of the documents data[off[i]:off[i + 1]]
     as a new array (in_place: computed in a copy that is both input and output)."""
-    a, keep = analyzer(lower, punct, min_len, stop)
+    a, keep = analyzer(lower, punct, min_len, stop, stem)
     data = np.ascontiguousarray(data, dtype=np.uint8)
     off = np.ascontiguousarray(off, dtype=np.uint64)
     out = data.copy() if in_place else np.empty(len(data), dtype=np.uint8)
@@ -901,11 +919,11 @@ class Engine:
         return {k: getattr(t, k) for k, _ in TransformInfo._fields_ if k != "size"}
 
     def analyze(self, corpus, off=None, lower: bool = False, punct: bool = False, min_len: int = 0, stop=(),
-                slot: int = AN_SLOT_CORPUS, doc_ids=None, ndocs_total: int = 0) -> Corpus:
+                slot: int = AN_SLOT_CORPUS, doc_ids=None, ndocs_total: int = 0, stem: bool = False) -> Corpus:
         """tfidf_analyze: corpus is a Corpus (host or device), or host bytes with their offsets
         `off`.  Returns the analyzed device Corpus in the context's slot buffers, valid until
         the next analyze with the same slot."""
-        a, keep = analyzer(lower, punct, min_len, stop)
+        a, keep = analyzer(lower, punct, min_len, stop, stem)
         if isinstance(corpus, Corpus):
             c = corpus
         else:
