@@ -847,8 +847,30 @@ int tfidf_last_model_info(const tfidf_ctx* ctx, tfidf_model_info* info);
  *                         separators {0x20,0x09..0x0D} becomes 0x20: 0x00..0x08, 0x0E..0x1F,
  *                         0x21..0x2F, 0x3A..0x40, 0x5B..0x60, 0x7B..0x7F (60 values, NUL among
  *                         them: with this flag a token equals its term)
- *        everything else is unchanged: bytes >= 0x80 (UTF-8 passes through) and the separators
- *        themselves ('\n' stays '\n')
+ *        everything else is unchanged: bytes >= 0x80 (UTF-8 passes through, unless
+ *        TFIDF_AN_UTF8 is set: 1b) and the separators themselves ('\n' stays '\n')
+ *   1b. sequence map, with TFIDF_AN_UTF8, beside the byte map.  Two tables of code points
+ *      >= U+0080, frozen at the Unicode version csrc/analyze_utf8_tab.h records (13.0.0):
+ *        FOLD    cp whose lowercase is exactly one code point L(cp) != cp with a UTF-8 form of
+ *                the same length (1342 code points; the 25 whose lowercase changes length, such
+ *                as U+0130, U+023A, U+1E9E, U+2126, U+212A, U+212B, are not in it)
+ *        BLANK   cp of general category P*, S* or Z* (8348 code points: NBSP, U+2003, the
+ *                typographic quotes and dashes, U+2026, currency signs, emoji)
+ *      A sequence is an occurrence of the bytes UTF-8(cp), cp in a table, that lies wholly
+ *      inside the document window; occurrences never overlap.  This equals decoding the document
+ *      as UTF-8 with every undecodable byte passed through.  Malformed bytes (overlong forms,
+ *      encoded surrogates, stray continuations, truncated leads) are never touched, nor is a
+ *      sequence that a document boundary, a window edge or the buffer's end cuts: shards and
+ *      batches analyze separately and must agree.
+ *        TFIDF_AN_PUNCT | TFIDF_AN_UTF8   every byte of a BLANK sequence becomes 0x20
+ *        TFIDF_AN_LOWER | TFIDF_AN_UTF8   a FOLD sequence becomes UTF-8(L(cp))
+ *      U+24B6..U+24CF are in both tables: with both flags the blank wins, as in ASCII.
+ *      TFIDF_AN_UTF8 alone is valid and changes nothing.  Cf (U+200B, U+00AD, U+FEFF), Mn
+ *      (combining marks) and Cc (C1 controls) are in neither table.  No special casing: U+03A3
+ *      always becomes U+03C3.  Steps 2 and 3 run on the mapped bytes: min_len and
+ *      TFIDF_AN_MAX_WORD count bytes, stop words are compared verbatim (the caller supplies the
+ *      folded form), and the stemmer takes tokens of a..z only.  L(L(cp)) does not exist, so the
+ *      analyzer without a stemmer stays idempotent.
  *   2. token filter, on the mapped bytes: tokens are the maximal runs of non-separator bytes
  *      inside the document (a document boundary ends a token, as for tfidf_corpus).  A token is
  *      blanked (every one of its bytes becomes 0x20) when its length in bytes is < min_len, or
@@ -901,6 +923,7 @@ int tfidf_last_model_info(const tfidf_ctx* ctx, tfidf_model_info* info);
  * whoever scores batches against a saved model passes the same analyzer again. */
 #define TFIDF_AN_LOWER 1u
 #define TFIDF_AN_PUNCT 2u
+#define TFIDF_AN_UTF8 16u                /* 4u and 8u are unknown flag bits */
 #define TFIDF_STEM_NONE   0u
 #define TFIDF_STEM_PORTER 1u
 #define TFIDF_AN_MAX_WORD 64u            /* longest stop word, largest min_len */
@@ -975,6 +998,8 @@ typedef struct tfidf_analyze_info {
     double   ms_kernel;       /* device time of the kernels (HIP events) */
     double   ms_total;        /* host wall time of the whole call */
     uint64_t stemmed_tokens;  /* tokens whose bytes the stemmer changed, counted like blanked_tokens */
+    uint64_t utf8_changed;    /* TFIDF_AN_UTF8: sequences whose bytes changed, each counted where its
+                                 first byte lies, like blanked_tokens */
 } tfidf_analyze_info;
 int tfidf_last_analyze_info(const tfidf_ctx* ctx, tfidf_analyze_info* info);
 

@@ -33,6 +33,14 @@
  *            long as well.  So no two workgroups write the same byte and the pass is out of
  *            place.  Tokens blanked are counted where they start: one integer atomic add per
  *            workgroup.
+ * With TFIDF_AN_UTF8 (and a map flag: alone it changes nothing and the kernels above run) the
+ * instantiations of their own k_an_map_u8 and k_an_filter<STEM, true> run: a group that holds a
+ * byte >= 0x80 resolves its UTF-8 sequences (analyze_utf8.h) from its own 16 bytes, the four
+ * bytes on either side of them, read from global memory again (its neighbours' loads brought
+ * them into the cache), and the document-start bitmap; every other group takes the SWAR path
+ * alone.  The tables stay in global memory.  Halo groups are staged the same way, so every byte
+ * held in LDS is sequence-mapped whatever its place in the held range.  Sequences changed are
+ * counted where they start, by the tile's own groups: one integer atomic add per workgroup.
  * The input may have any alignment: groups are cut at multiples of 16 of the OUTPUT, an
  * unaligned input is read as two aligned 16-byte loads and a byte shift, and byte by byte where
  * that would leave in[0, nbytes).
@@ -41,6 +49,7 @@
 #include "dev_common.h"
 #include "analyze_tab.h"
 #include "analyze_stem.h"
+#include "analyze_utf8.h"
 
 namespace {
 
@@ -48,6 +57,8 @@ constexpr int NT = 256;
 constexpr uint32_t HG = AN_HALO / 16u;         /* halo groups on each side */
 constexpr uint32_t NG = NT + 2u * HG;          /* groups held in LDS */
 constexpr uint32_t AN_FLAG_LOWER = 1u, AN_FLAG_PUNCT = 2u;   /* TFIDF_AN_* of include/tfidf.h */
+constexpr uint32_t AN_FLAG_UTF8 = 16u;
+static_assert(AN_FLAG_LOWER == AN_U8_LOWER && AN_FLAG_PUNCT == AN_U8_PUNCT, "analyze_utf8.h takes the map flags as they are");
 constexpr uint32_t AN_MAX_WORD = 64u;
 static_assert(AN_TILE == NT * 16u, "one 16-byte group per lane");
 static_assert(AN_HALO % 16u == 0 && AN_HALO > AN_MAX_WORD + 1u, "the halo argument");
@@ -152,6 +163,33 @@ __device__ __forceinline__ void store16(const AnArgs& a, uint64_t p, uint4 v) {
         gstore(a.out + p + j, (uint8_t)((j < 8 ? lo : hi) >> (8 * (j & 7))));
 }
 
+/* the sequence map on the group at byte p: raw are its bytes as loaded, v the byte-mapped ones,
+ * which receive the sequences' bytes.  Returns the sequences changed that start in the group.
+ * win != 0 puts a byte of the group inside [lo, hi), so 0 <= p < nbytes. */
+__device__ __forceinline__ uint32_t u8_patch(const AnArgs& a, long long p, uint4 raw, uint32_t win, uint4& v) {
+    uint32_t c[6] = {0u, raw.x, raw.y, raw.z, raw.w, 0u};
+    if (win == 0u || !an_u8_any(c + 1)) return 0u;
+    c[0] = an_u8_ld4(a.in, a.nbytes, p - 4);
+    c[5] = an_u8_ld4(a.in, a.nbytes, p + 16);
+    uint32_t g[4] = {v.x, v.y, v.z, v.w};
+    const uint32_t n = an_u8_group(c, an_u8_range24(p, a.lo, a.hi), an_u8_cut24(a.dstart, p, a.lo, a.hi),
+                                   a.flags & (AN_FLAG_LOWER | AN_FLAG_PUNCT), g);
+    v = make_uint4(g[0], g[1], g[2], g[3]);
+    return n;
+}
+
+/* the workgroup's sum of n, added to *ctr by one lane */
+__device__ __forceinline__ void an_count(uint32_t n, uint32_t* s_red, unsigned long long* ctr) {
+    const uint32_t tid = threadIdx.x, wsum = wave_sum(n);
+    if ((tid & 63u) == 0u) s_red[tid >> 6] = wsum;
+    __syncthreads();
+    if (tid == 0) {
+        uint32_t tot = 0;
+        for (int k = 0; k < NT / 64; ++k) tot += s_red[k];
+        if (tot) (void)gatomic_add(ctr, (unsigned long long)tot);
+    }
+}
+
 __global__ __launch_bounds__(NT) void k_an_docstarts(const AnArgs a) {
     const uint64_t d = (uint64_t)blockIdx.x * NT + threadIdx.x + 1u;
     if (d >= a.ndocs) return;
@@ -169,16 +207,37 @@ __global__ __launch_bounds__(NT) void k_an_map(const AnArgs a, uint64_t ngroups)
     store16(a, (uint64_t)p, map_group(v, range16(p, a.lo, a.hi), a.flags));
 }
 
+/* k_an_map with the sequence map: every lane stays for the count */
+__global__ __launch_bounds__(NT) void k_an_map_u8(const AnArgs a, uint64_t ngroups) {
+    __shared__ uint32_t s_red[NT / 64];
+    const uint64_t g = (uint64_t)blockIdx.x * NT + threadIdx.x;
+    uint32_t n = 0u;
+    if (g < ngroups) {
+        const uint32_t phase = (uint32_t)((uintptr_t)a.in & 15u);
+        const long long p = (long long)(g * 16u);
+        const uint32_t win = range16(p, a.lo, a.hi);
+        const uint4 raw = load16(a, p, phase);
+        uint4 v = map_group(raw, win, a.flags);
+        n = u8_patch(a, p, raw, win, v);
+        store16(a, (uint64_t)p, v);
+    }
+    an_count(n, s_red, a.blanked + 2);
+}
+
 struct Group {
     uint32_t tk, ds;
 };
 
-/* loads, maps and publishes group gi of the tile whose first group lies at byte p0 */
+/* loads, maps and publishes group gi of the tile whose first group lies at byte p0; with U8 the
+ * sequences too, and nu8 receives the ones changed that start in the group */
+template <bool U8>
 __device__ __forceinline__ Group an_stage(const AnArgs& a, long long p0, uint32_t gi, uint32_t phase, uint32_t* s_buf,
-                                          uint32_t* s_tk, uint32_t* s_cont) {
+                                          uint32_t* s_tk, uint32_t* s_cont, uint32_t& nu8) {
     const long long p = p0 + (long long)(gi * 16u);
     const uint32_t win = range16(p, a.lo, a.hi);
-    const uint4 v = map_group(load16(a, p, phase), win, a.flags);
+    const uint4 raw = load16(a, p, phase);
+    uint4 v = map_group(raw, win, a.flags);
+    if (U8) nu8 += u8_patch(a, p, raw, win, v);
     Group g;
     g.tk = ~ws_mask16_swar(v) & win;
     g.ds = 0u;
@@ -246,8 +305,8 @@ __device__ __forceinline__ uint32_t an_filter(const AnArgs& a, uint32_t gi, Grou
     return nblank;
 }
 
-template <bool STEM>
-__global__ __launch_bounds__(NT, STEM ? 4 : 8) void k_an_filter(const AnArgs a, uint64_t ntiles) {
+template <bool STEM, bool U8 = false>
+__global__ __launch_bounds__(NT, (STEM || U8) ? 4 : 8) void k_an_filter(const AnArgs a, uint64_t ntiles) {
     extern __shared__ __attribute__((aligned(16))) uint32_t s_tab[];   /* with STEM: s_patch and s_pm behind the table */
     __shared__ __attribute__((aligned(16))) uint32_t s_buf[NG * 4u];
     __shared__ __attribute__((aligned(16))) uint32_t s_tk[BM_WORDS], s_cont[BM_WORDS], s_blank[BM_WORDS];
@@ -264,7 +323,7 @@ __global__ __launch_bounds__(NT, STEM ? 4 : 8) void k_an_filter(const AnArgs a, 
     const uint32_t* words = s_tab + s_tab[2] / 4u;
     const uint32_t phase = (uint32_t)((uintptr_t)a.in & 15u);
     const uint32_t hgi = tid < HG ? tid : HG + NT + (tid - HG);   /* lanes 0..2 HG - 1: a halo group too */
-    uint32_t nblank = 0, nstem = 0;
+    uint32_t nblank = 0, nstem = 0, nu8 = 0, nu8_halo = 0;   /* a halo group's sequences count in its own tile */
     /* no barrier between steps: after the second barrier a lane reads only its own group of
      * s_buf and its own 16 bits of s_blank (which it clears for the next step; the halo groups'
      * bits are set but never read), and the next step's first phase rewrites both from that
@@ -274,9 +333,9 @@ __global__ __launch_bounds__(NT, STEM ? 4 : 8) void k_an_filter(const AnArgs a, 
      * barrier, which this lane reaches after its reads. */
     for (uint64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
         const long long p0 = (long long)(tile * AN_TILE) - (long long)AN_HALO;
-        const Group gm = an_stage(a, p0, HG + tid, phase, s_buf, s_tk, s_cont);
+        const Group gm = an_stage<U8>(a, p0, HG + tid, phase, s_buf, s_tk, s_cont, nu8);
         Group gh{0u, 0u};
-        if (tid < 2u * HG) gh = an_stage(a, p0, hgi, phase, s_buf, s_tk, s_cont);
+        if (tid < 2u * HG) gh = an_stage<U8>(a, p0, hgi, phase, s_buf, s_tk, s_cont, nu8_halo);
         __syncthreads();
         nblank += an_filter<STEM>(a, HG + tid, gm, s_buf, s_tk, s_cont, s_blank, slots, nslots, words, s_patch, s_pm, nstem);
         if (tid < HG) nblank += an_filter<STEM>(a, tid, gh, s_buf, s_tk, s_cont, s_blank, slots, nslots, words, s_patch, s_pm, nstem);
@@ -329,6 +388,10 @@ __global__ __launch_bounds__(NT, STEM ? 4 : 8) void k_an_filter(const AnArgs a, 
             if (tot) (void)gatomic_add(a.blanked + 1, (unsigned long long)tot);
         }
     }
+    if (U8) {
+        __syncthreads();
+        an_count(nu8, s_red, a.blanked + 2);
+    }
 }
 
 }  // namespace
@@ -349,20 +412,26 @@ int launch_analyze(const AnArgs& a, uint32_t nstop, uint32_t ncu, uint32_t grid_
     *grid = 0u;
     if (!a.nbytes) return 0;
     const uint32_t lds = an_lds_bytes(a, nstop);
+    const bool u8 = (a.flags & AN_FLAG_UTF8) != 0u;   /* the caller clears it where it changes nothing */
     if (!lds) {
         const uint64_t ngroups = (a.nbytes + 15u) / 16u, nblocks = (ngroups + NT - 1u) / NT;
         if (nblocks > 0x7FFFFFFFull) return -1;
-        k_an_map<<<(unsigned)nblocks, NT, 0, s>>>(a, ngroups);
+        if (u8) k_an_map_u8<<<(unsigned)nblocks, NT, 0, s>>>(a, ngroups);
+        else k_an_map<<<(unsigned)nblocks, NT, 0, s>>>(a, ngroups);
         return ok();
     }
     const uint64_t ntiles = (a.nbytes + AN_TILE - 1u) / AN_TILE;
     uint32_t per_cu = 163840u / lds;   /* LDS of a CU; 2048 lanes of a CU are eight workgroups */
-    const uint32_t fit = a.stemmer ? 6u : 8u;   /* the stemming instantiation holds 74 VGPRs: six waves per SIMD */
+    /* the stemming instantiation holds 74 VGPRs: six waves per SIMD; the ones with the sequence map 103 and 114: four */
+    const uint32_t fit = u8 ? 4u : (a.stemmer ? 6u : 8u);
     per_cu = per_cu > fit ? fit : (per_cu ? per_cu : 1u);
     uint64_t slots = (uint64_t)(ncu ? ncu : 256u) * per_cu;
     if (grid_cap && grid_cap < slots) slots = grid_cap;
     *grid = (uint32_t)(ntiles < slots ? ntiles : slots);
-    if (a.stemmer) k_an_filter<true><<<*grid, NT, a.tab_bytes + AN_STEM_LDS, s>>>(a, ntiles);
+    if (u8) {
+        if (a.stemmer) k_an_filter<true, true><<<*grid, NT, a.tab_bytes + AN_STEM_LDS, s>>>(a, ntiles);
+        else k_an_filter<false, true><<<*grid, NT, a.tab_bytes, s>>>(a, ntiles);
+    } else if (a.stemmer) k_an_filter<true><<<*grid, NT, a.tab_bytes + AN_STEM_LDS, s>>>(a, ntiles);
     else k_an_filter<false><<<*grid, NT, a.tab_bytes, s>>>(a, ntiles);
     return ok();
 }

@@ -1,8 +1,8 @@
 /*
  * analyze_host.c — the analyzer on the host (include/tfidf.h, section "analyzer"): the check
  * of a tfidf_analyzer, the build of its stop-word table (analyze_tab.h: the blob the device
- * kernel copies into LDS), tfidf_stem_porter, the Porter stemmer byte by byte, and
- * tfidf_analyze_host, the definition in plain C.  No HIP here: the file also links into a
+ * kernel copies into LDS), tfidf_stem_porter, the Porter stemmer byte by byte, the UTF-8
+ * sequence map of TFIDF_AN_UTF8 byte by byte, and tfidf_analyze_host, the definition in plain C.  No HIP here: the file also links into a
  * stand-alone test program.
  */
 #include <stdlib.h>
@@ -10,10 +10,12 @@
 
 #include "../../include/tfidf.h"
 #include "analyze_tab.h"
+#define AN_U8_NO_T2   /* the ranges alone: the direct table is the kernel's */
+#include "analyze_utf8_tab.h"
 
 int tfidf_analyzer_check(const tfidf_analyzer* an) {
     if (!an || an->size < sizeof(tfidf_analyzer)) return TFIDF_E_INVAL;
-    if (an->flags & ~(TFIDF_AN_LOWER | TFIDF_AN_PUNCT)) return TFIDF_E_INVAL;
+    if (an->flags & ~(TFIDF_AN_LOWER | TFIDF_AN_PUNCT | TFIDF_AN_UTF8)) return TFIDF_E_INVAL;
     if (an->min_len > TFIDF_AN_MAX_WORD) return TFIDF_E_INVAL;
     if (an->nstop > TFIDF_AN_MAX_STOP) return TFIDF_E_INVAL;
     if (an->stemmer > TFIDF_STEM_PORTER) return TFIDF_E_INVAL;
@@ -218,6 +220,75 @@ int tfidf_stem_porter(uint8_t* word, uint32_t len) {
     return (int)n;
 }
 
+/* --------------------------------------------------------- TFIDF_AN_UTF8 ----
+ * The sequence map byte by byte, with the well-formed byte ranges of the Unicode standard's
+ * table 3-7 and a linear walk over the tables: the second opinion on analyze_utf8.h. */
+
+/* the length of the well-formed sequence at s[0, avail) and its code point, or 0 */
+static uint32_t u8_seq(const uint8_t* s, uint64_t avail, uint32_t* cp) {
+    const uint32_t b0 = s[0];
+    uint32_t len, lo1 = 0x80u, hi1 = 0xBFu;
+    if (b0 >= 0xC2u && b0 <= 0xDFu) len = 2u;
+    else if (b0 >= 0xE0u && b0 <= 0xEFu) {
+        len = 3u;
+        if (b0 == 0xE0u) lo1 = 0xA0u;   /* no overlong form */
+        if (b0 == 0xEDu) hi1 = 0x9Fu;   /* no surrogate */
+    } else if (b0 >= 0xF0u && b0 <= 0xF4u) {
+        len = 4u;
+        if (b0 == 0xF0u) lo1 = 0x90u;
+        if (b0 == 0xF4u) hi1 = 0x8Fu;   /* nothing above U+10FFFF */
+    } else return 0u;
+    if (avail < len || s[1] < lo1 || s[1] > hi1) return 0u;
+    for (uint32_t k = 2; k < len; ++k)
+        if (s[k] < 0x80u || s[k] > 0xBFu) return 0u;
+    if (len == 2u) *cp = ((b0 & 0x1Fu) << 6) | (s[1] & 0x3Fu);
+    else if (len == 3u) *cp = ((b0 & 0x0Fu) << 12) | ((uint32_t)(s[1] & 0x3Fu) << 6) | (s[2] & 0x3Fu);
+    else *cp = ((b0 & 0x07u) << 18) | ((uint32_t)(s[1] & 0x3Fu) << 12) | ((uint32_t)(s[2] & 0x3Fu) << 6) | (s[3] & 0x3Fu);
+    return len;
+}
+
+static int u8_is_blank(uint32_t cp) {
+    for (uint32_t i = 0; i < AN_U8_NBLANK; ++i)
+        if (cp >= AN_U8_BLANK[i].lo && cp <= AN_U8_BLANK[i].hi) return 1;
+    return 0;
+}
+
+/* L(cp), or 0 for a code point outside FOLD */
+static uint32_t u8_lower(uint32_t cp) {
+    for (uint32_t i = 0; i < AN_U8_NFOLD; ++i) {
+        const an_u8_fold* f = AN_U8_FOLD + i;
+        if (cp >= f->lo && cp <= f->hi && (cp - f->lo) % f->stride == 0u) return (uint32_t)((int32_t)cp + f->delta);
+    }
+    return 0u;
+}
+
+/* the sequences that lie wholly inside the document s[0, n) */
+static void u8_map_doc(uint8_t* s, uint64_t n, uint32_t flags) {
+    for (uint64_t i = 0; i < n;) {
+        uint32_t cp = 0;
+        const uint32_t len = s[i] >= 0x80u ? u8_seq(s + i, n - i, &cp) : 0u;
+        if (!len) { ++i; continue; }
+        uint32_t lc;
+        if ((flags & TFIDF_AN_PUNCT) && u8_is_blank(cp)) memset(s + i, 0x20, len);
+        else if ((flags & TFIDF_AN_LOWER) && (lc = u8_lower(cp)) != 0u) {   /* the same length: FOLD's definition */
+            if (len == 2u) {
+                s[i] = (uint8_t)(0xC0u | (lc >> 6));
+                s[i + 1] = (uint8_t)(0x80u | (lc & 0x3Fu));
+            } else if (len == 3u) {
+                s[i] = (uint8_t)(0xE0u | (lc >> 12));
+                s[i + 1] = (uint8_t)(0x80u | ((lc >> 6) & 0x3Fu));
+                s[i + 2] = (uint8_t)(0x80u | (lc & 0x3Fu));
+            } else {
+                s[i] = (uint8_t)(0xF0u | (lc >> 18));
+                s[i + 1] = (uint8_t)(0x80u | ((lc >> 12) & 0x3Fu));
+                s[i + 2] = (uint8_t)(0x80u | ((lc >> 6) & 0x3Fu));
+                s[i + 3] = (uint8_t)(0x80u | (lc & 0x3Fu));
+            }
+        }
+        i += len;
+    }
+}
+
 int tfidf_analyze_host(const tfidf_analyzer* an, const uint8_t* bytes, uint64_t nbytes, const uint64_t* off, uint32_t n,
                        uint8_t* out) {
     const int rc = tfidf_analyzer_check(an);
@@ -253,6 +324,7 @@ int tfidf_analyze_host(const tfidf_analyzer* an, const uint8_t* bytes, uint64_t 
     for (uint32_t d = 0; d < n; ++d) {
         const uint64_t b = off[d], e = off[d + 1];
         for (uint64_t i = b; i < e; ++i) out[i] = map[out[i]];
+        if ((an->flags & TFIDF_AN_UTF8) && (an->flags & (TFIDF_AN_LOWER | TFIDF_AN_PUNCT))) u8_map_doc(out + b, e - b, an->flags);
         for (uint64_t i = b; i < e;) {
             if (an_is_sep(out[i])) { ++i; continue; }
             uint64_t j = i;

@@ -3248,7 +3248,7 @@ extern "C" int tfidf_analyze(tfidf_ctx* ctx, const tfidf_analyzer* an, const tfi
     ENSURE(ctx->an_tab, tab_bytes);
     ENSURE(ctx->an_cnt, 256);
     HIPCHK(hipMemcpyAsync(ctx->an_tab.p, blob.data(), tab_bytes, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemsetAsync(ctx->an_cnt.p, 0, 16, s));
+    HIPCHK(hipMemsetAsync(ctx->an_cnt.p, 0, 24, s));
 
     AnArgs a{};
     a.in = d_in;
@@ -3259,25 +3259,27 @@ extern "C" int tfidf_analyze(tfidf_ctx* ctx, const tfidf_analyzer* an, const tfi
     a.doc_off = ctx->an_off[slot].as<uint64_t>();
     a.ndocs = N;
     a.flags = an->flags;
+    if (!(a.flags & (TFIDF_AN_LOWER | TFIDF_AN_PUNCT))) a.flags &= ~TFIDF_AN_UTF8;   /* alone it changes nothing */
     a.min_len = an->min_len;
     a.tab = ctx->an_tab.as<uint32_t>();
     a.tab_bytes = tab_bytes;
     a.blanked = ctx->an_cnt.as<unsigned long long>();
     a.stemmer = an->stemmer;
     const uint32_t lds = an_lds_bytes(a, an->nstop);
-    if (lds) {
+    const bool need_dstart = lds || (a.flags & TFIDF_AN_UTF8);   /* a document boundary cuts a sequence */
+    if (need_dstart) {
         ENSURE(ctx->an_dstart, (size_t)(in.nbytes / 32u + 2u) * 4u);
         a.dstart = ctx->an_dstart.as<uint32_t>();
     }
     HIPCHK(hipEventRecord(ctx->ev_an[0], s));
     uint32_t grid = 0;
-    if ((lds && launch_an_docstarts(a, s)) || launch_analyze(a, an->nstop, ctx->ncu, ctx->an_grid, &grid, s)) {
+    if ((need_dstart && launch_an_docstarts(a, s)) || launch_analyze(a, an->nstop, ctx->ncu, ctx->an_grid, &grid, s)) {
         HIPCHK(hipGetLastError());
         return TFIDF_E_HIP;
     }
     HIPCHK(hipEventRecord(ctx->ev_an[1], s));
-    unsigned long long counts[2] = {0, 0};   /* tokens blanked, tokens stemmed */
-    HIPCHK(hipMemcpyAsync(counts, ctx->an_cnt.p, 16, hipMemcpyDeviceToHost, s));
+    unsigned long long counts[3] = {0, 0, 0};   /* tokens blanked, tokens stemmed, sequences changed */
+    HIPCHK(hipMemcpyAsync(counts, ctx->an_cnt.p, 24, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
 
     out->bytes = a.out;
@@ -3298,6 +3300,7 @@ extern "C" int tfidf_analyze(tfidf_ctx* ctx, const tfidf_analyzer* an, const tfi
     ai.grid = grid;
     ai.blanked_tokens = counts[0];
     ai.stemmed_tokens = counts[1];
+    ai.utf8_changed = counts[2];
     float ms = 0;
     (void)hipEventElapsedTime(&ms, ctx->ev_an[0], ctx->ev_an[1]);
     ai.ms_kernel = ms;

@@ -756,7 +756,9 @@ int launch_km_top(const KmTopArgs& a, hipStream_t s);
  * window, the token filter on the mapped bytes, everything else copied.  out is 16-byte
  * aligned, in has any alignment; no byte outside in[0, nbytes) is read and none outside
  * out[0, nbytes) written.  dstart: bit i = a document starts at byte i, lo < i < hi
- * (launch_an_docstarts), read by the filtering form only.  tab: the stop-word blob of
+ * (launch_an_docstarts), read by the filtering form and, with TFIDF_AN_UTF8 in flags, by the
+ * byte map too (a document boundary cuts a UTF-8 sequence).  flags holds TFIDF_AN_UTF8 only
+ * beside a map flag: alone it changes nothing and the caller clears it.  tab: the stop-word blob of
  * analyze_tab.h in device memory (a header alone when the list is empty). */
 struct AnArgs {
     const uint8_t* in;
@@ -768,7 +770,8 @@ struct AnArgs {
     uint32_t* dstart;            /* nbytes / 32 + 2 words */
     const uint32_t* tab;
     uint32_t tab_bytes;
-    unsigned long long* blanked; /* two counters zeroed by the caller: tokens blanked, tokens stemmed */
+    unsigned long long* blanked; /* three counters zeroed by the caller: tokens blanked, tokens stemmed,
+                                    UTF-8 sequences changed */
     uint32_t stemmer;            /* TFIDF_STEM_*: != 0 selects the stemming instantiation of the tile kernel */
 };
 /* zeroes dstart and sets the documents' start bits */

@@ -102,7 +102,12 @@
  *                          does not imply --lower: "Running" stays without it.  The words of
  *                          --stopwords FILE are not stemmed: they are compared with the
  *                          unstemmed tokens.
- * With any of the five, input/ is analyzed in HBM between ingest and run (every shard on its own
+ *   --utf8                 TFIDF_AN_UTF8: --lower also folds the UTF-8 sequences of cased
+ *                          letters whose lowercase has the same length, and --strip-punct also
+ *                          blanks the sequences of punctuation, symbols and separators (NBSP,
+ *                          typographic quotes and dashes, emoji).  Alone it changes nothing.  The
+ *                          words of --stopwords FILE pass through the same map.
+ * With any of the six, input/ is analyzed in HBM between ingest and run (every shard on its own
  * GPU), and the lines of --query FILE and the documents of --transform DIR pass through the same
  * analyzer on the host, also under --model FILE.  The model file does not record the analyzer:
  * whoever serves from it passes the same flags again.  Without any of them nothing new is
@@ -708,6 +713,7 @@ int main(int argc, char** argv) {
         else if (!strcmp(argv[i], "--lower")) { g_an.an.flags |= TFIDF_AN_LOWER; g_an.on = 1; }
         else if (!strcmp(argv[i], "--strip-punct")) { g_an.an.flags |= TFIDF_AN_PUNCT; g_an.on = 1; }
         else if (!strcmp(argv[i], "--stem")) { g_an.an.stemmer = TFIDF_STEM_PORTER; g_an.on = 1; }
+        else if (!strcmp(argv[i], "--utf8")) { g_an.an.flags |= TFIDF_AN_UTF8; g_an.on = 1; }
         else if (!strcmp(argv[i], "--stopwords") && i + 1 < argc) { g_an.stopfile = argv[++i]; g_an.on = 1; }
         else if (!strcmp(argv[i], "--min-token") && i + 1 < argc) {
             const long v = atol(argv[++i]);
@@ -750,9 +756,9 @@ int main(int argc, char** argv) {
                             "[--similar K [--similar-docs FILE] [--similar-file FILE]] "
                             "[--clusters K [--clusters-iter I] [--clusters-seeds FILE] [--clusters-terms T] [--clusters-file FILE]] "
                             "[--transform DIR [--transform-file FILE]] [--save-model FILE] "
-                            "[--lower] [--strip-punct] [--min-token N] [--stopwords FILE] [--stem]\n"
+                            "[--lower] [--strip-punct] [--min-token N] [--stopwords FILE] [--stem] [--utf8]\n"
                             "       tfidf --model FILE --transform DIR [--transform-file FILE] [--device D] "
-                            "[--lower] [--strip-punct] [--min-token N] [--stopwords FILE] [--stem]\n"
+                            "[--lower] [--strip-punct] [--min-token N] [--stopwords FILE] [--stem] [--utf8]\n"
                             "  --similar K without --similar-docs searches for every document: "
                             "ceil(N / group) scans of the scored pairs, group <= 64\n"
                             "  --save-model FILE writes the run's term table, df and N; --model FILE scores "
@@ -761,7 +767,9 @@ int main(int argc, char** argv) {
                             "query lines and the --transform documents before they are counted; the model file does "
                             "not record them\n"
                             "  --stem replaces tokens of 3..64 lower-case ASCII letters by their Porter stems; it does "
-                            "not imply --lower, and the words of --stopwords FILE are not stemmed\n");
+                            "not imply --lower, and the words of --stopwords FILE are not stemmed\n"
+                            "  --utf8 extends --lower and --strip-punct to UTF-8 sequences: cased letters whose lowercase "
+                            "has the same length are folded, punctuation, symbols and separators are blanked\n");
             return 2;
         }
     }

@@ -65,6 +65,7 @@ E_OUTPUT = -8
 E_MODEL = -12
 AN_LOWER = 1  # TFIDF_AN_LOWER
 AN_PUNCT = 2  # TFIDF_AN_PUNCT
+AN_UTF8 = 16  # TFIDF_AN_UTF8
 STEM_NONE = 0  # TFIDF_STEM_NONE
 STEM_PORTER = 1  # TFIDF_STEM_PORTER
 AN_MAX_WORD = 64  # TFIDF_AN_MAX_WORD
@@ -251,6 +252,12 @@ class AnalyzeInfo(C.Structure):
         ("blanked_tokens", C.c_uint64), ("ms_kernel", C.c_double), ("ms_total", C.c_double),
         ("stemmed_tokens", C.c_uint64),
     ]
+
+
+class AnalyzeInfoUtf8(AnalyzeInfo):
+    """tfidf_analyze_info as it is now.  The struct is size-prefixed: AnalyzeInfo is the layout up
+    to stemmed_tokens, which callers built before TFIDF_AN_UTF8 still pass."""
+    _fields_ = [("utf8_changed", C.c_uint64)]
 
 
 class DirPlan(C.Structure):
@@ -585,10 +592,10 @@ def model_load(path: str) -> dict:
         lib().tfidf_model_free(C.byref(m))
 
 
-def analyzer(lower: bool = False, punct: bool = False, min_len: int = 0, stop=(), stem: bool = False):
+def analyzer(lower: bool = False, punct: bool = False, min_len: int = 0, stop=(), stem: bool = False, utf8: bool = False):
     """A tfidf_analyzer over a list of stop words (bytes objects, already folded; they are
-    compared with the unstemmed tokens), with the Porter stemmer when `stem`; returns
-    (struct, arrays to keep alive)."""
+    compared with the unstemmed tokens), with the Porter stemmer when `stem` and the UTF-8
+    sequence map (TFIDF_AN_UTF8) when `utf8`; returns (struct, arrays to keep alive)."""
     stop = [bytes(w) for w in stop]
     sb = np.frombuffer(b"".join(stop), dtype=np.uint8)
     so = np.zeros(len(stop) + 1, dtype=np.uint64)
@@ -596,7 +603,7 @@ def analyzer(lower: bool = False, punct: bool = False, min_len: int = 0, stop=()
         so[1:] = np.cumsum([len(w) for w in stop], dtype=np.uint64)
     a = Analyzer()
     a.size = C.sizeof(Analyzer)
-    a.flags = (AN_LOWER if lower else 0) | (AN_PUNCT if punct else 0)
+    a.flags = (AN_LOWER if lower else 0) | (AN_PUNCT if punct else 0) | (AN_UTF8 if utf8 else 0)
     a.min_len = min_len
     a.stop_bytes = sb.ctypes.data if len(sb) else None
     a.stop_off = so.ctypes.data if stop else None
@@ -621,10 +628,10 @@ def stem_porter(word: bytes) -> bytes:
 
 
 def analyze_host(data, off, lower: bool = False, punct: bool = False, min_len: int = 0, stop=(), in_place: bool = False,
-                 stem: bool = False):
+                 stem: bool = False, utf8: bool = False):
     """tfidf_analyze_host (host only): the analyzed bytes of the documents data[off[i]:off[i + 1]]
     as a new array (in_place: computed in a copy that is both input and output)."""
-    a, keep = analyzer(lower, punct, min_len, stop, stem)
+    a, keep = analyzer(lower, punct, min_len, stop, stem, utf8)
     data = np.ascontiguousarray(data, dtype=np.uint8)
     off = np.ascontiguousarray(off, dtype=np.uint64)
     out = data.copy() if in_place else np.empty(len(data), dtype=np.uint8)
@@ -919,11 +926,12 @@ class Engine:
         return {k: getattr(t, k) for k, _ in TransformInfo._fields_ if k != "size"}
 
     def analyze(self, corpus, off=None, lower: bool = False, punct: bool = False, min_len: int = 0, stop=(),
-                slot: int = AN_SLOT_CORPUS, doc_ids=None, ndocs_total: int = 0, stem: bool = False) -> Corpus:
+                slot: int = AN_SLOT_CORPUS, doc_ids=None, ndocs_total: int = 0, stem: bool = False,
+                utf8: bool = False) -> Corpus:
         """tfidf_analyze: corpus is a Corpus (host or device), or host bytes with their offsets
         `off`.  Returns the analyzed device Corpus in the context's slot buffers, valid until
         the next analyze with the same slot."""
-        a, keep = analyzer(lower, punct, min_len, stop, stem)
+        a, keep = analyzer(lower, punct, min_len, stop, stem, utf8)
         if isinstance(corpus, Corpus):
             c = corpus
         else:
@@ -938,10 +946,11 @@ class Engine:
 
     def analyze_info(self) -> dict:
         """Counters and device time of the last analyze (tfidf_last_analyze_info)."""
-        t = AnalyzeInfo()
-        t.size = C.sizeof(AnalyzeInfo)
+        t = AnalyzeInfoUtf8()
+        t.size = C.sizeof(AnalyzeInfoUtf8)
         _chk(lib().tfidf_last_analyze_info(self.h, C.byref(t)), "tfidf_last_analyze_info")
-        return {k: getattr(t, k) for k, _ in AnalyzeInfo._fields_ if k not in ("size", "reserved")}
+        names = [k for k, _ in AnalyzeInfo._fields_ + AnalyzeInfoUtf8._fields_]
+        return {k: getattr(t, k) for k in names if k not in ("size", "reserved")}
 
     def model_export(self) -> dict:
         """The context's model (tfidf_model_export): N, terms (list of bytes in term-table order),
