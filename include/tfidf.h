@@ -1003,6 +1003,103 @@ typedef struct tfidf_analyze_info {
 } tfidf_analyze_info;
 int tfidf_last_analyze_info(const tfidf_ctx* ctx, tfidf_analyze_info* info);
 
+/* ----------------------------------------------------------------- n-grams -- */
+
+/* Word n-grams (shingles) in front of the counter: the one stage that is not bytes-to-bytes of
+ * the same length.  It turns a corpus into a corpus of another size whose tokens are the grams;
+ * tfidf_run, query, BM25, keywords, similar, clusters, transform and the model work on its
+ * output as on any corpus.  Byte-exact everywhere.
+ *
+ * Parameters: min_n and max_n with 1 <= min_n <= max_n <= TFIDF_NGRAM_MAX_N, and a joiner byte J
+ * (0: the default 0x5F '_'; any byte except NUL and the six separators 0x20, 0x09..0x0D).  After
+ * TFIDF_AN_PUNCT no token holds '_', so the grams are unambiguous.
+ *
+ * The tokens t_0..t_{m-1} of every document window [off[i], off[i + 1]) are the maximal runs of
+ * non-separator bytes inside the document; a document boundary ends a token, as for
+ * tfidf_corpus.  The output document is, position-major,
+ *
+ *     for p in 0..m-1:  for n in min_n..max_n:  if p + n <= m:
+ *         t_p J t_{p+1} J .. J t_{p+n-1}  0x20
+ *
+ * every gram followed by exactly one blank.  Tokens are copied verbatim, NUL bytes included; the
+ * run's own "term = bytes up to the first NUL" rule then applies to the gram.  The output corpus
+ * is the concatenation of the output documents: out_off[0] = 0, nbytes_out = out_off[ndocs];
+ * bytes outside [off[0], off[ndocs]) are dropped; a document with fewer than min_n tokens
+ * becomes an empty document; doc_ids and ndocs_total pass through; with (1, 1) the output is the
+ * input's tokens separated by single blanks.
+ *
+ * Example: b"XXnew  york\ncityrunning onYY" with off = [2, 16, 20, 26] ("runn|ing" is cut by a
+ * document boundary and no gram crosses it):
+ *     (1, 2)  b"new new_york york york_city city runn ing ing_on on "   out_off [0, 33, 38, 52]
+ *     (2, 3)  b"new_york new_york_city york_city ing_on "               out_off [0, 33, 33, 40]
+ *
+ * Consequences: docSize of a run of the output counts grams, not words.  The stage runs after
+ * the analyzer, so grams skip over blanked stop words, as in scikit-learn.  Like the analyzer it
+ * is not recorded in a model file: whoever serves from a model passes the same options again.  A
+ * gram of 16 MiB or more is refused by the run itself (TFIDF_E_CAPACITY), not here. */
+#define TFIDF_NGRAM_MAX_N 8u
+typedef struct tfidf_ngram_params {
+    uint64_t size;               /* sizeof(tfidf_ngram_params), set by the caller */
+    uint32_t min_n, max_n;
+    uint8_t  joiner;             /* 0: '_' */
+    uint8_t  reserved[7];        /* 0 */
+} tfidf_ngram_params;
+/* Host only.  TFIDF_E_INVAL for: NULL; size < sizeof(tfidf_ngram_params); min_n == 0;
+ * max_n < min_n; max_n > TFIDF_NGRAM_MAX_N; a joiner that is a separator; non-zero reserved
+ * bytes. */
+int tfidf_ngram_check(const tfidf_ngram_params* params);
+/* Host only, plain C: the definition above.  Document i is bytes[off[i], off[i + 1]).
+ * *out_bytes (*out_nbytes bytes; at least one byte is allocated) and *out_off (n + 1 entries)
+ * are malloc'd and released with tfidf_free.  TFIDF_E_INVAL for parameters that fail the check,
+ * a NULL output pointer, a NULL bytes with nbytes > 0, a NULL off with n > 0, a non-monotone off
+ * or off[n] > nbytes; TFIDF_E_NOMEM.  On an error the three outputs are zeroed. */
+int tfidf_ngrams_host(const tfidf_ngram_params* params, const uint8_t* bytes, uint64_t nbytes,
+                      const uint64_t* off, uint32_t n, uint8_t** out_bytes, uint64_t* out_nbytes,
+                      uint64_t** out_off);
+
+/* The same on the device (ngram.hip).  in: a host corpus (staged in a context buffer first) or a
+ * TFIDF_CORPUS_DEVICE corpus at any alignment of bytes, windows allowed.  *out: a device corpus
+ * in buffers owned by the context (slot `slot`), valid until the next tfidf_ngrams with the same
+ * slot on this context or tfidf_close; out->bytes is 16-byte aligned, doc_off (the new offsets)
+ * and doc_ids are the context's own device copies, ndocs / ndocs_total are the input's.
+ * Two slots of its own, separate from the analyzer's: the corpus goes to slot 0, batches to
+ * slot 1.  The usual chain is ingest -> tfidf_analyze slot 0 -> tfidf_ngrams slot 0 ->
+ * tfidf_run.
+ * TFIDF_E_INVAL: a NULL argument, slot > 1, parameters that fail the check, bad offsets (the
+ * rules of tfidf_transform), in->bytes inside the same n-gram slot's buffer.  ndocs == 0,
+ * nbytes == 0 and empty documents are valid.  TFIDF_E_CAPACITY: 2^32 - 1 tokens or more.  The
+ * kernels read no byte outside in->bytes[0, nbytes).  The result does not depend on grid or
+ * tile.  All buffers belong to the context: a repeated identical call allocates nothing
+ * (tfidf_alloc_stats).  The call neither needs nor disturbs a run's result and works before any
+ * tfidf_run.  There is no group entry point: shingle each shard on tfidf_group_ctx(g, r) before
+ * tfidf_group_run.
+ * The whole input is handled in one piece, without slicing: beside the output the call holds 24
+ * bytes of scratch per token (start, end, segment offset) plus the boundary bitmap and per-tile
+ * counts of the input (about nbytes / 8 + nbytes / 256) and 4 bytes per 4096 output bytes.  What
+ * a caller needs in practice has not been measured. */
+#define TFIDF_NG_SLOT_CORPUS 0u
+#define TFIDF_NG_SLOT_BATCH  1u
+int tfidf_ngrams(tfidf_ctx* ctx, const tfidf_ngram_params* params, const tfidf_corpus* in,
+                 uint32_t slot, tfidf_corpus* out);
+/* Counters of the last tfidf_ngrams (the caller sets `size` = sizeof, as tfidf_query_info). */
+typedef struct tfidf_ngram_info {
+    uint64_t size;
+    uint64_t nbytes_in;       /* in->nbytes */
+    uint64_t nbytes_out;
+    uint64_t ntokens;         /* tokens of the input's documents */
+    uint64_t ngrams;          /* grams written */
+    uint32_t ndocs;
+    uint32_t tile_bytes;      /* output bytes a workgroup of the write kernel owns */
+    uint32_t grid;            /* workgroups of the write kernel (0: nothing to write) */
+    uint32_t reserved;
+    uint64_t scratch_bytes;   /* device scratch beside the output: bitmap, counts, 24 bytes per token */
+    double   ms_bounds;       /* token bounds (HIP events, like the next two) */
+    double   ms_sizes;        /* segment sizes, their scan, the document offsets */
+    double   ms_write;        /* the write kernel */
+    double   ms_total;        /* host wall time of the whole call */
+} tfidf_ngram_info;
+int tfidf_last_ngram_info(const tfidf_ctx* ctx, tfidf_ngram_info* info);
+
 /* ---------------------------------------------------------------- ingest ---- */
 
 /* Reference input contract (TFIDF.c:98-110,130-147): N = number of entries of `dir`

@@ -301,6 +301,13 @@ struct tfidf_ctx {
     DevBuf an_in, an_bytes[2], an_off[2], an_ids[2], an_dstart, an_tab, an_cnt;
     hipEvent_t ev_an[2] = {};                   /* the kernels' bounds (created by the first call) */
     tfidf_analyze_info aninfo{};
+    /* word n-grams (tfidf_ngrams, ngram.hip): a host input's staged bytes and offsets; per slot
+     * the output bytes, the new offsets and the context's copy of the ids; the boundary scratch
+     * (status, gram counter, bitmap, per-tile counts), the 24 bytes per token (start, end,
+     * segment offset) and the write kernel's tile index of the call in flight */
+    DevBuf ng_in, ng_inoff, ng_bytes[2], ng_off[2], ng_ids[2], ng_a, ng_b, ng_tseg;
+    hipEvent_t ev_ng[4] = {};                   /* bounds / sizes / write bounds (created by the first call) */
+    tfidf_ngram_info nginfo{};
 #define WR_NBUF 8
 #define WR_BUF (16ull << 20)
 #define WR_GROUPS 8
@@ -609,6 +616,11 @@ void tfidf_close(tfidf_ctx* ctx) {
         if (e) (void)hipEventDestroy(e);
     for (DevBuf* b : {&ctx->an_in, &ctx->an_bytes[0], &ctx->an_bytes[1], &ctx->an_off[0], &ctx->an_off[1], &ctx->an_ids[0],
                       &ctx->an_ids[1], &ctx->an_dstart, &ctx->an_tab, &ctx->an_cnt})
+        b->release();
+    for (hipEvent_t e : ctx->ev_ng)
+        if (e) (void)hipEventDestroy(e);
+    for (DevBuf* b : {&ctx->ng_in, &ctx->ng_inoff, &ctx->ng_bytes[0], &ctx->ng_bytes[1], &ctx->ng_off[0], &ctx->ng_off[1],
+                      &ctx->ng_ids[0], &ctx->ng_ids[1], &ctx->ng_a, &ctx->ng_b, &ctx->ng_tseg})
         b->release();
     DevBuf* bufs[] = {&ctx->arena_buf, &ctx->in_bytes, &ctx->in_off, &ctx->in_ids, &ctx->syn_bytes, &ctx->syn_off,
                       &ctx->syn_ids, &ctx->syn_ntok, &ctx->syn_blkfirst, &ctx->syn_blkbytes, &ctx->syn_cdf,
@@ -3313,6 +3325,208 @@ extern "C" int tfidf_last_analyze_info(const tfidf_ctx* ctx, tfidf_analyze_info*
     if (!ctx || !info || info->size < sizeof(uint64_t)) return TFIDF_E_INVAL;
     const uint64_t n = info->size < sizeof(tfidf_analyze_info) ? info->size : sizeof(tfidf_analyze_info);
     tfidf_analyze_info o = ctx->aninfo;
+    o.size = n;
+    memcpy(info, &o, (size_t)n);
+    return TFIDF_OK;
+}
+
+/* ----------------------------------------------------------------- n-grams ----
+ * include/tfidf.h, section "n-grams"; ngram.hip.  The check and the host definition are
+ * ngram_host.c.  Like the analyzer the call stands beside a run: it reads and writes buffers of
+ * its own and none of the run's state (the arena is scratch between runs, as for
+ * tfidf_transform).  Two host round trips size the buffers: the tokens, then the output's bytes. */
+extern "C" int tfidf_ngrams(tfidf_ctx* ctx, const tfidf_ngram_params* params, const tfidf_corpus* in_, uint32_t slot,
+                            tfidf_corpus* out) {
+    if (!ctx || !params || !in_ || !out || slot > 1u) return TFIDF_E_INVAL;
+    const int prc = tfidf_ngram_check(params);
+    if (prc) return prc;
+    const tfidf_corpus in = *in_;   /* out may be the same struct */
+    const uint32_t N = in.ndocs;
+    if (N && !in.doc_off) return TFIDF_E_INVAL;
+    if (in.nbytes && !in.bytes) return TFIDF_E_INVAL;
+    const bool dev = (in.flags & TFIDF_CORPUS_DEVICE) != 0;
+    DevBuf& ob = ctx->ng_bytes[slot];
+    if (dev && ob.p && in.bytes >= ob.as<uint8_t>() && in.bytes < ob.as<uint8_t>() + ob.cap) return TFIDF_E_INVAL;
+    const auto wall0 = std::chrono::steady_clock::now();
+    HIPCHK(hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    /* the offsets on the host: checked here, by tfidf_transform's rules */
+    std::vector<uint64_t> off_copy;
+    const uint64_t* off = in.doc_off;
+    if (dev && N) {
+        off_copy.resize((size_t)N + 1);
+        HIPCHK(hipMemcpyAsync(off_copy.data(), in.doc_off, ((size_t)N + 1) * 8, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        off = off_copy.data();
+    }
+    for (uint32_t d = 0; d < N; ++d)
+        if (off[d] > off[d + 1]) return TFIDF_E_INVAL;
+    if (N && off[N] > in.nbytes) return TFIDF_E_INVAL;
+    for (hipEvent_t& e : ctx->ev_ng)
+        if (!e) HIPCHK(hipEventCreate(&e));
+    const uint64_t b0 = N ? off[0] : 0, b1 = N ? off[N] : 0;
+    const uint8_t* d_bytes = in.bytes;
+    const uint64_t* d_off = in.doc_off;
+    if (!dev && N) {   /* the window alone is staged, at its own offsets */
+        ENSURE(ctx->ng_in, in.nbytes + 64);
+        ENSURE(ctx->ng_inoff, ((size_t)N + 1) * 8);
+        if (b1 > b0) HIPCHK(hipMemcpyAsync(ctx->ng_in.as<uint8_t>() + b0, in.bytes + b0, b1 - b0, hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(ctx->ng_inoff.p, off, ((size_t)N + 1) * 8, hipMemcpyHostToDevice, s));
+        d_bytes = ctx->ng_in.as<uint8_t>();
+        d_off = ctx->ng_inoff.as<uint64_t>();
+    }
+    ENSURE(ctx->ng_off[slot], ((size_t)N + 1) * 8);
+    if (in.doc_ids && N) {
+        ENSURE(ctx->ng_ids[slot], (size_t)N * 4);
+        HIPCHK(hipMemcpyAsync(ctx->ng_ids[slot].p, in.doc_ids, (size_t)N * 4, dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
+    }
+
+    tfidf_ngram_info ni{};
+    ni.nbytes_in = in.nbytes;
+    ni.ndocs = N;
+    ni.tile_bytes = NG_TILE;
+    uint64_t T = 0, nbytes_out = 0;
+    unsigned long long ngrams = 0;
+    HIPCHK(hipEventRecord(ctx->ev_ng[0], s));
+    /* ---- token bounds: transform.hip's kernels over the whole window as one slice ---- */
+    TrSlice sl{};
+    size_t a_end = 0;
+    if (b1 > b0) {
+        sl.bytes = d_bytes;
+        sl.nbytes = in.nbytes;
+        sl.doc_off = d_off;
+        sl.d0 = 0;
+        sl.d1 = N;
+        sl.b0 = b0;
+        sl.b1 = b1;
+        sl.p0 = (long long)b0 - (long long)(((uintptr_t)d_bytes + b0) & 15u);
+        sl.ntiles = (uint64_t)((long long)b1 - sl.p0 + (TR_TILE - 1)) / TR_TILE;
+        /* ng_a: status and the gram counter, the bitmap, the per-tile counts */
+        const size_t a_dstart = 256, a_cs = al256(a_dstart + (size_t)(sl.ntiles * (TR_TILE / 32u) + 1u) * 4);
+        const size_t a_ce = al256(a_cs + (size_t)(sl.ntiles + 1) * 8);
+        a_end = al256(a_ce + (size_t)(sl.ntiles + 1) * 8);
+        ENSURE(ctx->ng_a, a_end);
+        uint8_t* A = ctx->ng_a.as<uint8_t>();
+        sl.status = (uint32_t*)A;
+        sl.dstart = (uint32_t*)(A + a_dstart);
+        sl.cnt_s = (uint64_t*)(A + a_cs);
+        sl.cnt_e = (uint64_t*)(A + a_ce);
+        HIPCHK(hipMemsetAsync(A, 0, 256, s));   /* status, gram counter */
+        ctx->arena.used = 0;   /* as tfidf_transform: nothing of a run's result lives in the arena */
+        if (launch_tr_docstarts(sl, s) || launch_tr_count(sl, s)) { HIPCHK(hipGetLastError()); return TFIDF_E_HIP; }
+        if (scan_excl_u64(sl.cnt_s, sl.cnt_s, sl.ntiles, ctx->arena, s) ||
+            scan_excl_u64(sl.cnt_e, sl.cnt_e, sl.ntiles, ctx->arena, s)) {
+            HIPCHK(hipGetLastError());
+            return TFIDF_E_HIP;
+        }
+        uint64_t tot[2] = {0, 0};
+        HIPCHK(hipMemcpyAsync(&tot[0], sl.cnt_s + sl.ntiles, 8, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(&tot[1], sl.cnt_e + sl.ntiles, 8, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        T = tot[0];
+        if (tot[1] != T || T > tr_max_tokens(b1 - b0, N)) {
+            fprintf(stderr, "tfidf: ngrams: %llu token starts, %llu ends in %llu bytes\n", (unsigned long long)tot[0],
+                    (unsigned long long)tot[1], (unsigned long long)(b1 - b0));
+            return TFIDF_E_STATE;
+        }
+        if (T > 0xFFFFFFFEull) return TFIDF_E_CAPACITY;
+    }
+    NgArgs na{};
+    if (T) {
+        /* ng_b: 24 bytes per token */
+        const size_t b_ts = 0, b_te = al256(b_ts + (size_t)T * 8), b_so = al256(b_te + (size_t)T * 8);
+        const size_t b_end = al256(b_so + ((size_t)T + 1) * 8);
+        ENSURE(ctx->ng_b, b_end);
+        {   /* the scans' block sums */
+            const size_t want = (size_t)(T / 32) + (1u << 20);
+            if (want > ctx->arena_buf.cap && arena_reset(ctx, want) != 0) return TFIDF_E_NOMEM;
+            ctx->arena.used = 0;
+        }
+        uint8_t* B = ctx->ng_b.as<uint8_t>();
+        sl.tok_start = (uint64_t*)(B + b_ts);
+        sl.tok_end = (uint64_t*)(B + b_te);
+        sl.tok_cap = T;
+        if (launch_tr_write(sl, s)) { HIPCHK(hipGetLastError()); return TFIDF_E_HIP; }
+        HIPCHK(hipEventRecord(ctx->ev_ng[1], s));
+        /* ---- segment sizes, their scan, the output's size ---- */
+        na.bytes = d_bytes;
+        na.nbytes = in.nbytes;
+        na.doc_off = d_off;
+        na.ndocs = N;
+        na.dstart = sl.dstart;
+        na.p0 = sl.p0;
+        na.min_n = params->min_n;
+        na.max_n = params->max_n;
+        na.joiner = params->joiner ? params->joiner : 0x5Fu;
+        na.tok_start = sl.tok_start;
+        na.tok_end = sl.tok_end;
+        na.ntok = T;
+        na.seg_off = (uint64_t*)(B + b_so);
+        na.ngrams = (unsigned long long*)(ctx->ng_a.as<uint8_t>() + 8);
+        if (launch_ng_sizes(na, s) || scan_excl_u64(na.seg_off, na.seg_off, T, ctx->arena, s)) {
+            HIPCHK(hipGetLastError());
+            return TFIDF_E_HIP;
+        }
+        uint32_t status = 0;
+        HIPCHK(hipMemcpyAsync(&nbytes_out, na.seg_off + T, 8, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(&ngrams, na.ngrams, 8, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(&status, sl.status, 4, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        if (status) {
+            fprintf(stderr, "tfidf: ngrams: status 0x%x\n", status);
+            return TFIDF_E_STATE;
+        }
+        ni.scratch_bytes = a_end + b_end;
+    } else {
+        HIPCHK(hipEventRecord(ctx->ev_ng[1], s));
+    }
+    ENSURE(ctx->ng_bytes[slot], nbytes_out + 64);
+    if (nbytes_out) {
+        na.out_off = ctx->ng_off[slot].as<uint64_t>();
+        na.out = ctx->ng_bytes[slot].as<uint8_t>();
+        na.nbytes_out = nbytes_out;
+        na.ntiles = (nbytes_out + NG_TILE - 1) / NG_TILE;
+        ENSURE(ctx->ng_tseg, (size_t)(na.ntiles + 1) * 4);
+        na.tile_seg = ctx->ng_tseg.as<uint32_t>();
+        ni.scratch_bytes += (size_t)(na.ntiles + 1) * 4;
+        if (launch_ng_offsets(na, s)) { HIPCHK(hipGetLastError()); return TFIDF_E_HIP; }
+        HIPCHK(hipEventRecord(ctx->ev_ng[2], s));
+        if (launch_ng_write(na, s)) { HIPCHK(hipGetLastError()); return TFIDF_E_HIP; }
+        ni.grid = (uint32_t)na.ntiles;
+    } else {   /* no gram: every document is empty */
+        HIPCHK(hipMemsetAsync(ctx->ng_off[slot].p, 0, ((size_t)N + 1) * 8, s));
+        HIPCHK(hipEventRecord(ctx->ev_ng[2], s));
+    }
+    HIPCHK(hipEventRecord(ctx->ev_ng[3], s));
+    HIPCHK(hipStreamSynchronize(s));
+
+    out->bytes = ctx->ng_bytes[slot].as<uint8_t>();
+    out->nbytes = nbytes_out;
+    out->doc_off = ctx->ng_off[slot].as<uint64_t>();
+    out->doc_ids = (in.doc_ids && N) ? ctx->ng_ids[slot].as<uint32_t>() : nullptr;
+    out->ndocs = N;
+    out->flags = TFIDF_CORPUS_DEVICE;
+    out->ndocs_total = in.ndocs_total;
+
+    ni.nbytes_out = nbytes_out;
+    ni.ntokens = T;
+    ni.ngrams = ngrams;
+    float ms = 0;
+    (void)hipEventElapsedTime(&ms, ctx->ev_ng[0], ctx->ev_ng[1]);
+    ni.ms_bounds = ms;
+    (void)hipEventElapsedTime(&ms, ctx->ev_ng[1], ctx->ev_ng[2]);
+    ni.ms_sizes = ms;
+    (void)hipEventElapsedTime(&ms, ctx->ev_ng[2], ctx->ev_ng[3]);
+    ni.ms_write = ms;
+    ni.ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - wall0).count();
+    ctx->nginfo = ni;
+    return TFIDF_OK;
+}
+
+extern "C" int tfidf_last_ngram_info(const tfidf_ctx* ctx, tfidf_ngram_info* info) {
+    if (!ctx || !info || info->size < sizeof(uint64_t)) return TFIDF_E_INVAL;
+    const uint64_t n = info->size < sizeof(tfidf_ngram_info) ? info->size : sizeof(tfidf_ngram_info);
+    tfidf_ngram_info o = ctx->nginfo;
     o.size = n;
     memcpy(info, &o, (size_t)n);
     return TFIDF_OK;

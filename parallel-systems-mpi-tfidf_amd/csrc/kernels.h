@@ -782,4 +782,39 @@ uint32_t an_lds_bytes(const AnArgs& a, uint32_t nstop);
  * *grid receives the workgroups launched (0: the byte map, or no bytes) */
 int launch_analyze(const AnArgs& a, uint32_t nstop, uint32_t ncu, uint32_t grid_cap, uint32_t* grid, hipStream_t s);
 
+/* ---- word n-grams (ngram.hip, tfidf_ngrams) ---- */
+#define NG_TILE 4096u   /* output bytes a workgroup of the write kernel owns: 256 lanes x one 16-byte store */
+/* The tokens come from transform.hip's boundary kernels: token i = bytes [tok_start[i],
+ * tok_end[i]), in order.  Segment i = the grams that start at token i, min_n first; seg_off holds
+ * the segments' byte counts (launch_ng_sizes), then their exclusive scan (the caller's
+ * scan_excl_u64 in place: seg_off[ntok] = the output's bytes). */
+struct NgArgs {
+    const uint8_t* bytes;        /* the input */
+    uint64_t nbytes;             /* bound of `bytes` */
+    const uint64_t* doc_off;     /* the input's ndocs + 1 offsets (device) */
+    uint32_t ndocs;
+    uint32_t min_n, max_n, joiner;
+    const uint32_t* dstart;      /* TrSlice's bitmap of the same input: bit i = a document starts at p0 + i */
+    long long p0;
+    const uint64_t* tok_start;
+    const uint64_t* tok_end;
+    uint64_t ntok;               /* > 0 */
+    uint64_t* seg_off;           /* ntok + 1 */
+    unsigned long long* ngrams;  /* grams written, zeroed by the caller (one integer add per workgroup) */
+    uint64_t* out_off;           /* ndocs + 1: the output's document offsets */
+    uint32_t* tile_seg;          /* ntiles + 1: the segment that holds a tile's first byte */
+    uint8_t* out;                /* 16-byte aligned, nbytes_out rounded up to 16 bytes writable */
+    uint64_t nbytes_out;
+    uint64_t ntiles;             /* ceil(nbytes_out / NG_TILE) */
+};
+/* one lane per token: the lengths of the next max_n - 1 tokens of the same row (no document
+ * start between them) -> seg_off[i] = the segment's bytes */
+int launch_ng_sizes(const NgArgs& a, hipStream_t s);
+/* after the scan: out_off[d] = seg_off[lower_bound(tok_start, doc_off[d])], one lane per document;
+ * tile_seg[t] = the last segment that starts at or before byte t * NG_TILE, one lane per tile */
+int launch_ng_offsets(const NgArgs& a, hipStream_t s);
+/* the output bytes: a workgroup per tile, the descriptors of the tile's segments in LDS, one
+ * 16-byte store per lane */
+int launch_ng_write(const NgArgs& a, hipStream_t s);
+
 #endif

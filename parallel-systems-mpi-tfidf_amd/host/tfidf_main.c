@@ -112,9 +112,20 @@
  * analyzer on the host, also under --model FILE.  The model file does not record the analyzer:
  * whoever serves from it passes the same flags again.  Without any of them nothing new is
  * called and every byte of every output is as before.
+ *
+ * Word n-grams (tfidf_ngrams on the GPU for input/, tfidf_ngrams_host for the rest), behind the
+ * analyzer:
+ *   --ngrams SPEC          SPEC is N (= 1-N) or A-B with 1 <= A <= B <= TFIDF_NGRAM_MAX_N: the
+ *                          terms are the grams of A..B consecutive tokens of a document, joined
+ *                          by '_'.  A bad SPEC ("0", "3-2", "9", "1-") is a usage error (exit 2).
+ *   --ngram-joiner C       the byte C instead of '_' (no separator); needs --ngrams.
+ * input/ is shingled in HBM after the analyzer (every shard on its own GPU), the lines of
+ * --query FILE and the documents of --transform DIR on the host, also under --model FILE.  The
+ * model file does not record the option.  Without --ngrams nothing new is called.
  */
 #include <dirent.h>
 #include <pthread.h>
+#include <stddef.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -215,6 +226,50 @@ static int analyze_host_batch(uint8_t* bytes, uint64_t nbytes, const uint64_t* o
     return g_an.on ? tfidf_analyze_host(&g_an.an, bytes, nbytes, off, n, bytes) : TFIDF_OK;
 }
 
+/* ---------------------------------------------------------------- n-grams -- */
+
+static struct {
+    int on;             /* 0: no --ngrams, behaviour and bytes as without the option */
+    tfidf_ngram_params p;
+} g_ng;
+
+/* --ngrams SPEC: N (= 1-N) or A-B, decimal digits only */
+static int parse_ngram_spec(const char* spec) {
+    char* end = NULL;
+    if (spec[0] < '0' || spec[0] > '9') return TFIDF_E_INVAL;
+    const unsigned long a = strtoul(spec, &end, 10);
+    unsigned long b = a, lo = 1;
+    if (*end == '-') {
+        const char* q = end + 1;
+        if (q[0] < '0' || q[0] > '9') return TFIDF_E_INVAL;
+        b = strtoul(q, &end, 10);
+        lo = a;
+    }
+    if (*end || lo < 1 || b < lo || b > TFIDF_NGRAM_MAX_N) return TFIDF_E_INVAL;
+    memset(&g_ng.p, 0, offsetof(tfidf_ngram_params, joiner));   /* --ngram-joiner may have come first */
+    g_ng.p.size = sizeof(g_ng.p);
+    g_ng.p.min_n = (uint32_t)lo;
+    g_ng.p.max_n = (uint32_t)b;
+    g_ng.on = 1;
+    return TFIDF_OK;
+}
+
+/* the shingled batch in place of a host batch (query lines, transform batches), behind the
+ * analyzer; the old arrays are freed.  A no-op without --ngrams */
+static int ngram_host_batch(uint8_t** bytes, uint64_t* nbytes, uint64_t** off, uint32_t n) {
+    if (!g_ng.on) return TFIDF_OK;
+    uint8_t* ob = NULL;
+    uint64_t on = 0, *oo = NULL;
+    const int rc = tfidf_ngrams_host(&g_ng.p, *bytes, *nbytes, *off, n, &ob, &on, &oo);
+    if (rc) return rc;
+    tfidf_free(*bytes);
+    tfidf_free(*off);
+    *bytes = ob;
+    *nbytes = on;
+    *off = oo;
+    return TFIDF_OK;
+}
+
 /* ---------------------------------------------------------------- queries -- */
 
 static struct {
@@ -267,6 +322,7 @@ static int run_queries(tfidf_ctx* ctx, tfidf_group* g) {
     int rc = load_queries(&bytes, &qs.nbytes, &off, &qs.nqueries);
     if (rc == TFIDF_E_NOINPUT) { printf("Error Opening File: %s\n", g_query.file); return TFIDF_OK; }
     if (!rc) rc = analyze_host_batch(bytes, qs.nbytes, off, qs.nqueries);
+    if (!rc) rc = ngram_host_batch(&bytes, &qs.nbytes, &off, qs.nqueries);
     if (rc) { free(bytes); free(off); return rc; }
     qs.bytes = bytes;
     qs.q_off = off;
@@ -449,6 +505,7 @@ static int run_transform(tfidf_ctx* ctx, tfidf_group* g) {
     if (rc == TFIDF_E_NOINPUT) { printf("Directory failed to open\n"); return TFIDF_OK; }
     if (rc == TFIDF_E_NODOC) { (void)missing_doc(g_transform.dir, bad, b.ndocs); return TFIDF_OK; }
     if (!rc) rc = analyze_host_batch(bytes, b.nbytes, off, b.ndocs);
+    if (!rc) rc = ngram_host_batch(&bytes, &b.nbytes, &off, b.ndocs);   /* kept until the rows are written: word_off points into it */
     if (rc) { tfidf_free(bytes); tfidf_free(off); return rc; }
     b.bytes = bytes;
     b.doc_off = off;
@@ -527,6 +584,7 @@ static int run_single(int device, const char* indir, const char* outpath, int de
     if (rc) { tfidf_close(ctx); return fail(rc); }
     if (c.ndocs == 0) { printf("More workers than input files! Exiting.\n"); tfidf_close(ctx); return 0; }
     if (g_an.on) rc = tfidf_analyze(ctx, &g_an.an, &c, TFIDF_AN_SLOT_CORPUS, &c);   /* in HBM, where the ingest left it */
+    if (!rc && g_ng.on) rc = tfidf_ngrams(ctx, &g_ng.p, &c, TFIDF_NG_SLOT_CORPUS, &c);
     if (!rc) rc = tfidf_run(ctx, &c);
     if (!rc && debug) rc = debug_jobs(ctx);
     if (rc) { tfidf_close(ctx); return fail(rc); }
@@ -585,6 +643,8 @@ static void* ingest_job(void* arg) {
                                       &j->corpus, &j->bad, NULL);
     if (!j->rc && g_an.on)
         j->rc = tfidf_analyze(tfidf_group_ctx(j->g, (int)j->shard), &g_an.an, &j->corpus, TFIDF_AN_SLOT_CORPUS, &j->corpus);
+    if (!j->rc && g_ng.on)
+        j->rc = tfidf_ngrams(tfidf_group_ctx(j->g, (int)j->shard), &g_ng.p, &j->corpus, TFIDF_NG_SLOT_CORPUS, &j->corpus);
     return NULL;
 }
 
@@ -673,6 +733,32 @@ static int run_sharded(int ngpus, int nshards, const char* indir, const char* ou
     return 0;
 }
 
+static int usage(void) {
+    fprintf(stderr, "usage: tfidf [--debug-jobs] [--stats] [--gpus N] [--shards K] [--device D] "
+                    "[--input DIR] [--output FILE] [--query FILE [--top K] [--hits FILE] [--bm25 [--bm25-k1 X] [--bm25-b Y]]] "
+                    "[--keywords K [--keywords-file FILE]] "
+                    "[--similar K [--similar-docs FILE] [--similar-file FILE]] "
+                    "[--clusters K [--clusters-iter I] [--clusters-seeds FILE] [--clusters-terms T] [--clusters-file FILE]] "
+                    "[--transform DIR [--transform-file FILE]] [--save-model FILE] "
+                    "[--lower] [--strip-punct] [--min-token N] [--stopwords FILE] [--stem] [--utf8] [--ngrams SPEC [--ngram-joiner C]]\n"
+                    "       tfidf --model FILE --transform DIR [--transform-file FILE] [--device D] "
+                    "[--lower] [--strip-punct] [--min-token N] [--stopwords FILE] [--stem] [--utf8] [--ngrams SPEC [--ngram-joiner C]]\n"
+                    "  --similar K without --similar-docs searches for every document: "
+                    "ceil(N / group) scans of the scored pairs, group <= 64\n"
+                    "  --save-model FILE writes the run's term table, df and N; --model FILE scores "
+                    "--transform DIR against such a file without input/ or output.txt\n"
+                    "  --lower, --strip-punct, --min-token N, --stopwords FILE and --stem analyze input/, the "
+                    "query lines and the --transform documents before they are counted; the model file does "
+                    "not record them\n"
+                    "  --stem replaces tokens of 3..64 lower-case ASCII letters by their Porter stems; it does "
+                    "not imply --lower, and the words of --stopwords FILE are not stemmed\n"
+                    "  --utf8 extends --lower and --strip-punct to UTF-8 sequences: cased letters whose lowercase "
+                    "has the same length are folded, punctuation, symbols and separators are blanked\n"
+                    "  --ngrams SPEC adds word n-grams behind the analyzer: SPEC is N (= 1-N) or A-B with 1 <= A <= B <= 8; "
+                    "the words of a gram are joined by '_' or by the byte of --ngram-joiner C\n");
+    return 2;
+}
+
 int main(int argc, char** argv) {
     int debug = 0, stats = 0, device = -1, ngpus = 0, nshards = 0;
     const char* indir = "input";
@@ -721,6 +807,14 @@ int main(int argc, char** argv) {
             g_an.an.min_len = (uint32_t)v;
             g_an.on = 1;
         }
+        else if (!strcmp(argv[i], "--ngrams") && i + 1 < argc) {
+            if (parse_ngram_spec(argv[++i]) != TFIDF_OK) return usage();
+        }
+        else if (!strcmp(argv[i], "--ngram-joiner") && i + 1 < argc) {
+            const char* c = argv[++i];
+            if (strlen(c) != 1) return usage();
+            g_ng.p.joiner = (uint8_t)c[0];
+        }
         else if (!strcmp(argv[i], "--transform-file") && i + 1 < argc) g_transform.file = argv[++i];
         else if (!strcmp(argv[i], "--transform") && i + 1 < argc) g_transform.dir = argv[++i];
         else if (!strcmp(argv[i], "--save-model") && i + 1 < argc) g_model.save = argv[++i];
@@ -750,30 +844,11 @@ int main(int argc, char** argv) {
             g_similar.k = (uint32_t)k;
         }
         else {
-            fprintf(stderr, "usage: tfidf [--debug-jobs] [--stats] [--gpus N] [--shards K] [--device D] "
-                            "[--input DIR] [--output FILE] [--query FILE [--top K] [--hits FILE] [--bm25 [--bm25-k1 X] [--bm25-b Y]]] "
-                            "[--keywords K [--keywords-file FILE]] "
-                            "[--similar K [--similar-docs FILE] [--similar-file FILE]] "
-                            "[--clusters K [--clusters-iter I] [--clusters-seeds FILE] [--clusters-terms T] [--clusters-file FILE]] "
-                            "[--transform DIR [--transform-file FILE]] [--save-model FILE] "
-                            "[--lower] [--strip-punct] [--min-token N] [--stopwords FILE] [--stem] [--utf8]\n"
-                            "       tfidf --model FILE --transform DIR [--transform-file FILE] [--device D] "
-                            "[--lower] [--strip-punct] [--min-token N] [--stopwords FILE] [--stem] [--utf8]\n"
-                            "  --similar K without --similar-docs searches for every document: "
-                            "ceil(N / group) scans of the scored pairs, group <= 64\n"
-                            "  --save-model FILE writes the run's term table, df and N; --model FILE scores "
-                            "--transform DIR against such a file without input/ or output.txt\n"
-                            "  --lower, --strip-punct, --min-token N, --stopwords FILE and --stem analyze input/, the "
-                            "query lines and the --transform documents before they are counted; the model file does "
-                            "not record them\n"
-                            "  --stem replaces tokens of 3..64 lower-case ASCII letters by their Porter stems; it does "
-                            "not imply --lower, and the words of --stopwords FILE are not stemmed\n"
-                            "  --utf8 extends --lower and --strip-punct to UTF-8 sequences: cased letters whose lowercase "
-                            "has the same length are folded, punctuation, symbols and separators are blanked\n");
-            return 2;
+            return usage();
         }
     }
     if (g_an.on && load_stopwords() != TFIDF_OK) return 2;
+    if (g_ng.on ? tfidf_ngram_check(&g_ng.p) != TFIDF_OK : g_ng.p.joiner != 0) return usage();   /* a separator as joiner; a joiner alone */
     if (g_model.load) {   /* a model holds no pairs: nothing to rank, list or print */
         if (!g_transform.dir) {
             fprintf(stderr, "tfidf: --model needs --transform DIR\n");

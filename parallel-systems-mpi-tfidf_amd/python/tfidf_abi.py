@@ -48,6 +48,7 @@ EXPORTS = [
     "tfidf_model_save", "tfidf_model_load", "tfidf_model_free", "tfidf_last_model_info",
     "tfidf_analyzer_check", "tfidf_analyze_host", "tfidf_analyze", "tfidf_last_analyze_info",
     "tfidf_stem_porter",
+    "tfidf_ngram_check", "tfidf_ngrams_host", "tfidf_ngrams", "tfidf_last_ngram_info",
 ]
 QUERY_MAX_K = 1024  # TFIDF_QUERY_MAX_K
 TERMS_MAX_K = 1024  # TFIDF_TERMS_MAX_K
@@ -73,6 +74,9 @@ AN_MAX_STOP = 4096  # TFIDF_AN_MAX_STOP
 AN_MAX_STOP_BYTES = 32768  # TFIDF_AN_MAX_STOP_BYTES
 AN_SLOT_CORPUS = 0  # TFIDF_AN_SLOT_CORPUS
 AN_SLOT_BATCH = 1  # TFIDF_AN_SLOT_BATCH
+NGRAM_MAX_N = 8  # TFIDF_NGRAM_MAX_N
+NG_SLOT_CORPUS = 0  # TFIDF_NG_SLOT_CORPUS
+NG_SLOT_BATCH = 1  # TFIDF_NG_SLOT_BATCH
 
 
 class Corpus(C.Structure):
@@ -260,6 +264,22 @@ class AnalyzeInfoUtf8(AnalyzeInfo):
     _fields_ = [("utf8_changed", C.c_uint64)]
 
 
+class NgramParams(C.Structure):
+    _fields_ = [
+        ("size", C.c_uint64), ("min_n", C.c_uint32), ("max_n", C.c_uint32), ("joiner", C.c_uint8),
+        ("reserved", C.c_uint8 * 7),
+    ]
+
+
+class NgramInfo(C.Structure):
+    _fields_ = [
+        ("size", C.c_uint64), ("nbytes_in", C.c_uint64), ("nbytes_out", C.c_uint64), ("ntokens", C.c_uint64),
+        ("ngrams", C.c_uint64), ("ndocs", C.c_uint32), ("tile_bytes", C.c_uint32), ("grid", C.c_uint32),
+        ("reserved", C.c_uint32), ("scratch_bytes", C.c_uint64), ("ms_bounds", C.c_double), ("ms_sizes", C.c_double),
+        ("ms_write", C.c_double), ("ms_total", C.c_double),
+    ]
+
+
 class DirPlan(C.Structure):
     _fields_ = [
         ("ndocs", C.c_uint32), ("nshards", C.c_uint32), ("doc_ids", C.POINTER(C.c_uint32)),
@@ -369,6 +389,11 @@ def lib() -> C.CDLL:
         L.tfidf_stem_porter.argtypes = [C.c_void_p, C.c_uint32]
         L.tfidf_analyze.argtypes = [C.c_void_p, C.POINTER(Analyzer), C.POINTER(Corpus), C.c_uint32, C.POINTER(Corpus)]
         L.tfidf_last_analyze_info.argtypes = [C.c_void_p, C.POINTER(AnalyzeInfo)]
+        L.tfidf_ngram_check.argtypes = [C.POINTER(NgramParams)]
+        L.tfidf_ngrams_host.argtypes = [C.POINTER(NgramParams), C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32,
+                                        C.POINTER(C.c_void_p), C.POINTER(C.c_uint64), C.POINTER(C.c_void_p)]
+        L.tfidf_ngrams.argtypes = [C.c_void_p, C.POINTER(NgramParams), C.POINTER(Corpus), C.c_uint32, C.POINTER(Corpus)]
+        L.tfidf_last_ngram_info.argtypes = [C.c_void_p, C.POINTER(NgramInfo)]
         if L.tfidf_abi_version() != ABI_VERSION:
             raise RuntimeError(f"{LIB_PATH}: ABI version {L.tfidf_abi_version()}, binding expects {ABI_VERSION} "
                                f"(stale build: rebuild with __graft_entry__.build())")
@@ -640,6 +665,39 @@ def analyze_host(data, off, lower: bool = False, punct: bool = False, min_len: i
                                   off.ctypes.data if len(off) > 1 else None, max(len(off) - 1, 0),
                                   out.ctypes.data if len(out) else None), "tfidf_analyze_host")
     return out
+
+
+def ngram_params(min_n: int = 1, max_n: int = 2, joiner: int = 0) -> NgramParams:
+    """A tfidf_ngram_params; joiner 0 is the default '_'."""
+    p = NgramParams()
+    p.size = C.sizeof(NgramParams)
+    p.min_n, p.max_n, p.joiner = min_n, max_n, joiner
+    return p
+
+
+def ngram_check(p: NgramParams) -> int:
+    """tfidf_ngram_check (host only): 0, or E_INVAL."""
+    return int(lib().tfidf_ngram_check(C.byref(p)))
+
+
+def ngrams_host(data, off, min_n: int = 1, max_n: int = 2, joiner: int = 0):
+    """tfidf_ngrams_host (host only): the word n-grams of the documents data[off[i]:off[i + 1]]
+    as (bytes uint8, doc_off uint64), the shingled corpus."""
+    p = ngram_params(min_n, max_n, joiner)
+    data = np.ascontiguousarray(data, dtype=np.uint8)
+    off = np.ascontiguousarray(off, dtype=np.uint64)
+    ob, on, oo = C.c_void_p(), C.c_uint64(0), C.c_void_p()
+    _chk(lib().tfidf_ngrams_host(C.byref(p), data.ctypes.data if len(data) else None, len(data),
+                                 off.ctypes.data if len(off) > 1 else None, max(len(off) - 1, 0),
+                                 C.byref(ob), C.byref(on), C.byref(oo)), "tfidf_ngrams_host")
+    try:
+        n = int(on.value)
+        out = np.frombuffer(C.string_at(ob.value, n), dtype=np.uint8).copy() if n else np.zeros(0, dtype=np.uint8)
+        out_off = np.frombuffer(C.string_at(oo.value, 8 * max(len(off), 1)), dtype=np.uint64).copy()
+    finally:
+        lib().tfidf_free(ob)
+        lib().tfidf_free(oo)
+    return out, out_off
 
 
 def synth_host(seed: int, V: int, mode: int, cdf, doc_ids, ntok):
@@ -951,6 +1009,30 @@ class Engine:
         _chk(lib().tfidf_last_analyze_info(self.h, C.byref(t)), "tfidf_last_analyze_info")
         names = [k for k, _ in AnalyzeInfo._fields_ + AnalyzeInfoUtf8._fields_]
         return {k: getattr(t, k) for k in names if k not in ("size", "reserved")}
+
+    def ngrams(self, corpus, off=None, min_n: int = 1, max_n: int = 2, joiner: int = 0, slot: int = NG_SLOT_CORPUS,
+               doc_ids=None, ndocs_total: int = 0) -> Corpus:
+        """tfidf_ngrams: corpus is a Corpus (host or device), or host bytes with their offsets
+        `off`.  Returns the shingled device Corpus in the context's slot buffers, valid until
+        the next ngrams with the same slot."""
+        p = ngram_params(min_n, max_n, joiner)
+        if isinstance(corpus, Corpus):
+            c = corpus
+        else:
+            c, keep = _host_corpus(corpus, off)
+            ids = None if doc_ids is None else np.ascontiguousarray(doc_ids, dtype=np.uint32)
+            c.doc_ids = None if ids is None else ids.ctypes.data
+            c.ndocs_total = ndocs_total
+        out = Corpus()
+        _chk(lib().tfidf_ngrams(self.h, C.byref(p), C.byref(c), slot, C.byref(out)), "tfidf_ngrams")
+        return out
+
+    def ngram_info(self) -> dict:
+        """Counters and device times of the last ngrams (tfidf_last_ngram_info)."""
+        t = NgramInfo()
+        t.size = C.sizeof(NgramInfo)
+        _chk(lib().tfidf_last_ngram_info(self.h, C.byref(t)), "tfidf_last_ngram_info")
+        return {k: getattr(t, k) for k, _ in NgramInfo._fields_ if k not in ("size", "reserved")}
 
     def model_export(self) -> dict:
         """The context's model (tfidf_model_export): N, terms (list of bytes in term-table order),
