@@ -1100,6 +1100,95 @@ typedef struct tfidf_ngram_info {
 } tfidf_ngram_info;
 int tfidf_last_ngram_info(const tfidf_ctx* ctx, tfidf_ngram_info* info);
 
+/* ------------------------------------------------------------------- prune -- */
+
+/* Vocabulary pruning by document frequency: min_df, max_df and max_features over the resident
+ * result of the last run.  tfidf_prune removes terms, and with them their pairs, from what the
+ * run left in HBM; it never changes a number that stays.  The reference keeps every word
+ * (TFIDF.c:152-188); a second run over a filtered corpus would change docSize and every score.
+ *
+ *   kept set    term t survives the range test when
+ *                 (min_df <= 1 || df(t) >= min_df) && (max_df == 0 || df(t) <= max_df),
+ *               df = the run's global df (tfidf_result.term_df).  With max_features = M > 0 only
+ *               the first M survivors of the range test are kept, in the order df descending,
+ *               then term rank ascending (term rank = the strcmp("word\t") order of the term
+ *               table).  M >= the number of survivors removes nothing more.  The ranking is by
+ *               df, not by collection frequency (the sum of the counts): the df is resident by
+ *               rank, and (df, rank) is a total order, so the cut is unique.
+ *   terms       the kept terms keep their relative order; their new ranks are 0..V'-1
+ *   pairs       a pair survives exactly when its term does; the surviving pairs of a document
+ *               keep their order
+ *   unchanged   count, df and score of a surviving pair are the run's bits: nothing is
+ *               recomputed.  docSize, N, ndocs, the document ids and the output order of the
+ *               documents are unchanged.  The tokens of a pruned word still count in docSize,
+ *               exactly as out-of-vocabulary tokens do in tfidf_transform.  A document may end
+ *               with no pairs.
+ * Consequences:
+ *   - tfidf_fetch after the call equals the fetch before it with the pruned terms and their
+ *     pairs removed and pair_term renumbered;
+ *   - the formatted text is the old text minus the lines of pruned words, in the same order;
+ *   - tfidf_transform of the run's own corpus against the pruned context gives the pruned pairs
+ *     bit for bit; a pruned word is out of vocabulary (it counts in doc_oov and doc_size);
+ *   - tfidf_query, _query_bm25, _top_terms, _similar, _kmeans and _model_export answer as they
+ *     would on a result that never held the pruned terms.  BM25's L and avgdl are unchanged,
+ *     because docSize is; the norms of tfidf_similar are recomputed;
+ *   - prune(a) then prune(b) on df ranges equals one prune with the intersected range;
+ *   - a prune that removes nothing leaves every byte as it was.
+ * After the call tfidf_last_run_info still describes the run.  A later tfidf_run or
+ * tfidf_model_import replaces everything as before: a run after a prune gives the unpruned
+ * result again.
+ * `size` is set by the caller to sizeof(tfidf_prune_params). */
+typedef struct tfidf_prune_params {
+    uint64_t size;
+    uint32_t min_df;         /* 0 or 1: no lower bound */
+    uint32_t max_df;         /* 0: no upper bound */
+    uint32_t max_features;   /* 0: no cut */
+    uint32_t reserved;       /* 0 */
+} tfidf_prune_params;
+/* Host only.  TFIDF_E_INVAL for: NULL; size < sizeof(tfidf_prune_params); non-zero reserved;
+ * max_df != 0 && min_df > max_df. */
+int tfidf_prune_check(const tfidf_prune_params* params);
+/* TFIDF_E_INVAL for a NULL ctx or parameters that fail the check.  TFIDF_E_STATE before a
+ * successful tfidf_run and on a context that holds only an imported model (prune the model on
+ * the host with tfidf_model_prune before importing it).  With a communicator attached the call
+ * is local and df is global, so min_df / max_df select the same words on every rank;
+ * max_features != 0 is TFIDF_E_INVAL there (the ranks share no term table; a cut over all
+ * ranks is not provided).  A failed call leaves the result exactly as it was: the new arrays
+ * are written into spare buffers of the context and swapped in when every step has succeeded.
+ * The run's corpus must still be valid afterwards, as before (long terms).  All buffers belong
+ * to the context: a repeated run -> prune sequence allocates nothing after the first
+ * (tfidf_alloc_stats).  The spares are as large as the arrays they stand in for: a context
+ * that prunes holds the pair arrays (16 bytes per pair) and the two term arrays twice.  Integer kernels only, no atomics on results: the outcome does not
+ * depend on grid or tile size. */
+int tfidf_prune(tfidf_ctx* ctx, const tfidf_prune_params* params);
+/* The same on every rank of a group at once (one host thread per rank).  max_features != 0 is
+ * TFIDF_E_INVAL at every group size.  After it tfidf_group_write_output, _query, _similar,
+ * _transform and _model_export equal a pruned single-shard run of the same corpus.  Returns the
+ * lowest rank's error; a rank that failed keeps its unpruned result while the others are
+ * pruned, so run again after an error. */
+int tfidf_group_prune(tfidf_group* g, const tfidf_prune_params* params);
+/* Counters of the last tfidf_prune (the caller sets `size` = sizeof, as tfidf_query_info). */
+typedef struct tfidf_prune_info {
+    uint64_t size;
+    uint32_t nterms_before, nterms_after;
+    uint64_t npairs_before, npairs_after;
+    uint32_t docs_emptied;    /* documents that held pairs before the call and hold none after */
+    uint32_t cut_df;          /* the df of the last term max_features kept when the cut removed a
+                                 survivor of the range test; 0 when it removed none */
+    double   ms_select;       /* device times (HIP events): the keep mask and the new ranks */
+    double   ms_terms;        /* the term arrays */
+    double   ms_pairs;        /* the pair pass: count, scan, write, document offsets */
+    double   ms_total;        /* host wall time of the whole call */
+} tfidf_prune_info;
+int tfidf_last_prune_info(const tfidf_ctx* ctx, tfidf_prune_info* info);
+/* Host only, plain C: the same definition on a model struct, for which df and the term order
+ * are all it needs.  *out is owned by the library and released with tfidf_model_free; its
+ * term_off starts at 0.  TFIDF_E_INVAL for a NULL argument, parameters that fail the check or a
+ * model that fails tfidf_model_check; TFIDF_E_NOMEM; *out is zeroed on every error.  This is
+ * how a saved model is pruned with no GPU, before tfidf_model_import.  A pruned model needs no
+ * options when it is served: the options are not recorded in the model file. */
+int tfidf_model_prune(const tfidf_model* in, const tfidf_prune_params* params, tfidf_model* out);
+
 /* ---------------------------------------------------------------- ingest ---- */
 
 /* Reference input contract (TFIDF.c:98-110,130-147): N = number of entries of `dir`

@@ -308,6 +308,17 @@ struct tfidf_ctx {
     DevBuf ng_in, ng_inoff, ng_bytes[2], ng_off[2], ng_ids[2], ng_a, ng_b, ng_tseg;
     hipEvent_t ev_ng[4] = {};                   /* bounds / sizes / write bounds (created by the first call) */
     tfidf_ngram_info nginfo{};
+    /* vocabulary pruning (tfidf_prune, prune.hip): the keep flags (then the new ranks), the keep
+     * bitmap, the max_features sort's ping-pong buffers, the per-tile counts and first documents,
+     * the emptied-documents counter; and the spare copies of the resident arrays the call writes
+     * into and swaps with the context's own when every step has succeeded (slot_of_rank, df by
+     * rank, out_term, out_cnt, out_score, out_off), each as large as the buffer it stands in for */
+    DevBuf pr_flag, pr_bits, pr_k0, pr_k1, pr_v0, pr_v1, pr_tcnt, pr_tdoc, pr_misc;
+    DevBuf pr_sor, pr_df, pr_term, pr_cnt, pr_score, pr_off;
+    hipEvent_t ev_pr[4] = {};                   /* select / terms / pairs bounds (created by the first call) */
+    tfidf_prune_info pinfo{};
+    uint64_t info_npairs = 0;                   /* the run's P and V as tfidf_last_run_info reports them (a prune */
+    uint32_t info_V = 0;                        /* changes npairs and V, not what the run was) */
 #define WR_NBUF 8
 #define WR_BUF (16ull << 20)
 #define WR_GROUPS 8
@@ -619,6 +630,12 @@ void tfidf_close(tfidf_ctx* ctx) {
         b->release();
     for (hipEvent_t e : ctx->ev_ng)
         if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : ctx->ev_pr)
+        if (e) (void)hipEventDestroy(e);
+    for (DevBuf* b : {&ctx->pr_flag, &ctx->pr_bits, &ctx->pr_k0, &ctx->pr_k1, &ctx->pr_v0, &ctx->pr_v1, &ctx->pr_tcnt,
+                      &ctx->pr_tdoc, &ctx->pr_misc, &ctx->pr_sor, &ctx->pr_df, &ctx->pr_term, &ctx->pr_cnt, &ctx->pr_score,
+                      &ctx->pr_off})
+        b->release();
     for (DevBuf* b : {&ctx->ng_in, &ctx->ng_inoff, &ctx->ng_bytes[0], &ctx->ng_bytes[1], &ctx->ng_off[0], &ctx->ng_off[1],
                       &ctx->ng_ids[0], &ctx->ng_ids[1], &ctx->ng_a, &ctx->ng_b, &ctx->ng_tseg})
         b->release();
@@ -1883,6 +1900,8 @@ extern "C" int tfidf_run(tfidf_ctx* ctx, const tfidf_corpus* in) {
     ctx->have_result = true;
     ctx->have_model = true;
     ctx->have_info = true;
+    ctx->info_npairs = ctx->npairs;
+    ctx->info_V = ctx->V;
     if (ctx->timing) (void)hipEventSynchronize(ctx->ev[S_NSTAGES]);   /* done on the device; the runtime may not know yet */
     if (ctx->timing == 2) {
         for (int i = 0; i < S_NSTAGES; ++i) ctx->ms_stage[i] = 0;
@@ -1989,8 +2008,8 @@ extern "C" int tfidf_last_run_info(tfidf_ctx* ctx, tfidf_run_info* out) {
     info = &full;   /* filled whole here, copied out up to the caller's size below */
     info->nbytes = ctx->run_nbytes;   /* no device round trip: the run read the bounds */
     info->ntokens = ctx->ntokens;
-    info->npairs = ctx->npairs;
-    info->nterms = ctx->V;
+    info->npairs = ctx->info_npairs;
+    info->nterms = ctx->info_V;
     info->nterms_global = ctx->Vg;
     info->nchunks = ctx->nchunks;
     info->partial_records = ctx->nrec_part;
@@ -3773,6 +3792,8 @@ extern "C" int tfidf_model_import(tfidf_ctx* ctx, const tfidf_model* m) {
     ctx->ndocs_total = Nt;
     ctx->ndocs = 0;
     ctx->npairs = 0;
+    ctx->info_npairs = 0;
+    ctx->info_V = V;
     ctx->corpus = tfidf_corpus{};
     ctx->corpus.nbytes = nbytes;   /* VocabRO.corpus_bytes: the blob stands where the corpus does */
     ctx->dev_bytes = ctx->m_blob.as<uint8_t>();
@@ -3797,6 +3818,189 @@ extern "C" int tfidf_last_model_info(const tfidf_ctx* ctx, tfidf_model_info* inf
     if (!ctx || !info || info->size < sizeof(uint64_t)) return TFIDF_E_INVAL;
     const uint64_t n = info->size < sizeof(tfidf_model_info) ? info->size : sizeof(tfidf_model_info);
     tfidf_model_info o = ctx->minfo;
+    o.size = n;
+    memcpy(info, &o, (size_t)n);
+    return TFIDF_OK;
+}
+
+/* ------------------------------------------------------------------- prune ----
+ * Vocabulary pruning by document frequency over the resident result (prune.hip; the parameter
+ * check and the model form are prune_host.c).  Select (flags, the max_features sort, bitmap, new
+ * ranks), the term arrays, the pair pass.  Everything is written into spare buffers of the
+ * context, which change places with the resident ones when every step has succeeded; only
+ * rank_of_slot is rewritten in place, by the last launch.  idf_rank is the score stage's scratch
+ * and has no reader after a run (transform reads the idf by df), so it is left alone. */
+
+/* a spare as large as the buffer it will change places with: after the swap neither a run nor
+ * the next prune has anything to grow */
+static int ensure_spare(DevBuf& spare, const DevBuf& orig, size_t need) {
+    const size_t want = orig.cap > need ? orig.cap : need;
+    if (spare.p && spare.cap >= want) return 0;
+    spare.release();
+    if (tfidf_dev_malloc(&spare.p, want) != hipSuccess) {
+        (void)hipGetLastError();
+        spare.p = nullptr;
+        return -1;
+    }
+    spare.cap = want;
+    return 0;
+}
+
+extern "C" int tfidf_prune(tfidf_ctx* ctx, const tfidf_prune_params* params) {
+    if (!ctx || tfidf_prune_check(params) != TFIDF_OK) return TFIDF_E_INVAL;
+    if (!ctx->have_result || ctx->model_only) return TFIDF_E_STATE;
+    if (ctx->xp && params->max_features) return TFIDF_E_INVAL;   /* the ranks share no term table */
+    const auto wall0 = std::chrono::steady_clock::now();
+    HIPCHK(hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    for (hipEvent_t& e : ctx->ev_pr)
+        if (!e) HIPCHK(hipEventCreate(&e));
+    if (!ctx->ncu) {
+        int n = 0;
+        if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, ctx->device) != hipSuccess || n <= 0) n = 256;
+        ctx->ncu = (uint32_t)n;
+    }
+    const uint32_t V = ctx->V, N = ctx->ndocs, M = params->max_features;
+    const uint64_t P = ctx->npairs, Nt = ctx->ndocs_total;
+    const uint64_t ntiles = P / PR_TILE + 1u;
+    const bool cut = M != 0u && M < V;   /* M >= V cannot remove a survivor */
+    DevBuf& dfb = ctx->xp ? ctx->df_global : ctx->df_local;   /* df_of_run */
+    ENSURE(ctx->pr_flag, ((size_t)V + 1) * 4 + 4);
+    ENSURE(ctx->pr_bits, (((size_t)V + 63) / 64) * 8 + 16);
+    ENSURE(ctx->pr_tcnt, (size_t)(ntiles + 1) * 8);
+    ENSURE(ctx->pr_tdoc, (size_t)(ntiles + 1) * 4);
+    ENSURE(ctx->pr_misc, 256);
+    if (cut) {
+        ENSURE(ctx->pr_k0, (size_t)V * 8 + 8);
+        ENSURE(ctx->pr_k1, (size_t)V * 8 + 8);
+        ENSURE(ctx->pr_v0, (size_t)V * 4 + 4);
+        ENSURE(ctx->pr_v1, (size_t)V * 4 + 4);
+    }
+    if (ensure_spare(ctx->pr_sor, ctx->slot_of_rank, (size_t)V * 4 + 4) || ensure_spare(ctx->pr_df, dfb, (size_t)V * 4 + 4) ||
+        ensure_spare(ctx->pr_term, ctx->out_term, (size_t)P * 4 + 4) || ensure_spare(ctx->pr_cnt, ctx->out_cnt, (size_t)P * 4 + 4) ||
+        ensure_spare(ctx->pr_score, ctx->out_score, (size_t)P * 8 + 8) || ensure_spare(ctx->pr_off, ctx->out_off, ((size_t)N + 1) * 8))
+        return TFIDF_E_NOMEM;
+    {   /* the scans' block sums and the sort's histograms */
+        const uint64_t nb = ((uint64_t)V + 2047) / 2048;
+        const size_t want = scan_scratch((uint64_t)V + 1) + scan_scratch(ntiles + 1) +
+                            (cut ? (size_t)(256 * nb + 1) * 4 + scan_scratch(256 * nb) : 0) + 8192;
+        if (want > ctx->arena_buf.cap && arena_reset(ctx, want) != 0) return TFIDF_E_NOMEM;
+        ctx->arena.used = 0;   /* as format_prepare: nothing of the result lives in the arena */
+    }
+    uint32_t* flag = ctx->pr_flag.as<uint32_t>();   /* the keep flags, then in place the new ranks */
+    uint32_t* bits = ctx->pr_bits.as<uint32_t>();
+    /* ---- select ---- */
+    HIPCHK(hipEventRecord(ctx->ev_pr[0], s));
+    if (launch_pr_range(df_of_run(ctx), V, Nt, params->min_df, params->max_df, flag,
+                        cut ? ctx->pr_k0.as<uint64_t>() : nullptr, ctx->pr_v0.as<uint32_t>(), s)) {
+        HIPCHK(hipGetLastError());
+        return TFIDF_E_HIP;
+    }
+    uint64_t cut_keys[2] = {PR_KEY_DEAD, PR_KEY_DEAD};   /* the sorted keys at positions M - 1 and M */
+    if (cut) {
+        uint32_t byte_mask = 1u << 4;   /* PR_KEY_DEAD's bit; below it the bytes Nt - df can reach */
+        for (int b = 0; b < 4; ++b)
+            if ((Nt >> (8 * b)) != 0) byte_mask |= 1u << b;
+        const int where = radix_sort_u64(ctx->pr_k0.as<uint64_t>(), ctx->pr_v0.as<uint32_t>(), ctx->pr_k1.as<uint64_t>(),
+                                         ctx->pr_v1.as<uint32_t>(), V, byte_mask, ctx->arena, s);
+        if (where < 0) { HIPCHK(hipGetLastError()); return where == -2 ? TFIDF_E_NOMEM : TFIDF_E_HIP; }
+        const uint64_t* ks = where ? ctx->pr_k1.as<uint64_t>() : ctx->pr_k0.as<uint64_t>();
+        const uint32_t* vs = where ? ctx->pr_v1.as<uint32_t>() : ctx->pr_v0.as<uint32_t>();
+        if (launch_pr_take(ks, vs, V, M, flag, s)) { HIPCHK(hipGetLastError()); return TFIDF_E_HIP; }
+        HIPCHK(hipMemcpyAsync(cut_keys, ks + (M - 1u), 16, hipMemcpyDeviceToHost, s));   /* M < V: both exist */
+    }
+    if (launch_pr_bitmap(flag, V, bits, s)) { HIPCHK(hipGetLastError()); return TFIDF_E_HIP; }
+    {
+        const int sc = scan_excl_u32(flag, flag, V, ctx->arena, s);
+        if (sc) { if (sc != -2) HIPCHK(hipGetLastError()); return sc == -2 ? TFIDF_E_NOMEM : TFIDF_E_HIP; }
+    }
+    HIPCHK(hipEventRecord(ctx->ev_pr[1], s));
+    uint32_t V2 = 0;
+    HIPCHK(hipMemcpyAsync(&V2, flag + V, 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    if (V2 > V) return TFIDF_E_STATE;
+    tfidf_prune_info pi{};
+    pi.nterms_before = V;
+    pi.npairs_before = P;
+    /* the cut removed a survivor of the range test exactly when position M holds one */
+    if (cut && cut_keys[1] != PR_KEY_DEAD && cut_keys[0] <= Nt) pi.cut_df = (uint32_t)(Nt - cut_keys[0]);
+    float ms = 0;
+    (void)hipEventElapsedTime(&ms, ctx->ev_pr[0], ctx->ev_pr[1]);
+    pi.ms_select = ms;
+    if (V2 == V) {   /* nothing to remove: every byte stays */
+        pi.nterms_after = V;
+        pi.npairs_after = P;
+        pi.ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - wall0).count();
+        ctx->pinfo = pi;
+        return TFIDF_OK;
+    }
+    /* ---- terms ---- */
+    PrTerms ta{bits, flag, V, ctx->slot_of_rank.as<uint32_t>(), df_of_run(ctx), ctx->pr_sor.as<uint32_t>(),
+               ctx->pr_df.as<uint32_t>()};
+    if (launch_pr_terms(ta, s)) { HIPCHK(hipGetLastError()); return TFIDF_E_HIP; }
+    HIPCHK(hipEventRecord(ctx->ev_pr[2], s));
+    /* ---- pairs ---- */
+    HIPCHK(hipMemsetAsync(ctx->pr_misc.p, 0, 16, s));
+    PrPairs pa{};
+    pa.out_off = ctx->out_off.as<uint64_t>();
+    pa.out_term = ctx->out_term.as<uint32_t>();
+    pa.out_cnt = ctx->out_cnt.as<uint32_t>();
+    pa.out_score = ctx->out_score.as<double>();
+    pa.npairs = P;
+    pa.ndocs = N;
+    pa.V = V;
+    pa.bits = bits;
+    pa.new_rank = flag;
+    pa.ntiles = ntiles;
+    pa.tile_cnt = ctx->pr_tcnt.as<uint64_t>();
+    pa.tile_doc = ctx->pr_tdoc.as<uint32_t>();
+    pa.new_term = ctx->pr_term.as<uint32_t>();
+    pa.new_cnt = ctx->pr_cnt.as<uint32_t>();
+    pa.new_score = ctx->pr_score.as<double>();
+    pa.new_off = ctx->pr_off.as<uint64_t>();
+    pa.emptied = ctx->pr_misc.as<uint32_t>();
+    if (launch_pr_tiledoc(pa, s) || launch_pr_count(pa, ctx->ncu, s)) { HIPCHK(hipGetLastError()); return TFIDF_E_HIP; }
+    {
+        const int sc = scan_excl_u64(pa.tile_cnt, pa.tile_cnt, ntiles, ctx->arena, s);
+        if (sc) { if (sc != -2) HIPCHK(hipGetLastError()); return sc == -2 ? TFIDF_E_NOMEM : TFIDF_E_HIP; }
+    }
+    if (launch_pr_write(pa, ctx->ncu, s) || launch_pr_emptied(pa, s)) { HIPCHK(hipGetLastError()); return TFIDF_E_HIP; }
+    HIPCHK(hipEventRecord(ctx->ev_pr[3], s));
+    uint64_t P2 = 0;
+    uint32_t emptied = 0;
+    HIPCHK(hipMemcpyAsync(&P2, pa.tile_cnt + ntiles, 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(&emptied, pa.emptied, 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));   /* every spare is written: from here on the call cannot fail half-way */
+    if (P2 > P) return TFIDF_E_STATE;
+    if (launch_pr_slots(ta, ctx->rank_of_slot.as<uint32_t>(), ctx->vcap, s)) { HIPCHK(hipGetLastError()); return TFIDF_E_HIP; }
+    HIPCHK(hipStreamSynchronize(s));
+    std::swap(ctx->slot_of_rank, ctx->pr_sor);
+    std::swap(dfb, ctx->pr_df);
+    std::swap(ctx->out_term, ctx->pr_term);
+    std::swap(ctx->out_cnt, ctx->pr_cnt);
+    std::swap(ctx->out_score, ctx->pr_score);
+    std::swap(ctx->out_off, ctx->pr_off);
+    ctx->V = V2;
+    ctx->npairs = P2;
+    ctx->text_valid = false;
+    ctx->tmeta_valid = false;
+    ctx->norm_valid = false;   /* bm25_L stays: docSize is unchanged */
+    pi.nterms_after = V2;
+    pi.npairs_after = P2;
+    pi.docs_emptied = emptied;
+    (void)hipEventElapsedTime(&ms, ctx->ev_pr[1], ctx->ev_pr[2]);
+    pi.ms_terms = ms;
+    (void)hipEventElapsedTime(&ms, ctx->ev_pr[2], ctx->ev_pr[3]);
+    pi.ms_pairs = ms;
+    pi.ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - wall0).count();
+    ctx->pinfo = pi;
+    return TFIDF_OK;
+}
+
+extern "C" int tfidf_last_prune_info(const tfidf_ctx* ctx, tfidf_prune_info* info) {
+    if (!ctx || !info || info->size < sizeof(uint64_t)) return TFIDF_E_INVAL;
+    const uint64_t n = info->size < sizeof(tfidf_prune_info) ? info->size : sizeof(tfidf_prune_info);
+    tfidf_prune_info o = ctx->pinfo;
     o.size = n;
     memcpy(info, &o, (size_t)n);
     return TFIDF_OK;

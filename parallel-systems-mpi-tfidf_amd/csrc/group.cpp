@@ -560,6 +560,21 @@ int tfidf_group_run(tfidf_group* g, const tfidf_corpus* shards) {
     return peer;
 }
 
+/* tfidf_prune on every rank at once.  df is global, so min_df / max_df select the same words
+ * on every rank; the shards share no term table, which is why there is no cut by max_features
+ * over a group (a global cut is left out). */
+int tfidf_group_prune(tfidf_group* g, const tfidf_prune_params* params) {
+    if (!g || tfidf_prune_check(params) != TFIDF_OK || params->max_features != 0u) return TFIDF_E_INVAL;
+    std::vector<int> rc((size_t)g->n, TFIDF_OK);
+    std::vector<std::thread> th;
+    for (int r = 1; r < g->n; ++r) th.emplace_back([&, r] { rc[r] = tfidf_prune(g->ctx[r], params); });
+    rc[0] = tfidf_prune(g->ctx[0], params);
+    for (auto& t : th) t.join();
+    for (int r = 0; r < g->n; ++r)
+        if (rc[r]) return rc[r];
+    return TFIDF_OK;
+}
+
 int tfidf_group_write_output(tfidf_group* g, const char* path) {
     if (!g || !path) return TFIDF_E_INVAL;
     std::vector<int> rc((size_t)g->n, TFIDF_OK);

@@ -817,4 +817,64 @@ int launch_ng_offsets(const NgArgs& a, hipStream_t s);
  * 16-byte store per lane */
 int launch_ng_write(const NgArgs& a, hipStream_t s);
 
+/* ---- vocabulary pruning by document frequency (prune.hip, tfidf_prune) ---- */
+#define PR_TILE 1024u              /* pairs a workgroup owns per step: 256 lanes x four pairs (one 16-byte load of out_term) */
+#define PR_LDS_TERMS (1u << 18)    /* the keep bitmap is staged in LDS up to this many terms (32 KiB: four
+                                      workgroups of the pair pass per CU); beyond it is read through L2 */
+#define PR_KEY_DEAD (1ull << 32)   /* sort key of a term that failed the range test (N - df < 2^32 sorts in front) */
+/* one lane per term rank: flag[r] = 1 when df[r] passes the range test, else 0; with key != null
+ * also key[r] = Nt - df[r] (PR_KEY_DEAD for a failed term) and val[r] = r for the max_features sort */
+int launch_pr_range(const uint32_t* df, uint32_t V, uint64_t Nt, uint32_t min_df, uint32_t max_df, uint32_t* flag,
+                    uint64_t* key, uint32_t* val, hipStream_t s);
+/* after the stable sort of (key, val): flag[val[p]] = p < M && key[p] != PR_KEY_DEAD, one lane per position */
+int launch_pr_take(const uint64_t* key, const uint32_t* val, uint32_t V, uint32_t M, uint32_t* flag, hipStream_t s);
+/* bits: word w bit b = flag[32 w + b] != 0; 2 * ceil(V / 64) words are written (a wave's ballot each pair) */
+int launch_pr_bitmap(const uint32_t* flag, uint32_t V, uint32_t* bits, hipStream_t s);
+/* new_rank = the exclusive scan of flag (V + 1 entries, new_rank[V] = V').  One lane per old rank r:
+ * a kept r scatters slot_of_rank and df to new_rank[r] */
+struct PrTerms {
+    const uint32_t* bits;
+    const uint32_t* new_rank;
+    uint32_t V;
+    const uint32_t* slot_of_rank;
+    const uint32_t* df;
+    uint32_t* new_slot_of_rank;
+    uint32_t* new_df;
+};
+int launch_pr_terms(const PrTerms& a, hipStream_t s);
+/* the one step in place, run last: rank_of_slot[slot_of_rank[r]] = new_rank[r] for a kept r and
+ * QUERY_NO_TERM for a pruned one (its key keeps its slot and stops resolving: vocab_find_rank);
+ * a slot >= slot_cap is skipped */
+int launch_pr_slots(const PrTerms& a, uint32_t* rank_of_slot, uint64_t slot_cap, hipStream_t s);
+/* The pair pass over tiles of PR_TILE pairs, ntiles = npairs / PR_TILE + 1 (the tile that holds
+ * index npairs exists, for the documents that end there).  count: tile_cnt[t] = kept pairs of
+ * tile t; the caller scans tile_cnt in place (tile_cnt[ntiles] = P').  write: the kept pairs to
+ * their compacted positions with new_rank[term], and new_off[j] = the kept pairs before
+ * min(out_off[j], npairs) for the documents whose offset lies in the tile (tile_doc, from
+ * launch_pr_tiledoc).  Persistent workgroups (grid <= ntiles) that own tiles t = block, block +
+ * grid, ..: every tile's result is its own, so the outcome does not depend on the grid. */
+struct PrPairs {
+    const uint64_t* out_off;     /* ndocs + 1 */
+    const uint32_t* out_term;
+    const uint32_t* out_cnt;
+    const double* out_score;
+    uint64_t npairs;
+    uint32_t ndocs, V;
+    const uint32_t* bits;
+    const uint32_t* new_rank;
+    uint64_t ntiles;
+    uint64_t* tile_cnt;          /* ntiles + 1 */
+    uint32_t* tile_doc;          /* ntiles + 1: the first j with min(out_off[j], npairs) >= t * PR_TILE */
+    uint32_t* new_term;
+    uint32_t* new_cnt;
+    double* new_score;
+    uint64_t* new_off;           /* ndocs + 1 */
+    uint32_t* emptied;           /* one word, zeroed by the caller: documents that lost their last pair */
+};
+int launch_pr_tiledoc(const PrPairs& a, hipStream_t s);
+int launch_pr_count(const PrPairs& a, uint32_t ncu, hipStream_t s);
+int launch_pr_write(const PrPairs& a, uint32_t ncu, hipStream_t s);
+/* after the write pass: one lane per document, one integer add per workgroup into *emptied */
+int launch_pr_emptied(const PrPairs& a, hipStream_t s);
+
 #endif

@@ -122,8 +122,23 @@
  * input/ is shingled in HBM after the analyzer (every shard on its own GPU), the lines of
  * --query FILE and the documents of --transform DIR on the host, also under --model FILE.  The
  * model file does not record the option.  Without --ngrams nothing new is called.
+ *
+ * Vocabulary pruning by document frequency (tfidf_prune / tfidf_group_prune after the run,
+ * tfidf_model_prune under --model FILE), before output.txt and every other file:
+ *   --min-df X             drop the words in fewer than X documents;
+ *   --max-df X             drop the words in more than X documents.  X is a count, or with a '.'
+ *                          a fraction of N in (0, 1]: ceil(X * N) for --min-df, floor(X * N) for
+ *                          --max-df;
+ *   --max-features M       of the words that pass, keep the M in the most documents (ties by word
+ *                          order).  One shard only: with --gpus or --shards above 1 it is refused
+ *                          (exit 2), like --clusters.
+ * Scores, counts and docSize are the run's: nothing is recomputed, so --transform input against
+ * the pruned result reproduces the pruned output.txt.  A model saved after pruning holds the
+ * kept words only and needs no option when it is served.  Without the options nothing new is
+ * called and every byte of every output is as before.
  */
 #include <dirent.h>
+#include <math.h>
 #include <pthread.h>
 #include <stddef.h>
 #include <stdio.h>
@@ -554,11 +569,71 @@ static int save_model(tfidf_ctx* ctx, tfidf_group* g) {
     return rc;
 }
 
-/* --model: no run; the file's model is imported and --transform scored against it */
+/* ------------------------------------------------------------------ prune -- */
+
+/* --min-df X, --max-df X, --max-features M: the vocabulary is pruned after the run (after every
+ * shard's run) and before output.txt and every other file, so all of them see the pruned
+ * result.  X is a count, or with a '.' a fraction of N in (0, 1]: ceil(X * N) for --min-df,
+ * floor(X * N) for --max-df, in binary64.  Without the options nothing is called. */
+static struct {
+    int on;
+    int min_frac, max_frac;
+    double min_x, max_x;
+    uint32_t min_df, max_df, max_features;
+} g_prune = {0, 0, 0, 0.0, 0.0, 0, 0, 0};
+
+/* X of --min-df / --max-df: 0 on success */
+static int parse_df(const char* a, int* frac, double* x, uint32_t* n) {
+    char* end = NULL;
+    if (strchr(a, '.')) {
+        const double v = strtod(a, &end);
+        if (end == a || *end || !(v > 0.0) || !(v <= 1.0)) return -1;
+        *frac = 1;
+        *x = v;
+        return 0;
+    }
+    if (a[0] < '0' || a[0] > '9') return -1;
+    const unsigned long long v = strtoull(a, &end, 10);
+    if (end == a || *end || v > 0xFFFFFFFFull) return -1;
+    *frac = 0;
+    *n = (uint32_t)v;
+    return 0;
+}
+
+/* the parameters for a corpus of N documents; TFIDF_E_INVAL when the fractions give min > max */
+static int prune_params_for(uint64_t N, tfidf_prune_params* p) {
+    memset(p, 0, sizeof(*p));
+    p->size = sizeof(*p);
+    p->min_df = g_prune.min_frac ? (uint32_t)ceil(g_prune.min_x * (double)N) : g_prune.min_df;
+    p->max_df = g_prune.max_frac ? (uint32_t)floor(g_prune.max_x * (double)N) : g_prune.max_df;
+    p->max_features = g_prune.max_features;
+    if (g_prune.max_frac && p->max_df == 0) {   /* no df is <= 0: nothing survives (max_df = 0 would mean no bound) */
+        p->min_df = 0xFFFFFFFFu;
+        return TFIDF_OK;
+    }
+    return tfidf_prune_check(p);
+}
+
+static int prune_bad_range(void) {
+    fprintf(stderr, "tfidf: --min-df is above --max-df\n");
+    return 2;
+}
+
+/* --model: no run; the file's model is pruned on the host (with the prune options), imported and
+ * --transform scored against it */
 static int run_model(int device) {
     tfidf_model m;
     int rc = tfidf_model_load(g_model.load, &m);
     if (rc) { fprintf(stderr, "tfidf: %s: %s\n", g_model.load, tfidf_strerror(rc)); return 3; }
+    if (g_prune.on) {
+        tfidf_prune_params pp;
+        tfidf_model pruned;
+        if (prune_params_for(m.ndocs_total, &pp) != TFIDF_OK) { tfidf_model_free(&m); return prune_bad_range(); }
+        rc = tfidf_model_prune(&m, &pp, &pruned);
+        tfidf_model_free(&m);
+        if (rc) return fail(rc);
+        m = pruned;
+    }
     tfidf_ctx* ctx = NULL;
     rc = tfidf_open(device, &ctx);
     if (!rc) rc = tfidf_model_import(ctx, &m);
@@ -587,6 +662,11 @@ static int run_single(int device, const char* indir, const char* outpath, int de
     if (!rc && g_ng.on) rc = tfidf_ngrams(ctx, &g_ng.p, &c, TFIDF_NG_SLOT_CORPUS, &c);
     if (!rc) rc = tfidf_run(ctx, &c);
     if (!rc && debug) rc = debug_jobs(ctx);
+    if (!rc && g_prune.on) {
+        tfidf_prune_params pp;
+        if (prune_params_for(c.ndocs_total ? c.ndocs_total : c.ndocs, &pp) != TFIDF_OK) { tfidf_close(ctx); return prune_bad_range(); }
+        rc = tfidf_prune(ctx, &pp);
+    }
     if (rc) { tfidf_close(ctx); return fail(rc); }
     tfidf_run_info ri;
     ri.size = sizeof(ri);
@@ -698,6 +778,11 @@ static int run_sharded(int ngpus, int nshards, const char* indir, const char* ou
     const double t_ingest = wall_ms();
     if (!rc) rc = tfidf_group_run(g, cs);
     for (int r = 0; r < nshards && !rc && debug; ++r) rc = debug_jobs(tfidf_group_ctx(g, r));
+    if (!rc && g_prune.on) {
+        tfidf_prune_params pp;
+        if (prune_params_for(plan.ndocs, &pp) != TFIDF_OK) { tfidf_group_close(g); tfidf_plan_free(&plan); return prune_bad_range(); }
+        rc = tfidf_group_prune(g, &pp);
+    }
     if (rc) { tfidf_group_close(g); tfidf_plan_free(&plan); return fail(rc); }
     const double t_run = wall_ms();
     /* each GPU formats its shard; the texts are written in shard order (TFIDF.c:253-282) */
@@ -740,8 +825,9 @@ static int usage(void) {
                     "[--similar K [--similar-docs FILE] [--similar-file FILE]] "
                     "[--clusters K [--clusters-iter I] [--clusters-seeds FILE] [--clusters-terms T] [--clusters-file FILE]] "
                     "[--transform DIR [--transform-file FILE]] [--save-model FILE] "
+                    "[--min-df X] [--max-df X] [--max-features M] "
                     "[--lower] [--strip-punct] [--min-token N] [--stopwords FILE] [--stem] [--utf8] [--ngrams SPEC [--ngram-joiner C]]\n"
-                    "       tfidf --model FILE --transform DIR [--transform-file FILE] [--device D] "
+                    "       tfidf --model FILE --transform DIR [--transform-file FILE] [--device D] [--min-df X] [--max-df X] [--max-features M] "
                     "[--lower] [--strip-punct] [--min-token N] [--stopwords FILE] [--stem] [--utf8] [--ngrams SPEC [--ngram-joiner C]]\n"
                     "  --similar K without --similar-docs searches for every document: "
                     "ceil(N / group) scans of the scored pairs, group <= 64\n"
@@ -754,6 +840,10 @@ static int usage(void) {
                     "not imply --lower, and the words of --stopwords FILE are not stemmed\n"
                     "  --utf8 extends --lower and --strip-punct to UTF-8 sequences: cased letters whose lowercase "
                     "has the same length are folded, punctuation, symbols and separators are blanked\n"
+                    "  --min-df X and --max-df X drop the words in fewer than / more than X documents before anything "
+                    "is written (X with a '.': a fraction of N in (0, 1]); --max-features M keeps the M words in the most "
+                    "documents (ties by word order; one shard only); scores and docSize are unchanged, and a model "
+                    "saved after pruning needs no option when it is served\n"
                     "  --ngrams SPEC adds word n-grams behind the analyzer: SPEC is N (= 1-N) or A-B with 1 <= A <= B <= 8; "
                     "the words of a gram are joined by '_' or by the byte of --ngram-joiner C\n");
     return 2;
@@ -836,6 +926,21 @@ int main(int argc, char** argv) {
             if (k < 1 || k > (long)TFIDF_KMEANS_MAX_K) { fprintf(stderr, "tfidf: --clusters takes 1..%u\n", TFIDF_KMEANS_MAX_K); return 2; }
             g_clusters.k = (uint32_t)k;
         }
+        else if ((!strcmp(argv[i], "--min-df") || !strcmp(argv[i], "--max-df")) && i + 1 < argc) {
+            const int is_max = !strcmp(argv[i], "--max-df");
+            if (parse_df(argv[++i], is_max ? &g_prune.max_frac : &g_prune.min_frac, is_max ? &g_prune.max_x : &g_prune.min_x,
+                         is_max ? &g_prune.max_df : &g_prune.min_df) != 0) {
+                fprintf(stderr, "tfidf: --min-df and --max-df take a count, or with a '.' a fraction of N in (0, 1]\n");
+                return 2;
+            }
+            g_prune.on = 1;
+        }
+        else if (!strcmp(argv[i], "--max-features") && i + 1 < argc) {
+            const long long v = atoll(argv[++i]);
+            if (v < 1 || v > 0xFFFFFFFFll) { fprintf(stderr, "tfidf: --max-features takes 1..4294967295\n"); return 2; }
+            g_prune.max_features = (uint32_t)v;
+            g_prune.on = 1;
+        }
         else if (!strcmp(argv[i], "--similar-docs") && i + 1 < argc) g_similar.docs = argv[++i];
         else if (!strcmp(argv[i], "--similar-file") && i + 1 < argc) g_similar.file = argv[++i];
         else if (!strcmp(argv[i], "--similar") && i + 1 < argc) {
@@ -849,6 +954,8 @@ int main(int argc, char** argv) {
     }
     if (g_an.on && load_stopwords() != TFIDF_OK) return 2;
     if (g_ng.on ? tfidf_ngram_check(&g_ng.p) != TFIDF_OK : g_ng.p.joiner != 0) return usage();   /* a separator as joiner; a joiner alone */
+    if (g_prune.on && !g_prune.min_frac && !g_prune.max_frac && g_prune.max_df != 0 && g_prune.min_df > g_prune.max_df)
+        return prune_bad_range();
     if (g_model.load) {   /* a model holds no pairs: nothing to rank, list or print */
         if (!g_transform.dir) {
             fprintf(stderr, "tfidf: --model needs --transform DIR\n");
@@ -881,6 +988,11 @@ int main(int argc, char** argv) {
     if (g_clusters.k && nshards != 1) {
         fprintf(stderr, "tfidf: --clusters runs on one shard only: the shards' term tables differ, so they share no "
                         "centroid matrix (drop --gpus / --shards)\n");
+        return 2;
+    }
+    if (g_prune.max_features && nshards != 1) {
+        fprintf(stderr, "tfidf: --max-features runs on one shard only: the shards' term tables differ, so they share no "
+                        "ranking of the words (drop --gpus / --shards; --min-df and --max-df work on any number)\n");
         return 2;
     }
     if (nshards == 1) return run_single(device >= 0 ? device : 0, indir, outpath, debug, stats);

@@ -49,6 +49,7 @@ EXPORTS = [
     "tfidf_analyzer_check", "tfidf_analyze_host", "tfidf_analyze", "tfidf_last_analyze_info",
     "tfidf_stem_porter",
     "tfidf_ngram_check", "tfidf_ngrams_host", "tfidf_ngrams", "tfidf_last_ngram_info",
+    "tfidf_prune_check", "tfidf_prune", "tfidf_group_prune", "tfidf_last_prune_info", "tfidf_model_prune",
 ]
 QUERY_MAX_K = 1024  # TFIDF_QUERY_MAX_K
 TERMS_MAX_K = 1024  # TFIDF_TERMS_MAX_K
@@ -280,6 +281,22 @@ class NgramInfo(C.Structure):
     ]
 
 
+class PruneParams(C.Structure):
+    _fields_ = [
+        ("size", C.c_uint64), ("min_df", C.c_uint32), ("max_df", C.c_uint32), ("max_features", C.c_uint32),
+        ("reserved", C.c_uint32),
+    ]
+
+
+class PruneInfo(C.Structure):
+    _fields_ = [
+        ("size", C.c_uint64), ("nterms_before", C.c_uint32), ("nterms_after", C.c_uint32),
+        ("npairs_before", C.c_uint64), ("npairs_after", C.c_uint64), ("docs_emptied", C.c_uint32),
+        ("cut_df", C.c_uint32), ("ms_select", C.c_double), ("ms_terms", C.c_double), ("ms_pairs", C.c_double),
+        ("ms_total", C.c_double),
+    ]
+
+
 class DirPlan(C.Structure):
     _fields_ = [
         ("ndocs", C.c_uint32), ("nshards", C.c_uint32), ("doc_ids", C.POINTER(C.c_uint32)),
@@ -394,6 +411,11 @@ def lib() -> C.CDLL:
                                         C.POINTER(C.c_void_p), C.POINTER(C.c_uint64), C.POINTER(C.c_void_p)]
         L.tfidf_ngrams.argtypes = [C.c_void_p, C.POINTER(NgramParams), C.POINTER(Corpus), C.c_uint32, C.POINTER(Corpus)]
         L.tfidf_last_ngram_info.argtypes = [C.c_void_p, C.POINTER(NgramInfo)]
+        L.tfidf_prune_check.argtypes = [C.POINTER(PruneParams)]
+        L.tfidf_prune.argtypes = [C.c_void_p, C.POINTER(PruneParams)]
+        L.tfidf_group_prune.argtypes = [C.c_void_p, C.POINTER(PruneParams)]
+        L.tfidf_last_prune_info.argtypes = [C.c_void_p, C.POINTER(PruneInfo)]
+        L.tfidf_model_prune.argtypes = [C.POINTER(Model), C.POINTER(PruneParams), C.POINTER(Model)]
         if L.tfidf_abi_version() != ABI_VERSION:
             raise RuntimeError(f"{LIB_PATH}: ABI version {L.tfidf_abi_version()}, binding expects {ABI_VERSION} "
                                f"(stale build: rebuild with __graft_entry__.build())")
@@ -698,6 +720,32 @@ def ngrams_host(data, off, min_n: int = 1, max_n: int = 2, joiner: int = 0):
         lib().tfidf_free(ob)
         lib().tfidf_free(oo)
     return out, out_off
+
+
+def prune_params(min_df: int = 0, max_df: int = 0, max_features: int = 0) -> PruneParams:
+    """A tfidf_prune_params: min_df 0 or 1 = no lower bound, max_df 0 = no upper bound,
+    max_features 0 = no cut."""
+    p = PruneParams()
+    p.size = C.sizeof(PruneParams)
+    p.min_df, p.max_df, p.max_features = min_df, max_df, max_features
+    return p
+
+
+def prune_check(p: PruneParams) -> int:
+    """tfidf_prune_check (host only): 0, or E_INVAL; None stands for a NULL pointer."""
+    return int(lib().tfidf_prune_check(None if p is None else C.byref(p)))
+
+
+def model_prune(model: dict, min_df: int = 0, max_df: int = 0, max_features: int = 0) -> dict:
+    """tfidf_model_prune (host only): the model dict without the pruned terms."""
+    m, keep = _model_struct(model)
+    p = prune_params(min_df, max_df, max_features)
+    out = Model()
+    _chk(lib().tfidf_model_prune(C.byref(m), C.byref(p), C.byref(out)), "tfidf_model_prune")
+    try:
+        return _model_dict(out)
+    finally:
+        lib().tfidf_model_free(C.byref(out))
 
 
 def synth_host(seed: int, V: int, mode: int, cdf, doc_ids, ntok):
@@ -1057,6 +1105,20 @@ class Engine:
         _chk(lib().tfidf_last_model_info(self.h, C.byref(t)), "tfidf_last_model_info")
         return {k: getattr(t, k) for k, _ in ModelInfo._fields_ if k not in ("size", "reserved")}
 
+    def prune(self, min_df: int = 0, max_df: int = 0, max_features: int = 0, params: PruneParams = None) -> dict:
+        """Removes the terms outside [min_df, max_df] or behind the max_features cut, and their
+        pairs, from the resident result (tfidf_prune); returns prune_info()."""
+        p = params if params is not None else prune_params(min_df, max_df, max_features)
+        _chk(lib().tfidf_prune(self.h, C.byref(p)), "tfidf_prune")
+        return self.prune_info()
+
+    def prune_info(self) -> dict:
+        """Counters and device times of the last prune (tfidf_last_prune_info)."""
+        t = PruneInfo()
+        t.size = C.sizeof(PruneInfo)
+        _chk(lib().tfidf_last_prune_info(self.h, C.byref(t)), "tfidf_last_prune_info")
+        return {k: getattr(t, k) for k, _ in PruneInfo._fields_ if k != "size"}
+
     @contextlib.contextmanager
     def fetched(self):
         """The last run's result as numpy views of the library's host arrays (tfidf_fetch
@@ -1200,6 +1262,12 @@ class Group:
             return _model_dict(m)
         finally:
             lib().tfidf_model_free(C.byref(m))
+
+    def prune(self, min_df: int = 0, max_df: int = 0, max_features: int = 0) -> None:
+        """tfidf_group_prune: every rank prunes its shard by the global df; max_features != 0 is
+        E_INVAL."""
+        p = prune_params(min_df, max_df, max_features)
+        _chk(lib().tfidf_group_prune(self.h, C.byref(p)), "tfidf_group_prune")
 
     def transform_corpus(self, c: Corpus) -> dict:
         """Group.transform of a tfidf_corpus (a device batch is E_INVAL)."""
