@@ -1189,6 +1189,116 @@ int tfidf_last_prune_info(const tfidf_ctx* ctx, tfidf_prune_info* info);
  * options when it is served: the options are not recorded in the model file. */
 int tfidf_model_prune(const tfidf_model* in, const tfidf_prune_params* params, tfidf_model* out);
 
+/* --------------------------------------------------------------- weighting -- */
+
+/* Weighting schemes over the resident result of the last run: sublinear tf, smooth idf and L1 /
+ * L2 row norms.  tfidf_run always computes the reference's fl(fl(count / docSize) * log(N / df))
+ * (TFIDF.c:202,243-244); tfidf_reweight replaces the scores of the resident pairs by another
+ * scheme, computed from the integers (count, docSize, df, N), never from the scores it finds.
+ *
+ * All arithmetic is IEEE binary64, round to nearest; fl() marks every rounding; no product is
+ * fused into an add; log is the host's libm log and is never evaluated on the device (the rule
+ * the run's idf table follows); (double) of an integer rounds to nearest.
+ *
+ *   tf(c, ds)   TFIDF_TF_RATIO   fl((double)c / (double)ds)                    TFIDF.c:202
+ *               TFIDF_TF_RAW     (double)c
+ *               TFIDF_TF_LOG     fl(1.0 + log((double)c))                      sublinear tf
+ *               TFIDF_TF_BINARY  1.0
+ *   idf(df)     TFIDF_IDF_REF    log(1.0 * N / df): the run's own table entry, its bits
+ *               TFIDF_IDF_SMOOTH fl(log(fl(fl((double)N + 1.0) / fl((double)df + 1.0))) + 1.0)
+ *               TFIDF_IDF_PLUS1  fl(log(1.0 * N / df) + 1.0)
+ *               TFIDF_IDF_NONE   1.0
+ *   w(d, t)     fl(tf * idf)
+ *   norm        TFIDF_NORM_NONE  score = w
+ *               TFIDF_NORM_L2    sq = ((+0.0 + fl(w1*w1)) + fl(w2*w2)) + .. over d's resident pairs
+ *                                in pair order (tfidf_similar's sq(d) applied to w); n = sqrt(sq),
+ *                                correctly rounded; score = fl(w / n); n == 0: the scores stay w
+ *               TFIDF_NORM_L1    s = ((+0.0 + w1) + w2) + ..; score = fl(w / s); s == 0: the
+ *                                scores stay w
+ * c, ds and df are the resident pair's wordCount, its document's docSize and the run's global df:
+ * the integers tfidf_fetch returns; N is the run's ndocs_total.  Every score is >= +0.0 and
+ * finite, so bit patterns still order like values (tfidf_query, tfidf_top_terms).  Two static
+ * limits keep every score inside the "%.16f" formatter's range [0, 2^63 / 10^16):
+ *   - TFIDF_TF_RAW with TFIDF_NORM_NONE is TFIDF_E_INVAL (a raw count times an idf has no bound);
+ *   - TFIDF_TF_LOG with TFIDF_NORM_NONE and N >= 2^48 is TFIDF_E_INVAL: below that N the product
+ *     stays under (1 + ln 2^32) * (ln 2^48 + 1) < 23.2 * 34.3 < 922; the others stay under 46.
+ * `size` is set by the caller to sizeof(tfidf_weighting). */
+enum { TFIDF_TF_RATIO = 0, TFIDF_TF_RAW = 1, TFIDF_TF_LOG = 2, TFIDF_TF_BINARY = 3 };
+enum { TFIDF_IDF_REF = 0, TFIDF_IDF_SMOOTH = 1, TFIDF_IDF_PLUS1 = 2, TFIDF_IDF_NONE = 3 };
+enum { TFIDF_NORM_NONE = 0, TFIDF_NORM_L2 = 1, TFIDF_NORM_L1 = 2 };
+typedef struct tfidf_weighting {
+    uint64_t size;
+    uint32_t tf, idf, norm, reserved;
+} tfidf_weighting;
+/* Host only.  TFIDF_E_INVAL for: NULL; size < sizeof(tfidf_weighting); an unknown tf, idf or norm
+ * value; non-zero reserved; TFIDF_TF_RAW with TFIDF_NORM_NONE.  The limit that depends on N is
+ * checked where N is known (tfidf_reweight, tfidf_result_reweight). */
+int tfidf_weighting_check(const tfidf_weighting* w);
+/* Replaces the scores of the resident pairs by the scheme's.
+ *   - reweight(a) then reweight(b) equals reweight(b); {RATIO, REF, NONE} restores the run's bits
+ *     exactly; a call whose scheme is already active changes no byte (the formatted text stays
+ *     valid);
+ *   - tfidf_fetch after the call equals the fetch before it with pair_score replaced; the
+ *     formatted text has the same lines with new digits; out_off, terms, counts, df, docSize and
+ *     N are untouched; BM25 is unaffected; the norms of tfidf_similar are recomputed;
+ *   - the scheme is part of the context's state until the next tfidf_run or tfidf_model_import,
+ *     which both reset it to the reference (a run after a prune gives the unpruned result
+ *     likewise);
+ *   - tfidf_transform follows the active scheme, so transforming the run's own corpus still
+ *     reproduces the resident pairs bit for bit: the same tf, idf and w, the norm over the row's
+ *     in-vocabulary pairs in pair order; out-of-vocabulary tokens count in doc_size as before;
+ *   - on a context that holds only an imported model the call sets the scheme for
+ *     tfidf_transform (there are no pairs to rewrite).  The model file does not record the
+ *     scheme, as it does not record the analyzer: whoever serves from a model passes it again;
+ *   - with tfidf_prune the L1 / L2 norm runs over the pairs resident at the time of the call:
+ *     prune then reweight normalises over the kept words (what a vectoriser with a limited
+ *     vocabulary does), reweight then prune keeps the bits of the unpruned norm.
+ * TFIDF_E_INVAL for a NULL ctx, parameters that fail the check, or TFIDF_TF_LOG with
+ * TFIDF_NORM_NONE on N >= 2^48.  TFIDF_E_STATE only when the context holds neither a run nor a
+ * model.  TFIDF_E_CAPACITY (TFIDF_TF_LOG) when more than 2^20 pairs hold a count above the
+ * tabulated range of 2^16: their list is bounded; no score has been written then.  A failed call
+ * leaves the scores as they were: the new ones go into a spare buffer of the context (the one
+ * tfidf_prune uses) that changes places with the resident one when every step has succeeded.
+ * A repeated run -> reweight sequence allocates nothing after the first (tfidf_alloc_stats).
+ * With a communicator attached the call is local: N and df are global and a document's pairs live
+ * in one shard, so every shard computes what a single shard would.  No floating-point atomics:
+ * the outcome does not depend on the grid or on which of the two launches takes a document. */
+int tfidf_reweight(tfidf_ctx* ctx, const tfidf_weighting* params);
+/* The active scheme ({RATIO, REF, NONE} after a run or an import).  `out->size` is set by the
+ * caller.  TFIDF_E_INVAL for NULL or a short size. */
+int tfidf_weighting_get(const tfidf_ctx* ctx, tfidf_weighting* out);
+/* The same on every rank of a group at once (one host thread per rank).  After it
+ * tfidf_group_write_output, _query, _similar and _transform equal a reweighted single-shard run
+ * of the same corpus.  Under a norm tfidf_group_transform lets the ranks transform with the norm
+ * off (a rank sees only its own vocabulary's part of a row) and normalises each merged row on the
+ * host by the definition above.  Returns the lowest rank's error. */
+int tfidf_group_reweight(tfidf_group* g, const tfidf_weighting* params);
+/* Counters of the last tfidf_reweight (the caller sets `size` = sizeof, as tfidf_query_info). */
+typedef struct tfidf_reweight_info {
+    uint64_t size;
+    uint32_t tf, idf, norm;   /* the scheme of the call */
+    uint32_t changed;         /* 0: the scheme was already active, nothing was written */
+    uint64_t npairs;          /* pairs rewritten */
+    uint32_t ndocs;
+    uint32_t zero_norm_docs;  /* documents that hold pairs and whose L1 / L2 norm is 0 */
+    uint64_t nlogs;           /* distinct logs the host computed for this call (idf and tf tables) */
+    uint32_t max_count;       /* TFIDF_TF_LOG: the largest wordCount (0 otherwise) */
+    uint32_t listed_counts;   /* TFIDF_TF_LOG: distinct counts above the tabulated range */
+    uint32_t big_docs;        /* documents the one-workgroup-per-document launch took */
+    uint32_t reserved;
+    double   ms_tables;       /* device times (HIP events): count maximum, tables, idf by rank */
+    double   ms_pairs;        /* the pair pass */
+    double   ms_total;        /* host wall time of the whole call */
+} tfidf_reweight_info;
+int tfidf_last_reweight_info(const tfidf_ctx* ctx, tfidf_reweight_info* info);
+/* Host only, plain C (weight_host.c): the same definition on a fetched result.  Rewrites
+ * r->pair_score in place from pair_count, pair_docsize, pair_df and ndocs_total; a document is a
+ * maximal run of equal pair_doc.  It serves a caller that already holds a fetched result and is
+ * the second opinion on the device.  TFIDF_E_INVAL for a NULL argument, parameters that fail the
+ * check, the N limit above, or a pair with count, docsize or df of 0 or df > N; the scores are
+ * untouched then. */
+int tfidf_result_reweight(tfidf_result* r, const tfidf_weighting* w);
+
 /* ---------------------------------------------------------------- ingest ---- */
 
 /* Reference input contract (TFIDF.c:98-110,130-147): N = number of entries of `dir`

@@ -205,6 +205,7 @@ struct tfidf_ctx {
         uint64_t Nt = 0;
         const uint32_t* vals = nullptr;   /* null: lut[d] for every df d = 1..Nt; else lut[k] for df vals[k], k < n */
         uint64_t n = 0;
+        uint32_t mode = 0;                /* TFIDF_IDF_REF: the run's log(N/df); else a weighting scheme's idf (tfidf_reweight) */
         std::chrono::steady_clock::time_point t0;
         int64_t end_ns = 0;
     } idf_pool;
@@ -319,6 +320,21 @@ struct tfidf_ctx {
     tfidf_prune_info pinfo{};
     uint64_t info_npairs = 0;                   /* the run's P and V as tfidf_last_run_info reports them (a prune */
     uint32_t info_V = 0;                        /* changes npairs and V, not what the run was) */
+    /* weighting schemes (tfidf_reweight, reweight.hip): the active scheme; the scheme's idf table in
+     * the layout of idf_vals (by df, or through `present`), which is never overwritten; the
+     * sublinear tf table fl(1 + log c), c = 0..rw_lut_n (the values do not depend on the run, so
+     * the table only ever grows), the listed counts above it and their values; the list of big
+     * documents; the count maximum and the counters.  The new scores go into prune's spare
+     * pr_score; the idf by rank into the run's idf_rank, which has no reader after a run. */
+    uint32_t wt_tf = 0, wt_idf = 0, wt_norm = 0;
+    uint32_t rw_idf_mode = 0;                   /* the idf mode rw_idf holds for this run or model (0: none) */
+    DevBuf rw_idf, rw_lut, rw_list, rw_listv, rw_big, rw_misc;
+    uint32_t rw_lut_n = 0;
+    std::vector<double> rw_lut_host;
+    std::vector<uint32_t> rw_list_host;
+    std::vector<double> rw_listv_host;
+    hipEvent_t ev_rw[3] = {};                   /* tables / pairs bounds (created by the first call) */
+    tfidf_reweight_info rwinfo{};
 #define WR_NBUF 8
 #define WR_BUF (16ull << 20)
 #define WR_GROUPS 8
@@ -632,6 +648,9 @@ void tfidf_close(tfidf_ctx* ctx) {
         if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : ctx->ev_pr)
         if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : ctx->ev_rw)
+        if (e) (void)hipEventDestroy(e);
+    for (DevBuf* b : {&ctx->rw_idf, &ctx->rw_lut, &ctx->rw_list, &ctx->rw_listv, &ctx->rw_big, &ctx->rw_misc}) b->release();
     for (DevBuf* b : {&ctx->pr_flag, &ctx->pr_bits, &ctx->pr_k0, &ctx->pr_k1, &ctx->pr_v0, &ctx->pr_v1, &ctx->pr_tcnt,
                       &ctx->pr_tdoc, &ctx->pr_misc, &ctx->pr_sor, &ctx->pr_df, &ctx->pr_term, &ctx->pr_cnt, &ctx->pr_score,
                       &ctx->pr_off})
@@ -1515,9 +1534,15 @@ static void idf_worker(tfidf_ctx::IdfPool* P, unsigned i) {
         double* lut = P->lut;
         const uint32_t* vals = P->vals;
         const uint64_t Nt = P->Nt, n = P->n, lo = (n * i) / P->active, hi = (n * (i + 1)) / P->active;
+        const uint32_t mode = P->mode;
         const auto t0 = P->t0;
         lk.unlock();
-        if (vals)
+        if (mode != TFIDF_IDF_REF) {   /* weight_host.c's formula, the one tfidf_result_reweight uses */
+            if (vals)
+                for (uint64_t k = lo; k < hi; ++k) lut[k] = tfidf_weight_idf(mode, Nt, vals[k]);
+            else
+                for (uint64_t d = lo + 1; d < hi + 1; ++d) lut[d] = tfidf_weight_idf(mode, Nt, (uint32_t)d);
+        } else if (vals)
             for (uint64_t k = lo; k < hi; ++k) lut[k] = log(1.0 * (double)Nt / (double)vals[k]);
         else
             for (uint64_t d = lo + 1; d < hi + 1; ++d) lut[d] = log(1.0 * (double)Nt / (double)d);
@@ -1539,7 +1564,8 @@ static void idf_pool_stop(tfidf_ctx* ctx) {
     P.th.clear();
 }
 /* posts a table job to the context's workers (lut: n values; vals null = every df 1..n) */
-static void idf_post(tfidf_ctx* ctx, double* lut, uint64_t Nt, const uint32_t* vals, uint64_t n) {
+static void idf_post(tfidf_ctx* ctx, double* lut, uint64_t Nt, const uint32_t* vals, uint64_t n,
+                     uint32_t mode = TFIDF_IDF_REF) {
     tfidf_ctx::IdfPool& P = ctx->idf_pool;
     const int live = g_live_ctx.load();
     const unsigned share = live > 1 ? (unsigned)(IDF_POOL / live > 1 ? IDF_POOL / live : 1) : IDF_POOL;
@@ -1553,6 +1579,7 @@ static void idf_post(tfidf_ctx* ctx, double* lut, uint64_t Nt, const uint32_t* v
         P.Nt = Nt;
         P.vals = vals;
         P.n = n;
+        P.mode = mode;
         P.t0 = std::chrono::steady_clock::now();
         P.end_ns = 0;
         P.busy = true;
@@ -1902,6 +1929,8 @@ extern "C" int tfidf_run(tfidf_ctx* ctx, const tfidf_corpus* in) {
     ctx->have_info = true;
     ctx->info_npairs = ctx->npairs;
     ctx->info_V = ctx->V;
+    ctx->wt_tf = ctx->wt_idf = ctx->wt_norm = 0;   /* a run's scores are the reference's */
+    ctx->rw_idf_mode = 0;
     if (ctx->timing) (void)hipEventSynchronize(ctx->ev[S_NSTAGES]);   /* done on the device; the runtime may not know yet */
     if (ctx->timing == 2) {
         for (int i = 0; i < S_NSTAGES; ++i) ctx->ms_stage[i] = 0;
@@ -2979,7 +3008,18 @@ inline uint64_t tr_bound(uint64_t nbytes, uint64_t nd) {
 inline size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
 }  // namespace
 
+/* the weighting section's helpers (below): a slice's rows are scored by reweight.hip when a
+ * scheme other than the reference's is active */
+enum { RWM_BIG = 0, RWM_ZERO = 1, RWM_CMAX = 2, RWM_NLIST = 3 };   /* rw_misc's words */
+static int rw_cmax_launch(tfidf_ctx* ctx, const uint32_t* count, uint64_t n, const uint32_t* n_dev);
+static int rw_tf_finish(tfidf_ctx* ctx, uint32_t cmax, uint32_t nlist, uint32_t* nlisted, uint64_t* nlogs);
+static void rw_scheme_args(tfidf_ctx* ctx, RwArgs& a, uint32_t tf, uint32_t norm, uint32_t nlisted);
+
 extern "C" int tfidf_transform(tfidf_ctx* ctx, const tfidf_corpus* batch, tfidf_rows* out) {
+    return tfidf_ctx_transform(ctx, batch, out, true);
+}
+
+int tfidf_ctx_transform(tfidf_ctx* ctx, const tfidf_corpus* batch, tfidf_rows* out, bool norm) {
     if (!ctx || !batch || !out) return TFIDF_E_INVAL;
     const uint32_t N = batch->ndocs;
     if (N && !batch->doc_off) return TFIDF_E_INVAL;
@@ -3030,6 +3070,10 @@ extern "C" int tfidf_transform(tfidf_ctx* ctx, const tfidf_corpus* batch, tfidf_
     ti.ndocs = N;
     const uint32_t V = ctx->V;
     const bool full_lut = ctx->ndocs_total <= IDF_FULL_MAX;   /* run_post: idf_vals by df, else through `present` */
+    /* the active weighting scheme (tfidf_reweight); the reference's takes the path it always took */
+    const uint32_t wtf = ctx->wt_tf, widf = ctx->wt_idf, wnorm = norm ? ctx->wt_norm : (uint32_t)TFIDF_NORM_NONE;
+    const bool ref_scheme = wtf == TFIDF_TF_RATIO && widf == TFIDF_IDF_REF && ctx->wt_norm == TFIDF_NORM_NONE;
+    if (!ref_scheme) ENSURE(ctx->rw_misc, 256);
     uint64_t Ptot = 0;
     std::vector<uint64_t> h_rowoff;
     for (uint32_t d0 = 0; d0 < N;) {
@@ -3156,9 +3200,15 @@ extern "C" int tfidf_transform(tfidf_ctx* ctx, const tfidf_corpus* batch, tfidf_
         pa.p_woff = (uint64_t*)(B + b_pwo);
         pa.p_wlen = (uint32_t*)(B + b_pwl);
         pa.status = sl.status;
-        if (launch_tr_flags(pa, s) || scan_excl_u32(pa.flag, pa.flag, T, ctx->arena, s) || launch_tr_pairs(pa, s)) {
+        if (launch_tr_flags(pa, s) || scan_excl_u32(pa.flag, pa.flag, T, ctx->arena, s) ||
+            (ref_scheme ? launch_tr_pairs(pa, s) : launch_tr_pairs_w(pa, s))) {
             HIPCHK(hipGetLastError());
             return TFIDF_E_HIP;
+        }
+        uint32_t cw[2] = {0, 0};   /* sublinear tf: the slice's largest count and its counts above the table */
+        if (!ref_scheme && wtf == TFIDF_TF_LOG) {
+            if (const int rc = rw_cmax_launch(ctx, pa.p_count, T, pa.pos + T)) return rc;
+            HIPCHK(hipMemcpyAsync(cw, ctx->rw_misc.as<uint32_t>() + RWM_CMAX, 8, hipMemcpyDeviceToHost, s));
         }
         HIPCHK(hipEventRecord(ctx->ev_tr[4], s));
         /* ---- back to the host: the slice's words first (the pair total sizes the rest) ---- */
@@ -3175,6 +3225,28 @@ extern "C" int tfidf_transform(tfidf_ctx* ctx, const tfidf_corpus* batch, tfidf_
             return TFIDF_E_STATE;
         }
         const uint64_t P = P32;
+        if (!ref_scheme && P) {   /* the rows' scores by the scheme: w, then the norm over each row's pairs */
+            uint32_t nlisted = 0;
+            uint64_t nlogs = 0;
+            if (wtf == TFIDF_TF_LOG)
+                if (const int rc = rw_tf_finish(ctx, cw[0], cw[1], &nlisted, &nlogs)) return rc;
+            ENSURE(ctx->rw_big, (size_t)nd * 4 + 4);
+            RwArgs wa{};
+            wa.off = pa.row_off;
+            wa.npairs = P;
+            wa.ndocs = nd;
+            wa.doc_size = pa.doc_size;
+            wa.count = pa.p_count;
+            wa.key = pa.p_df;
+            wa.key_n = ctx->ndocs_total + 1;
+            if (widf != TFIDF_IDF_NONE) {
+                wa.idf = widf == TFIDF_IDF_REF ? ctx->idf_vals.as<double>() : ctx->rw_idf.as<double>();
+                wa.idf_idx = pa.idf_idx;
+            }
+            wa.score = pa.p_score;
+            rw_scheme_args(ctx, wa, wtf, wnorm, nlisted);
+            if (launch_rw_pairs(wa, ctx->ncu, s)) { HIPCHK(hipGetLastError()); return TFIDF_E_HIP; }
+        }
         if (!grow_host(out->term, Ptot + P) || !grow_host(out->count, Ptot + P) || !grow_host(out->df, Ptot + P) ||
             !grow_host(out->score, Ptot + P) || !grow_host(out->word_off, Ptot + P) || !grow_host(out->word_len, Ptot + P))
             return TFIDF_E_NOMEM;
@@ -3794,6 +3866,8 @@ extern "C" int tfidf_model_import(tfidf_ctx* ctx, const tfidf_model* m) {
     ctx->npairs = 0;
     ctx->info_npairs = 0;
     ctx->info_V = V;
+    ctx->wt_tf = ctx->wt_idf = ctx->wt_norm = 0;   /* the model file records no scheme */
+    ctx->rw_idf_mode = 0;
     ctx->corpus = tfidf_corpus{};
     ctx->corpus.nbytes = nbytes;   /* VocabRO.corpus_bytes: the blob stands where the corpus does */
     ctx->dev_bytes = ctx->m_blob.as<uint8_t>();
@@ -4001,6 +4075,248 @@ extern "C" int tfidf_last_prune_info(const tfidf_ctx* ctx, tfidf_prune_info* inf
     if (!ctx || !info || info->size < sizeof(uint64_t)) return TFIDF_E_INVAL;
     const uint64_t n = info->size < sizeof(tfidf_prune_info) ? info->size : sizeof(tfidf_prune_info);
     tfidf_prune_info o = ctx->pinfo;
+    o.size = n;
+    memcpy(info, &o, (size_t)n);
+    return TFIDF_OK;
+}
+
+/* --------------------------------------------------------------- weighting ----
+ * Weighting schemes over the resident result (reweight.hip; the check, the formulas of the
+ * tables and the host form are weight_host.c).  Tables (the scheme's idf in the layout of
+ * idf_vals, the sublinear tf table, the idf by rank), then the pair pass into prune's spare
+ * score buffer, which changes places with out_score when every step has succeeded.  idf_vals is
+ * never written: the reference scheme reads it again. */
+
+/* The scheme's idf for every df the run's table covers, in that table's layout, on the
+ * context's workers; kept until the next run or import (a prune leaves the index a superset). */
+static int rw_idf_table(tfidf_ctx* ctx, uint32_t mode, uint64_t* nlogs) {
+    if (mode == TFIDF_IDF_REF || mode == TFIDF_IDF_NONE || ctx->rw_idf_mode == mode) return TFIDF_OK;
+    const uint64_t Nt = ctx->ndocs_total;
+    if (!ctx->V || !Nt) return TFIDF_OK;
+    hipStream_t s = ctx->stream;
+    if (const int q = idf_pin_quiesce(ctx)) return q;
+    const double keep_host = ctx->ms_idf_host, keep_wait = ctx->ms_idf_wait;   /* the run's, in tfidf_last_run_info */
+    std::vector<uint32_t> vals;
+    uint64_t n = Nt + 1;   /* entries of the table */
+    if (Nt > IDF_FULL_MAX) {   /* the distinct df values through the run's index, listed again */
+        const size_t want = (size_t)(Nt + 2) * 4 + 8192;
+        if (want > ctx->arena_buf.cap && arena_reset(ctx, want) != 0) return TFIDF_E_NOMEM;
+        ctx->arena.used = 0;   /* as format_prepare: nothing of the result lives in the arena */
+        uint32_t* vals_dev = (uint32_t*)ctx->arena.get((size_t)(Nt + 2) * 4);
+        if (!vals_dev) return TFIDF_E_NOMEM;
+        uint32_t* present = ctx->present.as<uint32_t>();
+        if (!present || ctx->present.cap < (Nt + 2) * 4) return TFIDF_E_STATE;
+        if (launch_df_list(present, Nt + 1, vals_dev, s)) { HIPCHK(hipGetLastError()); return TFIDF_E_HIP; }
+        uint32_t K = 0;
+        HIPCHK(hipMemcpyAsync(&K, present + Nt + 1, 4, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        if (K == 0 || (uint64_t)K > Nt + 1) return TFIDF_E_STATE;
+        vals.resize(K);
+        HIPCHK(hipMemcpyAsync(vals.data(), vals_dev, (size_t)K * 4, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        n = K;
+    }
+    ENSURE(ctx->rw_idf, (size_t)n * 8 + 8);
+    if (ctx->idf_pin_n < (size_t)n + 1) {
+        if (ctx->idf_pin) (void)hipHostFree(ctx->idf_pin);
+        ctx->idf_pin = nullptr;
+        ctx->idf_pin_n = 0;
+        if (hipHostMalloc((void**)&ctx->idf_pin, ((size_t)n + 1) * 8, hipHostMallocDefault) != hipSuccess) return TFIDF_E_NOMEM;
+        ctx->idf_pin_n = (size_t)n + 1;
+    }
+    if (vals.empty()) {
+        ctx->idf_pin[0] = 0.0;   /* df >= 1 for every term that occurs */
+        idf_post(ctx, ctx->idf_pin, Nt, nullptr, Nt, mode);
+        *nlogs += Nt;
+    } else {
+        idf_post(ctx, ctx->idf_pin, Nt, vals.data(), n, mode);
+        *nlogs += n;
+    }
+    idf_join(ctx);
+    ctx->ms_idf_host = keep_host;
+    ctx->ms_idf_wait = keep_wait;
+    HIPCHK(hipMemcpyAsync(ctx->rw_idf.p, ctx->idf_pin, (size_t)n * 8, hipMemcpyHostToDevice, s));
+    ctx->idf_pin_busy = true;
+    HIPCHK(hipStreamSynchronize(s));
+    ctx->idf_pin_busy = false;
+    ctx->rw_idf_mode = mode;
+    return TFIDF_OK;
+}
+
+/* sublinear tf, first half: the largest of n counts (n_dev: the total still on the device) and
+ * the list of those above RW_LUT_MAX, into rw_misc[RWM_CMAX..] and rw_list */
+static int rw_cmax_launch(tfidf_ctx* ctx, const uint32_t* count, uint64_t n, const uint32_t* n_dev) {
+    ENSURE(ctx->rw_misc, 256);
+    ENSURE(ctx->rw_list, (size_t)RW_LIST_MAX * 4);
+    ENSURE(ctx->rw_lut, ((size_t)RW_LUT_MAX + 1) * 8);
+    uint32_t* misc = ctx->rw_misc.as<uint32_t>();
+    HIPCHK(hipMemsetAsync(misc + RWM_CMAX, 0, 8, ctx->stream));
+    if (launch_rw_cmax(count, n, n_dev, misc + RWM_CMAX, ctx->rw_list.as<uint32_t>(), RW_LIST_MAX, ctx->stream)) {
+        HIPCHK(hipGetLastError());
+        return TFIDF_E_HIP;
+    }
+    return TFIDF_OK;
+}
+/* second half, with the two words on the host: the table fl(1 + log c) up to min(cmax,
+ * RW_LUT_MAX) (grown, never rebuilt: its values do not depend on the run) and the listed
+ * counts, sorted and distinct, with their values.  Synchronises the stream. */
+static int rw_tf_finish(tfidf_ctx* ctx, uint32_t cmax, uint32_t nlist, uint32_t* nlisted, uint64_t* nlogs) {
+    hipStream_t s = ctx->stream;
+    *nlisted = 0;
+    if (nlist > RW_LIST_MAX) return TFIDF_E_CAPACITY;   /* the list is bounded; nothing has been scored */
+    const uint32_t need = cmax < RW_LUT_MAX ? cmax : RW_LUT_MAX;
+    bool wait = false;
+    if (need > ctx->rw_lut_n || ctx->rw_lut_host.empty()) {
+        if (ctx->rw_lut_host.empty()) ctx->rw_lut_host.assign((size_t)RW_LUT_MAX + 1, 0.0);
+        const uint32_t first = ctx->rw_lut_n + 1u;
+        for (uint32_t c = first; c <= need; ++c) ctx->rw_lut_host[c] = tfidf_weight_tf_log(c);
+        const uint32_t from = ctx->rw_lut_n ? first : 0u;
+        if (need + 1u > from) {
+            HIPCHK(hipMemcpyAsync(ctx->rw_lut.as<double>() + from, ctx->rw_lut_host.data() + from, (size_t)(need + 1u - from) * 8,
+                                  hipMemcpyHostToDevice, s));
+            wait = true;
+        }
+        if (need >= first) *nlogs += need - first + 1u;
+    }
+    if (nlist) {
+        std::vector<uint32_t>& lc = ctx->rw_list_host;
+        lc.resize(nlist);
+        HIPCHK(hipMemcpyAsync(lc.data(), ctx->rw_list.p, (size_t)nlist * 4, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        std::sort(lc.begin(), lc.end());
+        lc.erase(std::unique(lc.begin(), lc.end()), lc.end());
+        std::vector<double>& lv = ctx->rw_listv_host;
+        lv.resize(lc.size());
+        for (size_t i = 0; i < lc.size(); ++i) lv[i] = tfidf_weight_tf_log(lc[i]);
+        ENSURE(ctx->rw_listv, lc.size() * 8 + 8);
+        HIPCHK(hipMemcpyAsync(ctx->rw_list.p, lc.data(), lc.size() * 4, hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(ctx->rw_listv.p, lv.data(), lv.size() * 8, hipMemcpyHostToDevice, s));
+        *nlisted = (uint32_t)lc.size();
+        *nlogs += lc.size();
+        wait = true;
+    }
+    if (wait) HIPCHK(hipStreamSynchronize(s));   /* the uploads read pageable host memory of the context */
+    if (need > ctx->rw_lut_n) ctx->rw_lut_n = need;
+    return TFIDF_OK;
+}
+
+/* the scheme-dependent members of a pair pass's arguments */
+static void rw_scheme_args(tfidf_ctx* ctx, RwArgs& a, uint32_t tf, uint32_t norm, uint32_t nlisted) {
+    a.tf_mode = tf;
+    a.norm = norm;
+    a.tf_lut = ctx->rw_lut.as<double>();
+    a.lut_n = ctx->rw_lut_n;
+    a.nlisted = nlisted;
+    a.listed_c = ctx->rw_list.as<uint32_t>();
+    a.listed_v = ctx->rw_listv.as<double>();
+    a.big_list = ctx->rw_big.as<uint32_t>();
+    a.misc = ctx->rw_misc.as<uint32_t>();
+}
+
+extern "C" int tfidf_reweight(tfidf_ctx* ctx, const tfidf_weighting* w) {
+    if (!ctx || tfidf_weighting_check(w) != TFIDF_OK) return TFIDF_E_INVAL;
+    if (!ctx->have_result && !ctx->have_model) return TFIDF_E_STATE;
+    if (tfidf_weighting_check_n(w, ctx->ndocs_total) != TFIDF_OK) return TFIDF_E_INVAL;
+    const auto wall0 = std::chrono::steady_clock::now();
+    HIPCHK(hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    for (hipEvent_t& e : ctx->ev_rw)
+        if (!e) HIPCHK(hipEventCreate(&e));
+    if (!ctx->ncu) {
+        int n = 0;
+        if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, ctx->device) != hipSuccess || n <= 0) n = 256;
+        ctx->ncu = (uint32_t)n;
+    }
+    const bool pairs = ctx->have_result && !ctx->model_only;
+    const uint32_t V = ctx->V, N = pairs ? ctx->ndocs : 0u;
+    const uint64_t P = pairs ? ctx->npairs : 0u, Nt = ctx->ndocs_total;
+    tfidf_reweight_info ri{};
+    ri.tf = w->tf;
+    ri.idf = w->idf;
+    ri.norm = w->norm;
+    ri.npairs = P;
+    ri.ndocs = N;
+    if (w->tf == ctx->wt_tf && w->idf == ctx->wt_idf && w->norm == ctx->wt_norm) {   /* active already: no byte changes */
+        ri.ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - wall0).count();
+        ctx->rwinfo = ri;
+        return TFIDF_OK;
+    }
+    ri.changed = 1;
+    HIPCHK(hipEventRecord(ctx->ev_rw[0], s));
+    if (const int rc = rw_idf_table(ctx, w->idf, &ri.nlogs)) return rc;
+    if (P && N) {
+        if (ensure_spare(ctx->pr_score, ctx->out_score, (size_t)P * 8 + 8)) return TFIDF_E_NOMEM;
+        ENSURE(ctx->rw_misc, 256);
+        ENSURE(ctx->rw_big, (size_t)N * 4 + 4);
+        uint32_t nlisted = 0;
+        if (w->tf == TFIDF_TF_LOG) {
+            if (const int rc = rw_cmax_launch(ctx, ctx->out_cnt.as<uint32_t>(), P, nullptr)) return rc;
+            uint32_t cw[2] = {0, 0};
+            HIPCHK(hipMemcpyAsync(cw, ctx->rw_misc.as<uint32_t>() + RWM_CMAX, 8, hipMemcpyDeviceToHost, s));
+            HIPCHK(hipStreamSynchronize(s));
+            if (const int rc = rw_tf_finish(ctx, cw[0], cw[1], &nlisted, &ri.nlogs)) return rc;
+            ri.max_count = cw[0];
+            ri.listed_counts = nlisted;
+        }
+        RwArgs a{};
+        a.off = ctx->out_off.as<uint64_t>();
+        a.npairs = P;
+        a.ndocs = N;
+        a.order = ctx->order;
+        a.doc_size = ctx->doc_size.as<uint32_t>();
+        a.count = ctx->out_cnt.as<uint32_t>();
+        a.key = ctx->out_term.as<uint32_t>();
+        a.key_n = V;
+        if (w->idf != TFIDF_IDF_NONE) {   /* the idf by rank: one 8-byte gather per pair in the pair pass */
+            ENSURE(ctx->idf_rank, (size_t)V * 8 + 8);
+            const double* tab = w->idf == TFIDF_IDF_REF ? ctx->idf_vals.as<double>() : ctx->rw_idf.as<double>();
+            const uint32_t* idx = Nt <= IDF_FULL_MAX ? nullptr : ctx->present.as<uint32_t>();
+            if (launch_rw_idf_rank(df_of_run(ctx), V, tab, idx, Nt + 1, ctx->idf_rank.as<double>(), s)) {
+                HIPCHK(hipGetLastError());
+                return TFIDF_E_HIP;
+            }
+            a.idf = ctx->idf_rank.as<double>();
+        }
+        a.score = ctx->pr_score.as<double>();
+        rw_scheme_args(ctx, a, w->tf, w->norm, nlisted);
+        HIPCHK(hipEventRecord(ctx->ev_rw[1], s));
+        if (launch_rw_pairs(a, ctx->ncu, s)) { HIPCHK(hipGetLastError()); return TFIDF_E_HIP; }
+        HIPCHK(hipEventRecord(ctx->ev_rw[2], s));
+        uint32_t mw[2] = {0, 0};
+        HIPCHK(hipMemcpyAsync(mw, ctx->rw_misc.as<uint32_t>() + RWM_BIG, 8, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));   /* the spare is written: from here on the call cannot fail */
+        std::swap(ctx->out_score, ctx->pr_score);
+        ctx->text_valid = false;
+        ctx->norm_valid = false;   /* bm25_L stays: docSize is unchanged */
+        ri.big_docs = mw[0] < N ? mw[0] : N;
+        ri.zero_norm_docs = mw[1];
+        float ms = 0;
+        (void)hipEventElapsedTime(&ms, ctx->ev_rw[0], ctx->ev_rw[1]);
+        ri.ms_tables = ms;
+        (void)hipEventElapsedTime(&ms, ctx->ev_rw[1], ctx->ev_rw[2]);
+        ri.ms_pairs = ms;
+    }
+    ctx->wt_tf = w->tf;
+    ctx->wt_idf = w->idf;
+    ctx->wt_norm = w->norm;
+    ri.ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - wall0).count();
+    ctx->rwinfo = ri;
+    return TFIDF_OK;
+}
+
+extern "C" int tfidf_weighting_get(const tfidf_ctx* ctx, tfidf_weighting* out) {
+    if (!ctx || !out || out->size < sizeof(tfidf_weighting)) return TFIDF_E_INVAL;
+    out->tf = ctx->wt_tf;
+    out->idf = ctx->wt_idf;
+    out->norm = ctx->wt_norm;
+    out->reserved = 0;
+    return TFIDF_OK;
+}
+
+extern "C" int tfidf_last_reweight_info(const tfidf_ctx* ctx, tfidf_reweight_info* info) {
+    if (!ctx || !info || info->size < sizeof(uint64_t)) return TFIDF_E_INVAL;
+    const uint64_t n = info->size < sizeof(tfidf_reweight_info) ? info->size : sizeof(tfidf_reweight_info);
+    tfidf_reweight_info o = ctx->rwinfo;
     o.size = n;
     memcpy(info, &o, (size_t)n);
     return TFIDF_OK;

@@ -575,6 +575,20 @@ int tfidf_group_prune(tfidf_group* g, const tfidf_prune_params* params) {
     return TFIDF_OK;
 }
 
+/* tfidf_reweight on every rank at once.  N and df are global and a document's pairs live in one
+ * shard, so every shard computes what a single shard would. */
+int tfidf_group_reweight(tfidf_group* g, const tfidf_weighting* params) {
+    if (!g || tfidf_weighting_check(params) != TFIDF_OK) return TFIDF_E_INVAL;
+    std::vector<int> rc((size_t)g->n, TFIDF_OK);
+    std::vector<std::thread> th;
+    for (int r = 1; r < g->n; ++r) th.emplace_back([&, r] { rc[r] = tfidf_reweight(g->ctx[r], params); });
+    rc[0] = tfidf_reweight(g->ctx[0], params);
+    for (auto& t : th) t.join();
+    for (int r = 0; r < g->n; ++r)
+        if (rc[r]) return rc[r];
+    return TFIDF_OK;
+}
+
 int tfidf_group_write_output(tfidf_group* g, const char* path) {
     if (!g || !path) return TFIDF_E_INVAL;
     std::vector<int> rc((size_t)g->n, TFIDF_OK);
@@ -967,13 +981,18 @@ int tfidf_group_transform(tfidf_group* g, const tfidf_corpus* batch, tfidf_rows*
     for (tfidf_rows& p : part) memset(&p, 0, sizeof(p));
     {
         std::vector<std::thread> th;
-        for (int r = 1; r < R; ++r) th.emplace_back([&, r] { rc[r] = tfidf_transform(g->ctx[r], batch, &part[r]); });
-        rc[0] = tfidf_transform(g->ctx[0], batch, &part[0]);
+        /* under a row norm the ranks return w: a rank sees only its own vocabulary's part of a row */
+        for (int r = 1; r < R; ++r) th.emplace_back([&, r] { rc[r] = tfidf_ctx_transform(g->ctx[r], batch, &part[r], false); });
+        rc[0] = tfidf_ctx_transform(g->ctx[0], batch, &part[0], false);
         for (auto& t : th) t.join();
     }
     int err = TFIDF_OK;
     for (int r = 0; r < R && !err; ++r) err = rc[r];
     const uint32_t N = batch->ndocs;
+    tfidf_weighting wt;
+    memset(&wt, 0, sizeof(wt));
+    wt.size = sizeof(wt);
+    if (!err) err = tfidf_weighting_get(g->ctx[0], &wt);   /* the same on every rank (tfidf_group_reweight) */
     tfidf_rows m;
     memset(&m, 0, sizeof(m));
     uint64_t cap = 0;
@@ -1022,6 +1041,8 @@ int tfidf_group_transform(tfidf_group* g, const tfidf_corpus* batch, tfidf_rows*
                 if (at[r] < part[r].row_off[d + 1] && part[r].word_off[at[r]] == wo) ++at[r];
         }
         m.doc_oov[d] = (uint32_t)(m.doc_size[d] - in_vocab);
+        /* the merged row is in pair order: the scheme's norm by the host definition (weight_host.c) */
+        if (wt.norm != TFIDF_NORM_NONE) (void)tfidf_weight_normalize(m.score + m.row_off[d], P - m.row_off[d], wt.norm);
     }
     if (!err) {
         m.row_off[N] = P;

@@ -671,6 +671,10 @@ struct TrPairs {
 };
 int launch_tr_flags(const TrPairs& a, hipStream_t s);
 int launch_tr_pairs(const TrPairs& a, hipStream_t s);
+/* the same under a weighting scheme other than the reference's (tfidf_reweight): an instantiation
+ * of its own that reads no idf and writes no score; launch_rw_pairs scores the rows from p_count,
+ * p_df and doc_size afterwards */
+int launch_tr_pairs_w(const TrPairs& a, hipStream_t s);
 
 /* ---- the portable model (model.hip, tfidf_model_import / tfidf_model_export) ---- */
 #define ST_MODEL_DUP 256u   /* import: a term's key was in the table already (the host check excludes it) */
@@ -876,5 +880,51 @@ int launch_pr_count(const PrPairs& a, uint32_t ncu, hipStream_t s);
 int launch_pr_write(const PrPairs& a, uint32_t ncu, hipStream_t s);
 /* after the write pass: one lane per document, one integer add per workgroup into *emptied */
 int launch_pr_emptied(const PrPairs& a, hipStream_t s);
+
+/* ---- weighting schemes (reweight.hip, tfidf_reweight; tfidf_transform under a scheme) ---- */
+#define RW_LUT_MAX (1u << 16)      /* sublinear tf: fl(1 + log c) is tabulated by the host for c = 1..min(Cmax, RW_LUT_MAX) */
+#define RW_LIST_MAX (1u << 20)     /* pairs whose count is above RW_LUT_MAX are listed (4 bytes each) up to this many */
+#define RW_BIG 4096u               /* documents over this many pairs: a workgroup each (QS_BIG's cut) */
+#define RW_KEEP 256u               /* a wave keeps the w of a document of up to this many pairs in registers */
+/* cmax[0] = max(count[0..n)), cmax[1] = the pairs with count > RW_LUT_MAX, whose counts are
+ * appended to list (in no fixed order: the host sorts them) while they fit in list_cap.  n is
+ * *n_dev when n_dev is not null (a transform slice's pair total, still on the device), clamped
+ * to n.  cmax is zeroed by the caller.  Integer atomics only. */
+int launch_rw_cmax(const uint32_t* count, uint64_t n, const uint32_t* n_dev, uint32_t* cmax, uint32_t* list,
+                   uint32_t list_cap, hipStream_t s);
+/* idf_rank[r] = idf[idf_idx ? idf_idx[df[r]] : df[r]], one lane per term rank */
+int launch_rw_idf_rank(const uint32_t* df, uint32_t V, const double* idf, const uint32_t* idf_idx, uint64_t idf_n,
+                       double* idf_rank, hipStream_t s);
+/* The pair pass, document-major.  Document j = pairs [off[j], off[j + 1]) (clamped to npairs);
+ * its docSize is doc_size[order ? order[j] : j].  Pair p: c = count[p], tf by tf_mode
+ * (TFIDF_TF_LOG: tf_lut[c] for c <= lut_n, else listed_v[i] with listed_c[i] == c, sorted),
+ * idf = 1.0 when idf is null, else idf[idf_idx ? idf_idx[key[p]] : key[p]] (key = term rank with
+ * an idf by rank, or df with the table by df), w = fl(tf * idf); the norm as include/tfidf.h
+ * defines it: one ordered sum per document, carried by every lane of the wave that owns the
+ * document.  A wave keeps w in registers up to RW_KEEP pairs and reloads what it wrote beyond;
+ * documents over RW_BIG pairs go to a second launch, one workgroup each, whose wave 0 adds each
+ * tile's 256 rounded terms in pair order.  score may not alias an input. */
+struct RwArgs {
+    const uint64_t* off;         /* ndocs + 1 */
+    uint64_t npairs;
+    uint32_t ndocs;
+    uint32_t tf_mode, norm;
+    const uint32_t* order;       /* null: identity */
+    const uint32_t* doc_size;
+    const uint32_t* count;
+    const uint32_t* key;
+    uint64_t key_n;              /* keys at or above it read no table (idf 1.0; never with valid input) */
+    const double* idf;
+    const uint32_t* idf_idx;
+    const double* tf_lut;
+    uint32_t lut_n;
+    uint32_t nlisted;
+    const uint32_t* listed_c;
+    const double* listed_v;
+    double* score;
+    uint32_t* big_list;          /* [ndocs] scratch */
+    uint32_t* misc;              /* [0] big_count, [1] documents with pairs and a zero norm; zeroed by the launch */
+};
+int launch_rw_pairs(const RwArgs& a, uint32_t ncu, hipStream_t s);
 
 #endif

@@ -175,6 +175,9 @@ __global__ __launch_bounds__(NT) void k_tr_docsize(const TrPairs a) {
     a.doc_size[i] = (uint32_t)(lower_bound_u64(a.tok_start, a.ntok, e) - lower_bound_u64(a.tok_start, a.ntok, b));
 }
 
+/* REF: the reference's score, as the run computes it.  !REF (a weighting scheme is active,
+ * tfidf_reweight): the integers only; reweight.hip scores the rows afterwards */
+template <bool REF>
 __global__ __launch_bounds__(NT) void k_tr_pairs(const TrPairs a) {
     const uint64_t i = (uint64_t)blockIdx.x * NT + threadIdx.x;
     if (i >= a.ntok) return;
@@ -197,13 +200,15 @@ __global__ __launch_bounds__(NT) void k_tr_pairs(const TrPairs a) {
     const uint32_t t = a.val[i];   /* the sort is stable: the run's first record is its first token */
     const uint32_t ds = a.doc_size[row - a.d0], df = a.df[rank];
     if (o >= a.ntok || t >= a.ntok || ds == 0u || df == 0u || df > a.Nt) { atomicOr(a.status, ST_BOUNDS); return; }
-    const double idf = a.idf_idx ? a.idf[a.idf_idx[df]] : a.idf[df];
-    const double tf = (double)(uint32_t)cnt / (double)ds;   /* TFIDF.c:202 */
     a.p_row[o] = row;
     a.p_term[o] = rank;
     a.p_count[o] = (uint32_t)cnt;
     a.p_df[o] = df;
-    a.p_score[o] = tf * idf;                                /* TFIDF.c:243-244: two roundings */
+    if (REF) {
+        const double idf = a.idf_idx ? a.idf[a.idf_idx[df]] : a.idf[df];
+        const double tf = (double)(uint32_t)cnt / (double)ds;   /* TFIDF.c:202 */
+        a.p_score[o] = tf * idf;                                /* TFIDF.c:243-244: two roundings */
+    }
     a.p_woff[o] = a.tok_start[t];
     a.p_wlen[o] = a.tlen[t];
 }
@@ -260,7 +265,15 @@ int launch_tr_flags(const TrPairs& a, hipStream_t s) {
 int launch_tr_pairs(const TrPairs& a, hipStream_t s) {
     const uint64_t nd = (uint64_t)(a.d1 - a.d0);
     if (nd) k_tr_docsize<<<grid_for(nd), NT, 0, s>>>(a);
-    if (a.ntok) k_tr_pairs<<<grid_for(a.ntok), NT, 0, s>>>(a);
+    if (a.ntok) k_tr_pairs<true><<<grid_for(a.ntok), NT, 0, s>>>(a);
+    k_tr_rowoff<<<grid_for(nd + 1u), NT, 0, s>>>(a);
+    return ok();
+}
+
+int launch_tr_pairs_w(const TrPairs& a, hipStream_t s) {
+    const uint64_t nd = (uint64_t)(a.d1 - a.d0);
+    if (nd) k_tr_docsize<<<grid_for(nd), NT, 0, s>>>(a);
+    if (a.ntok) k_tr_pairs<false><<<grid_for(a.ntok), NT, 0, s>>>(a);
     k_tr_rowoff<<<grid_for(nd + 1u), NT, 0, s>>>(a);
     return ok();
 }

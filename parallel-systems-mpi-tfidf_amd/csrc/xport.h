@@ -91,6 +91,20 @@ struct SimExport {
 int tfidf_ctx_similar_export(tfidf_ctx* ctx, const uint32_t* doc_ids, uint32_t ndocs, SimExport* e);
 int tfidf_ctx_similar_ext(tfidf_ctx* ctx, const SimExport* rows, uint32_t k, tfidf_neighbors* out);
 
+/* weight_host.c (plain C): the pieces of the weighting definition the engine's tables and the
+ * group transform share with tfidf_result_reweight */
+extern "C" {
+int tfidf_weighting_check_n(const tfidf_weighting* w, uint64_t ndocs_total);   /* the check plus the limit that needs N */
+double tfidf_weight_tf_log(uint32_t c);                                        /* fl(1.0 + log((double)c)) */
+double tfidf_weight_idf(uint32_t mode, uint64_t N, uint32_t df);
+int tfidf_weight_normalize(double* w, uint64_t n, uint32_t norm);              /* one row in place; 1: the norm is 0 */
+}
+/* engine.cpp: tfidf_transform is tfidf_ctx_transform with norm = true.  norm = false leaves the
+ * active scheme's row norm out (w is returned): tfidf_group_transform normalises the merged rows */
+struct tfidf_corpus;
+struct tfidf_rows;
+int tfidf_ctx_transform(tfidf_ctx* ctx, const tfidf_corpus* batch, tfidf_rows* out, bool norm);
+
 /* engine.cpp: hipMalloc counted in tfidf_run_info.device_allocs / device_alloc_bytes */
 hipError_t tfidf_dev_malloc(void** p, size_t bytes);
 

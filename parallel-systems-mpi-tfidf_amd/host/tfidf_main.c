@@ -136,6 +136,20 @@
  * the pruned result reproduces the pruned output.txt.  A model saved after pruning holds the
  * kept words only and needs no option when it is served.  Without the options nothing new is
  * called and every byte of every output is as before.
+ *
+ * Weighting schemes (tfidf_reweight / tfidf_group_reweight after the run and after the pruning
+ * options, before output.txt and every other file; under --model FILE after the import):
+ *   --tf ratio|raw|log|binary     the term frequency: count / docSize (the reference's), the count,
+ *                                 1 + ln(count), or 1.  --sublinear-tf is a synonym of --tf log.
+ *   --idf ref|smooth|plus1|none   ln(N / df) (the reference's), ln((N + 1) / (df + 1)) + 1,
+ *                                 ln(N / df) + 1, or 1.
+ *   --norm none|l1|l2             every document's scores divided by their sum or by the root of the
+ *                                 sum of their squares.
+ * --tf raw needs a norm.  --query, --keywords, --similar, --clusters and --transform follow the
+ * scheme (BM25 does not read the scores); --transform input reproduces output.txt.  The model
+ * file does not record the scheme: pass the options again with --model FILE.  With --debug-jobs
+ * the options are refused (exit 2): those blocks are the reference's.  Without the options
+ * nothing new is called and every byte of every output is as before.
  */
 #include <dirent.h>
 #include <math.h>
@@ -619,6 +633,23 @@ static int prune_bad_range(void) {
     return 2;
 }
 
+/* -------------------------------------------------------------- weighting -- */
+
+/* --tf, --idf, --norm, --sublinear-tf: the scores are computed again by the scheme after the run
+ * (after every shard's run) and after the pruning options, before output.txt and every other
+ * file; under --model after the import, for --transform */
+static struct {
+    int on;
+    tfidf_weighting w;
+} g_weight = {0, {sizeof(tfidf_weighting), TFIDF_TF_RATIO, TFIDF_IDF_REF, TFIDF_NORM_NONE, 0}};
+
+/* the index of `s` among n names, or -1 */
+static int name_index(const char* s, const char* const* names, int n) {
+    for (int i = 0; i < n; ++i)
+        if (!strcmp(s, names[i])) return i;
+    return -1;
+}
+
 /* --model: no run; the file's model is pruned on the host (with the prune options), imported and
  * --transform scored against it */
 static int run_model(int device) {
@@ -638,6 +669,7 @@ static int run_model(int device) {
     rc = tfidf_open(device, &ctx);
     if (!rc) rc = tfidf_model_import(ctx, &m);
     tfidf_model_free(&m);   /* the context owns what it needs */
+    if (!rc && g_weight.on) rc = tfidf_reweight(ctx, &g_weight.w);   /* the file records no scheme */
     if (!rc) rc = run_transform(ctx, NULL);
     tfidf_close(ctx);
     return rc ? fail(rc) : 0;
@@ -667,6 +699,7 @@ static int run_single(int device, const char* indir, const char* outpath, int de
         if (prune_params_for(c.ndocs_total ? c.ndocs_total : c.ndocs, &pp) != TFIDF_OK) { tfidf_close(ctx); return prune_bad_range(); }
         rc = tfidf_prune(ctx, &pp);
     }
+    if (!rc && g_weight.on) rc = tfidf_reweight(ctx, &g_weight.w);   /* over the pairs the pruning left */
     if (rc) { tfidf_close(ctx); return fail(rc); }
     tfidf_run_info ri;
     ri.size = sizeof(ri);
@@ -783,6 +816,7 @@ static int run_sharded(int ngpus, int nshards, const char* indir, const char* ou
         if (prune_params_for(plan.ndocs, &pp) != TFIDF_OK) { tfidf_group_close(g); tfidf_plan_free(&plan); return prune_bad_range(); }
         rc = tfidf_group_prune(g, &pp);
     }
+    if (!rc && g_weight.on) rc = tfidf_group_reweight(g, &g_weight.w);
     if (rc) { tfidf_group_close(g); tfidf_plan_free(&plan); return fail(rc); }
     const double t_run = wall_ms();
     /* each GPU formats its shard; the texts are written in shard order (TFIDF.c:253-282) */
@@ -826,8 +860,10 @@ static int usage(void) {
                     "[--clusters K [--clusters-iter I] [--clusters-seeds FILE] [--clusters-terms T] [--clusters-file FILE]] "
                     "[--transform DIR [--transform-file FILE]] [--save-model FILE] "
                     "[--min-df X] [--max-df X] [--max-features M] "
+                    "[--tf ratio|raw|log|binary] [--sublinear-tf] [--idf ref|smooth|plus1|none] [--norm none|l1|l2] "
                     "[--lower] [--strip-punct] [--min-token N] [--stopwords FILE] [--stem] [--utf8] [--ngrams SPEC [--ngram-joiner C]]\n"
                     "       tfidf --model FILE --transform DIR [--transform-file FILE] [--device D] [--min-df X] [--max-df X] [--max-features M] "
+                    "[--tf T] [--sublinear-tf] [--idf I] [--norm L] "
                     "[--lower] [--strip-punct] [--min-token N] [--stopwords FILE] [--stem] [--utf8] [--ngrams SPEC [--ngram-joiner C]]\n"
                     "  --similar K without --similar-docs searches for every document: "
                     "ceil(N / group) scans of the scored pairs, group <= 64\n"
@@ -844,6 +880,11 @@ static int usage(void) {
                     "is written (X with a '.': a fraction of N in (0, 1]); --max-features M keeps the M words in the most "
                     "documents (ties by word order; one shard only); scores and docSize are unchanged, and a model "
                     "saved after pruning needs no option when it is served\n"
+                    "  --tf, --idf and --norm replace the reference's count / docSize * ln(N / df) after the run and the "
+                    "pruning: --tf log (= --sublinear-tf) is 1 + ln(count), --idf smooth is ln((N + 1) / (df + 1)) + 1, "
+                    "--idf plus1 is ln(N / df) + 1, --norm l1|l2 divides a document's scores by their sum or by the root of "
+                    "the sum of their squares; --tf raw needs a norm; the model file does not record them; not with "
+                    "--debug-jobs\n"
                     "  --ngrams SPEC adds word n-grams behind the analyzer: SPEC is N (= 1-N) or A-B with 1 <= A <= B <= 8; "
                     "the words of a gram are joined by '_' or by the byte of --ngram-joiner C\n");
     return 2;
@@ -941,6 +982,23 @@ int main(int argc, char** argv) {
             g_prune.max_features = (uint32_t)v;
             g_prune.on = 1;
         }
+        else if (!strcmp(argv[i], "--sublinear-tf")) { g_weight.w.tf = TFIDF_TF_LOG; g_weight.on = 1; }
+        else if ((!strcmp(argv[i], "--tf") || !strcmp(argv[i], "--idf") || !strcmp(argv[i], "--norm")) && i + 1 < argc) {
+            static const char* const tf_names[] = {"ratio", "raw", "log", "binary"};       /* TFIDF_TF_* */
+            static const char* const idf_names[] = {"ref", "smooth", "plus1", "none"};     /* TFIDF_IDF_* */
+            static const char* const norm_names[] = {"none", "l2", "l1"};                  /* TFIDF_NORM_* */
+            const char* opt = argv[i];
+            const int v = !strcmp(opt, "--tf") ? name_index(argv[++i], tf_names, 4)
+                          : !strcmp(opt, "--idf") ? name_index(argv[++i], idf_names, 4) : name_index(argv[++i], norm_names, 3);
+            if (v < 0) {
+                fprintf(stderr, "tfidf: --tf takes ratio|raw|log|binary, --idf ref|smooth|plus1|none, --norm none|l1|l2\n");
+                return 2;
+            }
+            if (!strcmp(opt, "--tf")) g_weight.w.tf = (uint32_t)v;
+            else if (!strcmp(opt, "--idf")) g_weight.w.idf = (uint32_t)v;
+            else g_weight.w.norm = (uint32_t)v;
+            g_weight.on = 1;
+        }
         else if (!strcmp(argv[i], "--similar-docs") && i + 1 < argc) g_similar.docs = argv[++i];
         else if (!strcmp(argv[i], "--similar-file") && i + 1 < argc) g_similar.file = argv[++i];
         else if (!strcmp(argv[i], "--similar") && i + 1 < argc) {
@@ -956,6 +1014,17 @@ int main(int argc, char** argv) {
     if (g_ng.on ? tfidf_ngram_check(&g_ng.p) != TFIDF_OK : g_ng.p.joiner != 0) return usage();   /* a separator as joiner; a joiner alone */
     if (g_prune.on && !g_prune.min_frac && !g_prune.max_frac && g_prune.max_df != 0 && g_prune.min_df > g_prune.max_df)
         return prune_bad_range();
+    if (g_weight.on) {
+        if (tfidf_weighting_check(&g_weight.w) != TFIDF_OK) {
+            fprintf(stderr, "tfidf: --tf raw needs --norm l1 or --norm l2: a raw count times an idf has no bound\n");
+            return 2;
+        }
+        if (debug) {
+            fprintf(stderr, "tfidf: --tf, --idf, --norm and --sublinear-tf cannot be combined with --debug-jobs: its blocks are "
+                            "the reference's\n");
+            return 2;
+        }
+    }
     if (g_model.load) {   /* a model holds no pairs: nothing to rank, list or print */
         if (!g_transform.dir) {
             fprintf(stderr, "tfidf: --model needs --transform DIR\n");

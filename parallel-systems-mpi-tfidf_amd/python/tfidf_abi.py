@@ -50,6 +50,8 @@ EXPORTS = [
     "tfidf_stem_porter",
     "tfidf_ngram_check", "tfidf_ngrams_host", "tfidf_ngrams", "tfidf_last_ngram_info",
     "tfidf_prune_check", "tfidf_prune", "tfidf_group_prune", "tfidf_last_prune_info", "tfidf_model_prune",
+    "tfidf_weighting_check", "tfidf_reweight", "tfidf_weighting_get", "tfidf_group_reweight",
+    "tfidf_last_reweight_info", "tfidf_result_reweight",
 ]
 QUERY_MAX_K = 1024  # TFIDF_QUERY_MAX_K
 TERMS_MAX_K = 1024  # TFIDF_TERMS_MAX_K
@@ -78,6 +80,9 @@ AN_SLOT_BATCH = 1  # TFIDF_AN_SLOT_BATCH
 NGRAM_MAX_N = 8  # TFIDF_NGRAM_MAX_N
 NG_SLOT_CORPUS = 0  # TFIDF_NG_SLOT_CORPUS
 NG_SLOT_BATCH = 1  # TFIDF_NG_SLOT_BATCH
+TF_MODES = {"ratio": 0, "raw": 1, "log": 2, "binary": 3}  # TFIDF_TF_*
+IDF_MODES = {"ref": 0, "smooth": 1, "plus1": 2, "none": 3}  # TFIDF_IDF_*
+NORM_MODES = {"none": 0, "l2": 1, "l1": 2}  # TFIDF_NORM_*
 
 
 class Corpus(C.Structure):
@@ -297,6 +302,21 @@ class PruneInfo(C.Structure):
     ]
 
 
+class Weighting(C.Structure):
+    _fields_ = [
+        ("size", C.c_uint64), ("tf", C.c_uint32), ("idf", C.c_uint32), ("norm", C.c_uint32), ("reserved", C.c_uint32),
+    ]
+
+
+class ReweightInfo(C.Structure):
+    _fields_ = [
+        ("size", C.c_uint64), ("tf", C.c_uint32), ("idf", C.c_uint32), ("norm", C.c_uint32), ("changed", C.c_uint32),
+        ("npairs", C.c_uint64), ("ndocs", C.c_uint32), ("zero_norm_docs", C.c_uint32), ("nlogs", C.c_uint64),
+        ("max_count", C.c_uint32), ("listed_counts", C.c_uint32), ("big_docs", C.c_uint32), ("reserved", C.c_uint32),
+        ("ms_tables", C.c_double), ("ms_pairs", C.c_double), ("ms_total", C.c_double),
+    ]
+
+
 class DirPlan(C.Structure):
     _fields_ = [
         ("ndocs", C.c_uint32), ("nshards", C.c_uint32), ("doc_ids", C.POINTER(C.c_uint32)),
@@ -416,6 +436,12 @@ def lib() -> C.CDLL:
         L.tfidf_group_prune.argtypes = [C.c_void_p, C.POINTER(PruneParams)]
         L.tfidf_last_prune_info.argtypes = [C.c_void_p, C.POINTER(PruneInfo)]
         L.tfidf_model_prune.argtypes = [C.POINTER(Model), C.POINTER(PruneParams), C.POINTER(Model)]
+        L.tfidf_weighting_check.argtypes = [C.POINTER(Weighting)]
+        L.tfidf_reweight.argtypes = [C.c_void_p, C.POINTER(Weighting)]
+        L.tfidf_weighting_get.argtypes = [C.c_void_p, C.POINTER(Weighting)]
+        L.tfidf_group_reweight.argtypes = [C.c_void_p, C.POINTER(Weighting)]
+        L.tfidf_last_reweight_info.argtypes = [C.c_void_p, C.POINTER(ReweightInfo)]
+        L.tfidf_result_reweight.argtypes = [C.POINTER(Result), C.POINTER(Weighting)]
         if L.tfidf_abi_version() != ABI_VERSION:
             raise RuntimeError(f"{LIB_PATH}: ABI version {L.tfidf_abi_version()}, binding expects {ABI_VERSION} "
                                f"(stale build: rebuild with __graft_entry__.build())")
@@ -746,6 +772,50 @@ def model_prune(model: dict, min_df: int = 0, max_df: int = 0, max_features: int
         return _model_dict(out)
     finally:
         lib().tfidf_model_free(C.byref(out))
+
+
+def _mode(table: dict, v) -> int:
+    return table[v] if isinstance(v, str) else int(v)
+
+
+def weighting(tf="ratio", idf="ref", norm="none") -> Weighting:
+    """A tfidf_weighting: names ("log", "smooth", "l2", ..) or the enum values."""
+    w = Weighting()
+    w.size = C.sizeof(Weighting)
+    w.tf, w.idf, w.norm = _mode(TF_MODES, tf), _mode(IDF_MODES, idf), _mode(NORM_MODES, norm)
+    return w
+
+
+def _weighting_names(w: Weighting) -> dict:
+    def name(table, v):
+        return next((k for k, x in table.items() if x == v), v)
+    return {"tf": name(TF_MODES, w.tf), "idf": name(IDF_MODES, w.idf), "norm": name(NORM_MODES, w.norm)}
+
+
+def weighting_check(w: Weighting) -> int:
+    """tfidf_weighting_check (host only): 0, or E_INVAL; None stands for a NULL pointer."""
+    return int(lib().tfidf_weighting_check(None if w is None else C.byref(w)))
+
+
+def result_reweight(res: dict, tf="ratio", idf="ref", norm="none", N: int = 0, params: Weighting = None) -> dict:
+    """tfidf_result_reweight (host only, plain C) on a result dict (Engine.fetch's or the oracle's):
+    the dict with score and output_txt replaced.  N: ndocs_total when the dict does not carry it."""
+    w = params if params is not None else weighting(tf, idf, norm)
+    P = int(res["npairs"])
+    keep = [np.ascontiguousarray(res[k], dtype=np.uint32).copy() for k in ("doc", "count", "docsize", "df")]
+    score = np.ascontiguousarray(res["score"], dtype=np.float64).copy()
+    r = Result()
+    r.npairs = P
+    r.ndocs_total = int(N) if N else int(res["ndocs_total"])
+    if P:
+        u32 = C.POINTER(C.c_uint32)
+        r.pair_doc, r.pair_count, r.pair_docsize, r.pair_df = (a.ctypes.data_as(u32) for a in keep)
+        r.pair_score = score.ctypes.data_as(C.POINTER(C.c_double))
+    _chk(lib().tfidf_result_reweight(C.byref(r), C.byref(w)), "tfidf_result_reweight")
+    out = {k: v for k, v in res.items() if k not in ("tf_jobs", "idf_jobs")}
+    out["score"] = score
+    out["output_txt"] = format_lines(out)
+    return out
 
 
 def synth_host(seed: int, V: int, mode: int, cdf, doc_ids, ntok):
@@ -1119,6 +1189,26 @@ class Engine:
         _chk(lib().tfidf_last_prune_info(self.h, C.byref(t)), "tfidf_last_prune_info")
         return {k: getattr(t, k) for k, _ in PruneInfo._fields_ if k != "size"}
 
+    def reweight(self, tf="ratio", idf="ref", norm="none", params: Weighting = None) -> dict:
+        """Replaces the resident scores by the scheme's (tfidf_reweight); returns reweight_info()."""
+        w = params if params is not None else weighting(tf, idf, norm)
+        _chk(lib().tfidf_reweight(self.h, C.byref(w)), "tfidf_reweight")
+        return self.reweight_info()
+
+    def weighting(self) -> dict:
+        """The active scheme as names (tfidf_weighting_get)."""
+        w = Weighting()
+        w.size = C.sizeof(Weighting)
+        _chk(lib().tfidf_weighting_get(self.h, C.byref(w)), "tfidf_weighting_get")
+        return _weighting_names(w)
+
+    def reweight_info(self) -> dict:
+        """Counters and device times of the last reweight (tfidf_last_reweight_info)."""
+        t = ReweightInfo()
+        t.size = C.sizeof(ReweightInfo)
+        _chk(lib().tfidf_last_reweight_info(self.h, C.byref(t)), "tfidf_last_reweight_info")
+        return {k: getattr(t, k) for k, _ in ReweightInfo._fields_ if k not in ("size", "reserved")}
+
     @contextlib.contextmanager
     def fetched(self):
         """The last run's result as numpy views of the library's host arrays (tfidf_fetch
@@ -1268,6 +1358,11 @@ class Group:
         E_INVAL."""
         p = prune_params(min_df, max_df, max_features)
         _chk(lib().tfidf_group_prune(self.h, C.byref(p)), "tfidf_group_prune")
+
+    def reweight(self, tf="ratio", idf="ref", norm="none") -> None:
+        """tfidf_group_reweight: every rank reweights its shard (N and df are global)."""
+        w = weighting(tf, idf, norm)
+        _chk(lib().tfidf_group_reweight(self.h, C.byref(w)), "tfidf_group_reweight")
 
     def transform_corpus(self, c: Corpus) -> dict:
         """Group.transform of a tfidf_corpus (a device batch is E_INVAL)."""
