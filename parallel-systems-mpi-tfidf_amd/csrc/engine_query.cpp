@@ -1,0 +1,416 @@
+/*
+ * engine_query.cpp — tfidf_query, tfidf_query_bm25 and the top-k driver they share with
+ * tfidf_similar (query.hip, bm25.hip).
+ * The context and the helpers every engine file shares: engine_ctx.h.
+ */
+#include <float.h>
+#include <math.h>
+
+#include <algorithm>
+#include <string>
+#include <unordered_map>
+
+#include "engine_ctx.h"
+
+/* ------------------------------------------------------------------- query ----
+ * Top-k retrieval over the resident result (query.hip).  The host tokenises the batch
+ * (fscanf("%s") tokens, terms cut at their first NUL: TFIDF.c:141-147,152), the device maps
+ * the batch's distinct terms to term ranks, and every group of queries takes one pass over
+ * the pairs and a few top-k rounds.  The vocabulary table is only read: no stage after K1
+ * writes vkeys or vrep (the vocabulary stage reads them into its own sort keys and writes
+ * rank_of_slot at the used slots; fetch and format read them again), and all three K1
+ * kernels insert from the pair-aligned home (vocab_insert's default, VS_HOME). */
+
+static inline bool query_is_ws(uint8_t c) { return c == 0x20u || (c >= 0x09u && c <= 0x0Du); }
+
+extern "C" void tfidf_hits_free(tfidf_hits* h) {
+    if (!h) return;
+    free(h->nhits); free(h->nmatch); free(h->nterms_found); free(h->doc); free(h->score);
+    memset(h, 0, sizeof(*h));
+}
+
+/* the exact sum of doc_size over the context's documents (BM25's default avgdl): a host sum
+ * over one copy, kept until the next run */
+int tfidf_ctx_bm25_lengths(tfidf_ctx* ctx, uint64_t* L, uint64_t* n) {
+    if (!ctx || !L || !n) return TFIDF_E_INVAL;
+    if (!ctx->have_result) return TFIDF_E_STATE;
+    if (!ctx->bm25_L_valid) {
+        HIPCHK(hipSetDevice(ctx->device));
+        std::vector<uint32_t> dsz(ctx->ndocs);
+        if (ctx->ndocs) {
+            HIPCHK(hipMemcpyAsync(dsz.data(), ctx->doc_size.p, (size_t)ctx->ndocs * 4, hipMemcpyDeviceToHost, ctx->stream));
+            HIPCHK(hipStreamSynchronize(ctx->stream));
+        }
+        uint64_t sum = 0;
+        for (uint32_t v : dsz) sum += v;
+        ctx->bm25_L = sum;
+        ctx->bm25_L_valid = true;
+    }
+    *L = ctx->bm25_L;
+    *n = ctx->ndocs;
+    return TFIDF_OK;
+}
+
+int tfidf_bm25_params_check(const tfidf_bm25_params* p, Bm25Call* out) {
+    Bm25Call c{TFIDF_BM25_DEFAULT_K1, TFIDF_BM25_DEFAULT_B, 0.0};
+    if (p) {
+        if (p->size < sizeof(tfidf_bm25_params)) return TFIDF_E_INVAL;
+        c = Bm25Call{p->k1, p->b, p->avgdl};
+    }
+    /* written so that a NaN fails every test */
+    if (!(c.k1 >= 0.0 && c.k1 <= TFIDF_BM25_MAX_K1)) return TFIDF_E_INVAL;
+    if (!(c.b >= 0.0 && c.b <= 1.0)) return TFIDF_E_INVAL;
+    if (!(c.avgdl == 0.0 || (c.avgdl >= TFIDF_BM25_MIN_AVGDL && c.avgdl <= DBL_MAX))) return TFIDF_E_INVAL;
+    *out = c;
+    return TFIDF_OK;
+}
+
+/* ---- what tfidf_query, tfidf_query_bm25 and tfidf_similar share on the host: the group
+ * budget, the top-k rounds over a group's dense accumulators, the read-back of the result ---- */
+static_assert(SG_MAX == QG_MAX, "queries and rows share one group budget");
+TopkPlan topk_plan(uint32_t N, uint32_t k, uint32_t rows, uint64_t acc_bytes) {
+    TopkPlan p{};
+    p.nsl0 = ((uint64_t)N + QT_SLICE - 1) / QT_SLICE;
+    p.per_q = (uint64_t)N * 12 + 2 * (p.nsl0 * k * 12 + p.nsl0 * 4) + 8;
+    p.G = acc_bytes / p.per_q;
+    p.G = p.G < 1 ? 1 : (p.G > QG_MAX ? QG_MAX : p.G);
+    if (p.G > rows) p.G = rows ? rows : 1;
+    p.cand_el = p.G * p.nsl0 * k;
+    return p;
+}
+/* the plan's buffers: apart from the budget, because a call with nothing to scan allocates nothing */
+int topk_ensure(tfidf_ctx* ctx, const TopkPlan& p, uint32_t N) {
+    ENSURE(ctx->q_acc, p.G * N * 8);
+    ENSURE(ctx->q_cnt, p.G * N * 4);
+    ENSURE(ctx->q_big, (size_t)N * 4 + 4);
+    ENSURE(ctx->q_cand0, p.cand_el * 12 + p.G * p.nsl0 * 4);
+    ENSURE(ctx->q_cand1, p.cand_el * 12 + p.G * p.nsl0 * 4);
+    ENSURE(ctx->q_misc, p.G * 8 + 16);
+    return TFIDF_OK;
+}
+static TopkCand topk_cand(tfidf_ctx* ctx, const TopkPlan& p, int c) {
+    uint64_t* s = (c ? ctx->q_cand1 : ctx->q_cand0).as<uint64_t>();
+    uint32_t* id = (uint32_t*)(s + p.cand_el);
+    return TopkCand{s, id, id + p.cand_el};
+}
+/* the top-k rounds of a group of gn queries (rows): the accumulators' slices, then the slices'
+ * lists until one is left per query: row q = entries [q * k, q * k + n[q]) of *res */
+int topk_rounds(tfidf_ctx* ctx, const TopkPlan& p, const double* acc, const uint32_t* cnt, uint32_t N, uint32_t k,
+                uint32_t gn, unsigned long long* d_nm, TopkCand* res) {
+    hipStream_t s = ctx->stream;
+    int cur = 0;
+    TopkCand o = topk_cand(ctx, p, cur);
+    QTopkArgs ta{};
+    ta.acc = acc;
+    ta.cnt = cnt;
+    ta.order = ctx->order;
+    ta.doc_ids = ctx->dev_ids;
+    ta.n_in = N;
+    ta.kk = k;
+    ta.out_s = o.s;
+    ta.out_id = o.id;
+    ta.out_n = o.n;
+    ta.out_slices = (uint32_t)p.nsl0;
+    ta.nmatch = d_nm;
+    LAUNCH(launch_query_topk(ta, gn, s));
+    uint64_t nsl = p.nsl0;
+    while (nsl > 1) {
+        const TopkCand in = o;
+        QTopkArgs tb{};
+        tb.in_s = in.s;
+        tb.in_id = in.id;
+        tb.in_n = in.n;
+        tb.in_slices = (uint32_t)nsl;
+        tb.n_in = nsl * k;
+        tb.kk = k;
+        nsl = (tb.n_in + QT_SLICE - 1) / QT_SLICE;
+        cur ^= 1;
+        o = topk_cand(ctx, p, cur);
+        tb.out_s = o.s;
+        tb.out_id = o.id;
+        tb.out_n = o.n;
+        tb.out_slices = (uint32_t)nsl;
+        tb.nmatch = d_nm;
+        LAUNCH(launch_query_topk(tb, gn, s));
+    }
+    *res = o;
+    return TFIDF_OK;
+}
+/* the result of topk_rounds and the match counts on the host; waits for the stream */
+int topk_read_back(tfidf_ctx* ctx, const TopkCand& res, const unsigned long long* d_nm, uint32_t gn, uint32_t k,
+                   uint64_t* h_s, uint32_t* h_id, uint32_t* h_n, uint64_t* h_nm) {
+    hipStream_t s = ctx->stream;
+    HIPCHK(hipMemcpyAsync(h_s, res.s, (size_t)gn * k * 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(h_id, res.id, (size_t)gn * k * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(h_n, res.n, (size_t)gn * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(h_nm, d_nm, (size_t)gn * 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return TFIDF_OK;
+}
+
+int tfidf_ctx_query(tfidf_ctx* ctx, const tfidf_queries* qs, uint32_t k, tfidf_hits* out, std::vector<uint8_t>* found_out,
+                    std::vector<uint64_t>* found_off_out, const Bm25Call* bm) {
+    if (!ctx || !qs || !out) return TFIDF_E_INVAL;
+    if (k == 0 || k > TFIDF_QUERY_MAX_K || qs->nqueries > TFIDF_QUERY_MAX_QUERIES) return TFIDF_E_INVAL;
+    const uint32_t nq = qs->nqueries;
+    if (nq && !qs->q_off) return TFIDF_E_INVAL;
+    for (uint32_t q = 0; q < nq; ++q)
+        if (qs->q_off[q] > qs->q_off[q + 1]) return TFIDF_E_INVAL;
+    if (nq && (qs->q_off[nq] > qs->nbytes || (qs->q_off[nq] > qs->q_off[0] && !qs->bytes))) return TFIDF_E_INVAL;
+    if (!ctx->have_result) return TFIDF_E_STATE;
+    const auto wall0 = std::chrono::steady_clock::now();
+    if (const int rc = call_begin(ctx, ctx->ev_q)) return rc;
+    hipStream_t s = ctx->stream;
+    double avgdl = 0.0;   /* BM25: 0 = no document has a token, every row is empty */
+    if (bm) {
+        avgdl = bm->avgdl;
+        if (!(avgdl > 0.0)) {
+            uint64_t L = 0, n = 0;
+            const int rc = tfidf_ctx_bm25_lengths(ctx, &L, &n);
+            if (rc) return rc;
+            avgdl = L ? (double)L / (double)n : 0.0;
+        }
+    }
+    memset(out, 0, sizeof(*out));
+    out->nqueries = nq;
+    out->k = k;
+    out->nhits = (uint32_t*)calloc((size_t)nq + 1, 4);
+    out->nmatch = (uint64_t*)calloc((size_t)nq + 1, 8);
+    out->nterms_found = (uint32_t*)calloc((size_t)nq + 1, 4);
+    out->doc = (uint32_t*)calloc((size_t)nq * k + 1, 4);
+    out->score = (double*)calloc((size_t)nq * k + 1, 8);
+    struct HitsGuard {   /* an error return leaves *out zeroed */
+        tfidf_hits* h;
+        ~HitsGuard() { if (h) tfidf_hits_free(h); }
+    } guard{out};
+    if (!out->nhits || !out->nmatch || !out->nterms_found || !out->doc || !out->score) return TFIDF_E_NOMEM;
+
+    /* ---- tokens -> the batch's distinct terms, per query (term, weight) in first-occurrence order ---- */
+    std::unordered_map<std::string, uint32_t> term_id;
+    std::vector<const std::string*> terms;
+    std::vector<uint64_t> qt_off((size_t)nq + 1, 0);
+    std::vector<uint32_t> qt_term, qt_w;
+    for (uint32_t q = 0; q < nq; ++q) {
+        const uint8_t* b = qs->bytes;
+        const uint64_t e = qs->q_off[q + 1];
+        std::unordered_map<uint32_t, size_t> seen;
+        for (uint64_t i = qs->q_off[q]; i < e;) {
+            while (i < e && query_is_ws(b[i])) ++i;
+            if (i >= e) break;
+            const uint64_t t0 = i;
+            while (i < e && !query_is_ws(b[i])) ++i;
+            uint64_t tl = 0;
+            while (t0 + tl < i && b[t0 + tl] != 0) ++tl;   /* strcmp semantics: up to the first NUL */
+            auto ins = term_id.emplace(std::string((const char*)b + t0, (size_t)tl), (uint32_t)terms.size());
+            if (ins.second) terms.push_back(&ins.first->first);
+            auto at = seen.emplace(ins.first->second, qt_term.size());
+            if (at.second) { qt_term.push_back(ins.first->second); qt_w.push_back(1u); }
+            else if (qt_w[at.first->second] != 0xFFFFFFFFu) ++qt_w[at.first->second];
+        }
+        qt_off[q + 1] = qt_term.size();
+    }
+    const uint32_t nT = (uint32_t)terms.size();
+    tfidf_query_info qi{};
+    qi.nqueries = nq;
+    qi.k = k;
+    qi.nterms = nT;
+
+    /* ---- lookup: one lane per distinct term ---- */
+    std::vector<uint32_t> rank(nT, QUERY_NO_TERM), df_found(bm ? nT : 0, 0u);
+    std::vector<uint64_t> toff((size_t)nT + 1, 0);
+    std::string blob;
+    if (nT && ctx->V) {
+        for (uint32_t t = 0; t < nT; ++t) { toff[t] = blob.size(); blob += *terms[t]; }
+        toff[nT] = blob.size();
+        const size_t offb = ((size_t)nT + 1) * 8;
+        ENSURE(ctx->q_terms, offb + blob.size() + 16);
+        ENSURE(ctx->q_rank, (size_t)nT * (bm ? 8 : 4) + 4);   /* BM25: the found terms' df behind the ranks */
+        HIPCHK(hipMemcpyAsync(ctx->q_terms.p, toff.data(), offb, hipMemcpyHostToDevice, s));
+        if (!blob.empty())
+            HIPCHK(hipMemcpyAsync(ctx->q_terms.as<uint8_t>() + offb, blob.data(), blob.size(), hipMemcpyHostToDevice, s));
+        QLookupArgs la{};
+        la.tbytes = ctx->q_terms.as<uint8_t>() + offb;
+        la.toff = ctx->q_terms.as<uint64_t>();
+        la.nterms = nT;
+        la.vkeys = ctx->vkeys.as<uint4>();
+        la.vrep = ctx->vrep.as<uint64_t>();
+        la.mask = ctx->vcap - 1;
+        la.home = ~1ull;
+        la.rank_of_slot = ctx->rank_of_slot.as<uint32_t>();
+        la.corpus = ctx->dev_bytes;
+        la.corpus_bytes = ctx->corpus.nbytes;
+        la.V = ctx->V;
+        la.rank_out = ctx->q_rank.as<uint32_t>();
+        HIPCHK(hipEventRecord(ctx->ev_q[0], s));
+        LAUNCH(launch_query_lookup(la, s));
+        LAUNCH(bm && launch_bm25_df(la.rank_out, nT, df_of_run(ctx), ctx->V, la.rank_out + nT, s));
+        HIPCHK(hipEventRecord(ctx->ev_q[1], s));
+        HIPCHK(hipMemcpyAsync(rank.data(), ctx->q_rank.p, (size_t)nT * 4, hipMemcpyDeviceToHost, s));
+        if (bm) HIPCHK(hipMemcpyAsync(df_found.data(), la.rank_out + nT, (size_t)nT * 4, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        qi.ms_lookup = ev_ms(ctx->ev_q[0], ctx->ev_q[1]);
+    }
+    for (uint32_t t = 0; t < nT; ++t) qi.nterms_found += rank[t] != QUERY_NO_TERM;
+    if (found_out) found_out->assign(qt_term.size(), 0);
+    if (found_off_out) *found_off_out = qt_off;
+    for (uint32_t q = 0; q < nq; ++q)
+        for (uint64_t x = qt_off[q]; x < qt_off[q + 1]; ++x)
+            if (rank[qt_term[x]] != QUERY_NO_TERM) {
+                ++out->nterms_found[q];
+                if (found_out) (*found_out)[x] = 1;
+            }
+
+    /* ---- BM25: idf per distinct found term, the host's libm log (one operation per line) ---- */
+    std::vector<double> idf(bm ? nT : 0, 0.0);
+    for (uint32_t t = 0; bm && t < nT; ++t) {
+        if (rank[t] == QUERY_NO_TERM) continue;
+        const uint64_t Nt = ctx->ndocs_total, df = df_found[t] < Nt ? df_found[t] : Nt;
+        const double num = (double)(Nt - df) + 0.5;
+        const double den = (double)df + 0.5;
+        const double ratio = num / den;
+        const double arg = 1.0 + ratio;
+        idf[t] = log(arg);
+    }
+
+    /* ---- query groups under the accumulator budget ---- */
+    /* BM25 with avgdl 0 (L = 0: no document of the context has a token, so there are no pairs):
+     * N = 0 turns every group below off and the rows stay empty, as the header defines */
+    const uint32_t N = bm && !(avgdl > 0.0) ? 0u : ctx->ndocs;
+    const TopkPlan plan = topk_plan(N, k, nq, ctx->query_acc_bytes);
+    const uint64_t G = plan.G;
+    qi.group_queries = (uint32_t)G;
+    qi.acc_bytes = G * plan.per_q;
+    if (N && nq) {
+        const int rc = topk_ensure(ctx, plan, N);
+        if (rc) return rc;
+    }
+    std::vector<uint64_t> h_s((size_t)G * k), h_nm(G);
+    std::vector<uint32_t> h_id((size_t)G * k), h_n(G);
+    struct Post { uint32_t rank, q, w, term; };
+    std::vector<Post> posts;
+    std::vector<uint32_t> tab;
+    for (uint32_t g0 = 0; N && g0 < nq; g0 += (uint32_t)G) {
+        const uint32_t gn = nq - g0 < G ? nq - g0 : (uint32_t)G;
+        posts.clear();
+        for (uint32_t q = 0; q < gn; ++q)
+            for (uint64_t x = qt_off[g0 + q]; x < qt_off[g0 + q + 1]; ++x)
+                if (rank[qt_term[x]] != QUERY_NO_TERM) posts.push_back(Post{rank[qt_term[x]], q, qt_w[x], qt_term[x]});
+        if (posts.empty()) continue;   /* no term of the group is in the vocabulary: no hits */
+        if (posts.size() > 0x7FFFFFFFull) return TFIDF_E_CAPACITY;
+        ++qi.ngroups;
+        std::sort(posts.begin(), posts.end(), [](const Post& a, const Post& b) { return a.rank != b.rank ? a.rank < b.rank : a.q < b.q; });
+        /* the group's table: sorted distinct ranks, CSR offsets, postings' queries and weights */
+        uint32_t nG = 0;
+        for (size_t i = 0; i < posts.size(); ++i) nG += i == 0 || posts[i].rank != posts[i - 1].rank;
+        const uint32_t nP = (uint32_t)posts.size();
+        /* BM25: the weights are binary64 W(q,t) = fl(w * idf), at the next even word */
+        const size_t w_at = (size_t)2 * nG + 1 + nP + (bm ? (nP + 1) & 1u : 0u);
+        tab.assign(w_at + (bm ? 2 : 1) * (size_t)nP, 0);
+        uint32_t* gterm = tab.data();
+        uint32_t* poff = gterm + nG;
+        uint32_t* pq = poff + nG + 1;
+        uint32_t* pw = gterm + w_at;
+        for (uint32_t i = 0, t = 0; i < nP; ++i) {
+            if (i == 0 || posts[i].rank != posts[i - 1].rank) { gterm[t] = posts[i].rank; poff[t] = i; ++t; }
+            pq[i] = posts[i].q;
+            if (bm) {
+                const double W = (double)posts[i].w * idf[posts[i].term];
+                memcpy(pw + 2 * (size_t)i, &W, 8);
+            } else {
+                pw[i] = posts[i].w;
+            }
+        }
+        poff[nG] = nP;
+        ENSURE(ctx->q_tab, tab.size() * 4 + 16);
+        HIPCHK(hipMemcpyAsync(ctx->q_tab.p, tab.data(), tab.size() * 4, hipMemcpyHostToDevice, s));
+        unsigned long long* d_nm = ctx->q_misc.as<unsigned long long>();
+        HIPCHK(hipMemsetAsync(d_nm, 0, (size_t)G * 8, s));
+        DocScanArgs sa{};
+        sa.out_off = ctx->out_off.as<uint64_t>();
+        sa.out_term = ctx->out_term.as<uint32_t>();
+        sa.ndocs = N;
+        sa.npairs = ctx->npairs;
+        sa.gterm = ctx->q_tab.as<uint32_t>();
+        sa.ngterm = nG;
+        sa.post_off = sa.gterm + nG;
+        sa.post_q = sa.post_off + nG + 1;
+        sa.post_w = sa.gterm + w_at;
+        sa.tab_words = tab.size() <= 0xFFFFFFFFull ? (uint32_t)tab.size() : 0u;
+        sa.nq = gn;
+        sa.acc = ctx->q_acc.as<double>();
+        sa.cnt = ctx->q_cnt.as<uint32_t>();
+        sa.big_list = ctx->q_big.as<uint32_t>();
+        sa.big_count = (uint32_t*)(d_nm + G);
+        HIPCHK(hipEventRecord(ctx->ev_q[0], s));
+        int lrc;
+        if (bm) {
+            BScoreArgs ba{sa};
+            ba.out_cnt = ctx->out_cnt.as<uint32_t>();
+            ba.order = ctx->order;
+            ba.doc_size = ctx->doc_size.as<uint32_t>();
+            ba.k1 = bm->k1;
+            ba.b = bm->b;
+            ba.avgdl = avgdl;
+            ba.k1_plus_1 = bm->k1 + 1.0;
+            ba.one_minus_b = 1.0 - bm->b;
+            lrc = launch_bm25_score(ba, ctx->ncu, s);
+        } else {
+            QScoreArgs ta{sa};
+            ta.out_score = ctx->out_score.as<double>();
+            lrc = launch_query_score(ta, ctx->ncu, s);
+        }
+        LAUNCH(lrc);
+        HIPCHK(hipEventRecord(ctx->ev_q[1], s));
+        TopkCand res{};
+        int rc = topk_rounds(ctx, plan, sa.acc, sa.cnt, N, k, gn, d_nm, &res);
+        if (rc) return rc;
+        HIPCHK(hipEventRecord(ctx->ev_q[2], s));
+        rc = topk_read_back(ctx, res, d_nm, gn, k, h_s.data(), h_id.data(), h_n.data(), h_nm.data());
+        if (rc) return rc;
+        qi.ms_score += ev_ms(ctx->ev_q[0], ctx->ev_q[1]);
+        qi.ms_topk += ev_ms(ctx->ev_q[1], ctx->ev_q[2]);
+        for (uint32_t q = 0; q < gn; ++q) {
+            const uint32_t n = h_n[q] < k ? h_n[q] : k;
+            out->nhits[g0 + q] = n;
+            out->nmatch[g0 + q] = h_nm[q];
+            for (uint32_t i = 0; i < n; ++i) {
+                out->doc[(size_t)(g0 + q) * k + i] = h_id[(size_t)q * k + i];
+                memcpy(&out->score[(size_t)(g0 + q) * k + i], &h_s[(size_t)q * k + i], 8);
+            }
+        }
+    }
+    qi.ms_total = wall_ms(wall0);
+    if (bm) {
+        tfidf_bm25_info bi{};
+        bi.nqueries = qi.nqueries; bi.k = qi.k; bi.nterms = qi.nterms; bi.nterms_found = qi.nterms_found;
+        bi.ngroups = qi.ngroups; bi.group_queries = qi.group_queries; bi.acc_bytes = qi.acc_bytes;
+        bi.ms_lookup = qi.ms_lookup; bi.ms_score = qi.ms_score; bi.ms_topk = qi.ms_topk; bi.ms_total = qi.ms_total;
+        bi.avgdl = avgdl;
+        ctx->binfo = bi;
+    } else {
+        ctx->qinfo = qi;
+    }
+    guard.h = nullptr;
+    return TFIDF_OK;
+}
+
+extern "C" int tfidf_query(tfidf_ctx* ctx, const tfidf_queries* queries, uint32_t k, tfidf_hits* out) {
+    return tfidf_ctx_query(ctx, queries, k, out, nullptr, nullptr);
+}
+
+extern "C" int tfidf_query_bm25(tfidf_ctx* ctx, const tfidf_queries* queries, uint32_t k, const tfidf_bm25_params* params,
+                                tfidf_hits* out) {
+    if (!ctx || !queries || !out) return TFIDF_E_INVAL;
+    Bm25Call bm{};
+    const int rc = tfidf_bm25_params_check(params, &bm);
+    if (rc) return rc;
+    return tfidf_ctx_query(ctx, queries, k, out, nullptr, nullptr, &bm);
+}
+
+extern "C" int tfidf_last_bm25_info(const tfidf_ctx* ctx, tfidf_bm25_info* info) {
+    return ctx ? copy_info(info, ctx->binfo) : TFIDF_E_INVAL;
+}
+
+extern "C" int tfidf_last_query_info(const tfidf_ctx* ctx, tfidf_query_info* info) {
+    return ctx ? copy_info(info, ctx->qinfo) : TFIDF_E_INVAL;
+}

@@ -59,13 +59,13 @@ struct Xport {
 int tfidf_ctx_attach_xport(tfidf_ctx* ctx, Xport* xp);
 int tfidf_ctx_device(const tfidf_ctx* ctx);
 hipStream_t tfidf_ctx_stream(const tfidf_ctx* ctx);
-/* engine.cpp: tfidf_query that also reports which query terms the shard's vocabulary holds:
+/* engine_query.cpp: tfidf_query that also reports which query terms the shard's vocabulary holds:
  * found[found_off[q] + i] for the i-th distinct term of query q in first-occurrence order
  * (the same numbering on every rank: tfidf_group_query counts a term found by any rank once) */
 struct Bm25Call;
 int tfidf_ctx_query(tfidf_ctx* ctx, const tfidf_queries* queries, uint32_t k, tfidf_hits* out,
                     std::vector<uint8_t>* found, std::vector<uint64_t>* found_off, const Bm25Call* bm = nullptr);
-/* engine.cpp: tfidf_query_bm25 is tfidf_ctx_query with validated parameters (bm non-null: the
+/* engine_query.cpp: tfidf_query_bm25 is tfidf_ctx_query with validated parameters (bm non-null: the
  * scoring pass is bm25.hip's, the counters go to tfidf_last_bm25_info).  avgdl 0: this
  * context's own average */
 struct Bm25Call {
@@ -76,7 +76,7 @@ int tfidf_bm25_params_check(const tfidf_bm25_params* params, Bm25Call* out);
 /* L = the exact sum of docSize over the context's documents, n = the documents it holds */
 int tfidf_ctx_bm25_lengths(tfidf_ctx* ctx, uint64_t* L, uint64_t* n);
 
-/* engine.cpp: the two halves of tfidf_group_similar on one shard.  Export: the rows' documents
+/* engine_similar.cpp: the two halves of tfidf_group_similar on one shard.  Export: the rows' documents
  * as this shard holds them (pos UINT32_MAX: it does not; the row is empty): row i's vector is
  * entries [voff[i], voff[i + 1]) of (word, score), word x = wbytes[woff[x], woff[x + 1]), in
  * term-table order.  Search: this shard's neighbours of rows given that way (id, norm, voff,
@@ -99,7 +99,7 @@ double tfidf_weight_tf_log(uint32_t c);                                        /
 double tfidf_weight_idf(uint32_t mode, uint64_t N, uint32_t df);
 int tfidf_weight_normalize(double* w, uint64_t n, uint32_t norm);              /* one row in place; 1: the norm is 0 */
 }
-/* engine.cpp: tfidf_transform is tfidf_ctx_transform with norm = true.  norm = false leaves the
+/* engine_transform.cpp: tfidf_transform is tfidf_ctx_transform with norm = true.  norm = false leaves the
  * active scheme's row norm out (w is returned): tfidf_group_transform normalises the merged rows */
 struct tfidf_corpus;
 struct tfidf_rows;
