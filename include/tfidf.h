@@ -1299,6 +1299,145 @@ int tfidf_last_reweight_info(const tfidf_ctx* ctx, tfidf_reweight_info* info);
  * untouched then. */
 int tfidf_result_reweight(tfidf_result* r, const tfidf_weighting* w);
 
+/* ---------------------------------------------------------- near duplicates -- */
+
+/* Which documents of the resident result are copies or near-copies of one another: min-wise
+ * hashing over each document's term set, LSH bands to propose candidate pairs, and an exact
+ * Jaccard verification of every candidate.  With word shingles in front of the run
+ * (tfidf_ngrams) a document's set is its shingle set.  All of it is integer arithmetic plus one
+ * correctly rounded division; all integers are unsigned and wrap at their width.
+ *
+ *   mix64(z)    z ^= z >> 30; z *= 0xBF58476D1CE4E5B9; z ^= z >> 27; z *= 0x94D049BB133111EB;
+ *               z ^= z >> 31
+ *   S(d)        the terms of document d's resident pairs (after tfidf_prune: the kept words);
+ *               counts and scores play no part (tfidf_reweight has no effect); n(d) = |S(d)|
+ *   documents   in output order (the "docN@" order, position pos), as in tfidf_kmeans.  A
+ *               document with n(d) = 0 takes part in nothing: its signature is all 0xFFFFFFFF,
+ *               it is in no candidate pair and it is a group of one
+ *   h0(t)       mix64(FNV-1a-64(term bytes)), offset basis 0xCBF29CE484222325 and prime
+ *               0x100000001B3 (the model file's): a function of the bytes alone, the same in
+ *               every shard and on an imported model
+ *   family      from a u64 seed: s = seed; next() = mix64(s += 0x9E3779B97F4A7C15); for
+ *               i = 0..H-1 in this order a_i = next() | 1, b_i = (u32)(next() >> 32);
+ *               g_i(x) = (u32)((a_i * x mod 2^64) >> 32) + b_i mod 2^32
+ *   signature   sig[d][i] = min over t in S(d) of g_i(h0(t)), a u32; 1 <= H <= 256
+ *   bands       r rows each, r >= 1, r divides H, b = H / r.  Band key of (d, j), j = 0..b-1:
+ *               k = mix64(j + 1); for i = j*r .. j*r + r - 1 in order k = mix64(k ^ sig[d][i])
+ *   candidates  for every band j the documents with n(d) >= 1 are ordered by (band key, pos);
+ *               each two consecutive documents with equal keys give the candidate
+ *               (pos_a, pos_b), pos_a < pos_b: a chain, so m equal documents give m - 1
+ *               candidates, never m^2.  C = the union over the bands, as a set; ncand = |C|
+ *   verify      for every candidate: shared = the terms S(a) and S(b) have in common (by term
+ *               rank), uni = n(a) + n(b) - shared, jaccard = fl((double)shared / (double)uni) (one IEEE binary64 division),
+ *               same = the number of i with sig[a][i] == sig[b][i] (same / H is the estimate).
+ *               A candidate is kept when jaccard >= threshold (a plain double compare).  The
+ *               kept edges are ordered by (pos_a, pos_b)
+ *   groups      the connected components of the kept edges over the positions; group[pos] is
+ *               the lowest position of its component (the document's own when it is alone)
+ *
+ * Consequences: every reported pair is exact.  Which pairs become candidates is a deterministic
+ * function of (result, H, r, seed).  The chance that a pair of Jaccard s shares a band is the
+ * textbook 1 - (1 - s^r)^b; chaining links a bucket's members in position order, and a stranger
+ * that collides into a bucket splits the chain, it does not remove it.  Nothing depends on grid,
+ * launch shape or budget.  With the defaults (H = 128, r = 4) the S-curve's midpoint is
+ * (1/32)^(1/4) ~ 0.42 and a pair at 0.8 is missed with probability (1 - 0.8^4)^32 < 1e-7: that
+ * follows from the formula; nothing of it is measured.
+ *
+ * `size` is set by the caller to sizeof(tfidf_dedup_params).  nhashes == 0 selects the defaults
+ * H = 128, r = 4, seed = 1 (rows and seed are ignored then). */
+#define TFIDF_MINHASH_MAX_H      256u
+#define TFIDF_DEDUP_DEFAULT_H    128u
+#define TFIDF_DEDUP_DEFAULT_ROWS 4u
+#define TFIDF_DEDUP_DEFAULT_SEED 1ull
+typedef struct tfidf_dedup_params {
+    uint64_t size;
+    uint32_t nhashes;     /* H; 0: the defaults */
+    uint32_t rows;        /* r */
+    uint64_t seed;
+    double   threshold;   /* in [0, 1]; tfidf_minhash checks and ignores it */
+} tfidf_dedup_params;
+/* Host only.  TFIDF_E_INVAL for: NULL; size < sizeof(tfidf_dedup_params); H > 256; with H != 0
+ * r == 0 or r not dividing H; a threshold outside [0, 1] or NaN. */
+int tfidf_dedup_check(const tfidf_dedup_params* params);
+
+/* Signatures, row-major ndocs * nhashes, documents in output order.  Arrays are owned by the
+ * library and released by tfidf_signatures_free(). */
+typedef struct tfidf_signatures {
+    uint32_t  ndocs;
+    uint32_t  nhashes;
+    uint32_t* doc;        /* global id by position */
+    uint32_t* npairs;     /* n(d) by position */
+    uint32_t* sig;        /* ndocs * nhashes */
+} tfidf_signatures;
+typedef struct tfidf_dups {
+    uint32_t  ndocs;
+    uint32_t  ngroups;    /* components of two or more documents */
+    uint64_t  ncand;      /* |C| */
+    uint64_t  nedges;     /* kept candidates */
+    uint32_t* doc;        /* ndocs: global id by position */
+    uint32_t* group;      /* ndocs: the lowest position of the document's component */
+    /* per kept edge, ordered by (a_pos, b_pos) */
+    uint32_t* a_pos;
+    uint32_t* b_pos;
+    uint32_t* a_doc;
+    uint32_t* b_doc;
+    uint32_t* shared;
+    uint32_t* uni;
+    uint32_t* same;
+    double*   jaccard;
+} tfidf_dups;
+/* Over the resident result of the last run, one shard (there is no group form yet; h0 is defined
+ * on bytes so that one can be bit-identical).  The result is not disturbed.  The run's corpus
+ * must still be valid: the bytes of terms of 16 bytes and more are read from it.  With a
+ * communicator attached the call is local.  All device buffers belong to the context: a
+ * repeated identical call allocates nothing (tfidf_alloc_stats).  The per-term h0 table (8 bytes
+ * per term) is kept until the next tfidf_run, tfidf_prune or tfidf_model_import.
+ * TFIDF_E_INVAL: NULL arguments or parameters that fail the check.  TFIDF_E_STATE: before a
+ * successful run, and on a context that holds only an imported model.  TFIDF_E_CAPACITY, before
+ * any device work: when ndocs * H * 4 (the signatures) plus the bound b * (M - 1) * 16 on the
+ * candidate scratch (M = the documents with pairs) exceeds TFIDF_DEDUP_MB MiB (environment, read
+ * by tfidf_open; default 1024, a guess that no measurement stands behind), or when b * M does
+ * not fit 32 bits.  On an error *out is zeroed. */
+int tfidf_minhash(tfidf_ctx* ctx, const tfidf_dedup_params* params, tfidf_signatures* out);
+void tfidf_signatures_free(tfidf_signatures* s);
+int tfidf_near_dups(tfidf_ctx* ctx, const tfidf_dedup_params* params, tfidf_dups* out);
+void tfidf_dups_free(tfidf_dups* d);
+/* Counters of the last tfidf_minhash or tfidf_near_dups (the caller sets `size` = sizeof, as
+ * tfidf_query_info).  tfidf_minhash leaves the candidate counters and their times 0. */
+typedef struct tfidf_dedup_info {
+    uint64_t size;
+    uint32_t ndocs;
+    uint32_t nhashes;
+    uint32_t rows;
+    uint32_t clusterable;   /* M: documents with n(d) >= 1 */
+    uint64_t ncand;
+    uint64_t nedges;
+    uint32_t ngroups;
+    uint32_t big_docs;      /* documents the one-workgroup-per-document signature launch took */
+    uint64_t sig_bytes;     /* ndocs * H * 4 */
+    uint64_t work_bytes;    /* device scratch of the band and verify stages */
+    double   ms_hash;       /* device times (HIP events): the h0 table (0 when it was kept) */
+    double   ms_sig;        /* the signature pass */
+    double   ms_bands;      /* band keys, sorts, candidates */
+    double   ms_verify;     /* the exact intersection */
+    double   ms_total;      /* host wall time of the whole call */
+} tfidf_dedup_info;
+int tfidf_last_dedup_info(const tfidf_ctx* ctx, tfidf_dedup_info* info);
+/* Host only, plain C (dedup_host.c): the same definition on a fetched result, the second opinion
+ * on the device.  A document's set is the pair_term of its pairs (a document is a maximal run of
+ * equal pair_doc); the documents are r->doc_id in "docN@" order, so a document without pairs is
+ * there with n(d) = 0; a term's bytes come from the term table.  TFIDF_E_INVAL for NULL
+ * arguments, parameters that fail the check, a pair_term outside the term table or a pair_doc
+ * that is not among doc_id; *out is zeroed then. */
+int tfidf_result_minhash(const tfidf_result* r, const tfidf_dedup_params* params, tfidf_signatures* out);
+int tfidf_result_near_dups(const tfidf_result* r, const tfidf_dedup_params* params, tfidf_dups* out);
+/* Host only: group[pos] = the lowest position of pos's component under the n edges
+ * (a_pos[i], b_pos[i]) over positions 0..ndocs-1, and *ngroups = the components of two or more.
+ * The union-find both paths end with.  TFIDF_E_INVAL for a NULL array that is needed or an edge
+ * outside the positions. */
+int tfidf_dedup_groups(uint32_t ndocs, const uint32_t* a_pos, const uint32_t* b_pos, uint64_t n, uint32_t* group,
+                       uint32_t* ngroups);
+
 /* ---------------------------------------------------------------- ingest ---- */
 
 /* Reference input contract (TFIDF.c:98-110,130-147): N = number of entries of `dir`

@@ -188,6 +188,11 @@ int tfidf_open(int device, tfidf_ctx** out) {
         const unsigned long long mb = strtoull(ktr, nullptr, 0);
         if (mb >= 1 && mb <= (1ull << 20)) ctx->transform_bytes = mb << 20;
     }
+    const char* kdd = getenv("TFIDF_DEDUP_MB");
+    if (kdd) {
+        const unsigned long long mb = strtoull(kdd, nullptr, 0);
+        if (mb >= 1 && mb <= (1ull << 20)) ctx->dedup_bytes = mb << 20;
+    }
     const char* kkm = getenv("TFIDF_KMEANS_MB");
     if (kkm) {
         const unsigned long long mb = strtoull(kkm, nullptr, 0);
@@ -292,6 +297,9 @@ void tfidf_close(tfidf_ctx* ctx) {
     for (hipEvent_t e : ctx->ev_k)
         if (e) (void)hipEventDestroy(e);
     for (DevBuf* b : {&ctx->km_C, &ctx->km_work, &ctx->km_top, &ctx->km_words}) b->release();
+    for (hipEvent_t e : ctx->ev_dd)
+        if (e) (void)hipEventDestroy(e);
+    for (DevBuf* b : {&ctx->dd_h0, &ctx->dd_sig, &ctx->dd_fam, &ctx->dd_misc, &ctx->dd_work}) b->release();
     for (hipEvent_t e : ctx->ev_tr)
         if (e) (void)hipEventDestroy(e);
     for (DevBuf* b : {&ctx->tr_bytes, &ctx->tr_off, &ctx->tr_a, &ctx->tr_b}) b->release();
@@ -1536,6 +1544,7 @@ extern "C" int tfidf_run(tfidf_ctx* ctx, const tfidf_corpus* in) {
     ctx->text_valid = false;
     ctx->tmeta_valid = false;
     ctx->norm_valid = false;
+    ctx->h0_valid = false;
     ctx->bm25_L_valid = false;
     CorpusDev c{};
     const uint32_t* dev_ids = nullptr;

@@ -16,6 +16,7 @@
  *   engine_terms.cpp      tfidf_top_terms
  *   engine_similar.cpp    tfidf_similar, the halves of tfidf_group_similar; sim_norms
  *   engine_kmeans.cpp     tfidf_kmeans
+ *   engine_dedup.cpp      tfidf_minhash, tfidf_near_dups (dedup.hip; the groups: dedup_host.c)
  * The add-on calls run between runs on the context's stream and use the run's arena as scratch
  * only; none of them is on the path tfidf_run times.
  */
@@ -305,6 +306,15 @@ struct tfidf_ctx {
     std::vector<double> rw_listv_host;
     hipEvent_t ev_rw[3] = {};                   /* tables / pairs bounds (created by the first call) */
     tfidf_reweight_info rwinfo{};
+    /* near duplicates (tfidf_minhash / tfidf_near_dups, dedup.hip): h0 by term rank (kept until the
+     * next run, prune or import), the signatures by output position, the hash family, the counter
+     * words with the list of big documents behind them, and the band and verify stages' work
+     * buffer (keys, values, flags, candidates, the positions with pairs) */
+    DevBuf dd_h0, dd_sig, dd_fam, dd_misc, dd_work;
+    uint64_t dedup_bytes = 1024ull << 20;       /* env TFIDF_DEDUP_MB: signatures + the bound on candidate scratch */
+    hipEvent_t ev_dd[3] = {};                   /* hash / signature, bands / verify bounds (created by the first call) */
+    bool h0_valid = false;                      /* dd_h0 holds this result's term hashes */
+    tfidf_dedup_info ddinfo{};
 #define WR_NBUF 8
 #define WR_BUF (16ull << 20)
 #define WR_GROUPS 8

@@ -927,4 +927,69 @@ struct RwArgs {
 };
 int launch_rw_pairs(const RwArgs& a, uint32_t ncu, hipStream_t s);
 
+/* ---- near duplicates (dedup.hip, tfidf_minhash / tfidf_near_dups) ---- */
+#define DD_BIG_PAIRS 4096u         /* documents over this many pairs: a workgroup each in the signature pass, and
+                                      candidates that hold one a workgroup each in the verification (QS_BIG's cut) */
+#define DD_MAX_H 256u              /* TFIDF_MINHASH_MAX_H */
+/* h0[r] = mix64(FNV-1a-64(term bytes)), one lane per term rank: the bytes of a short term from
+ * tkey (tlen of them), of a long term from the corpus at the position tkey holds (launch_term_meta) */
+int launch_dd_h0(const uint4* tkey, const uint32_t* tlen, uint32_t V, const uint8_t* corpus, uint64_t corpus_bytes,
+                 uint64_t* h0, hipStream_t s);
+/* The signature pass, document-major: sig[j * H + i] = min over the pairs p of document j (pairs
+ * [off[j], off[j + 1]) clamped to npairs) of (u32)((fam_a[i] * h0[term[p]]) >> 32) + fam_b[i];
+ * 0xFFFFFFFF for a document without pairs.  A wave per document whose lanes own the hash
+ * functions (i = lane, lane + 64, ..); documents over DD_BIG_PAIRS pairs go to a second launch, a
+ * workgroup each, whose waves combine their minima in LDS.  A minimum is order-free: the shape
+ * changes no bit. */
+struct DdSigArgs {
+    const uint64_t* off;         /* ndocs + 1 */
+    uint64_t npairs;
+    uint32_t ndocs;
+    uint32_t H;                  /* 1..DD_MAX_H */
+    uint32_t V;                  /* terms at or above it are skipped (never with valid input) */
+    const uint32_t* term;        /* per pair: term rank */
+    const uint64_t* h0;          /* V */
+    const uint64_t* fam_a;       /* DD_MAX_H */
+    const uint32_t* fam_b;       /* DD_MAX_H */
+    uint32_t* sig;               /* ndocs * H */
+    uint32_t* big_list;          /* [ndocs] scratch */
+    uint32_t* big_count;         /* one word, zeroed by the launch */
+};
+int launch_dd_sig(const DdSigArgs& a, uint32_t ncu, hipStream_t s);
+/* Band keys in band-major order: entry x = j * M + m (band j, the m-th document with pairs,
+ * position live[m]) gets key[x] = the band key of include/tfidf.h and val[x] = x. */
+int launch_dd_bandkeys(const uint32_t* sig, const uint32_t* live, uint32_t M, uint32_t H, uint32_t rows, uint64_t* key,
+                       uint32_t* val, hipStream_t s);
+/* flag[x] = 1 when the sorted entries x - 1 and x hold equal keys of one band (val / M), else 0
+ * (flag[0] = 0); n entries */
+int launch_dd_runflag(const uint64_t* key, const uint32_t* val, uint64_t n, uint32_t M, uint32_t* flag, hipStream_t s);
+/* the flagged entries' candidates (live[val[x - 1] % M] << 32 | live[val[x] % M]) at at[x]
+ * (the flags' exclusive scan) */
+int launch_dd_runwrite(const uint32_t* val, const uint32_t* at, uint64_t n, uint32_t M, const uint32_t* live,
+                       uint64_t* cand, hipStream_t s);
+/* flag[x] = 1 when the sorted candidate x differs from x - 1 (flag[0] = 1), and the write of the
+ * flagged ones at at[x] */
+int launch_dd_uniqflag(const uint64_t* cand, uint64_t n, uint32_t* flag, hipStream_t s);
+int launch_dd_uniqwrite(const uint64_t* cand, const uint32_t* at, uint64_t n, uint64_t* out, hipStream_t s);
+/* Verification: per candidate c = (a << 32 | b) shared[c] = the terms the two ascending lists
+ * have in common (lanes take terms of the shorter list and binary-search the longer one) and
+ * same[c] = the equal signature entries.  A wave per candidate; candidates with a document over
+ * DD_BIG_PAIRS pairs go to a second launch, a workgroup each.  The wave or workgroup owns its
+ * output words: no atomics on results. */
+struct DdVerArgs {
+    const uint64_t* cand;
+    uint64_t ncand;
+    const uint64_t* off;
+    uint64_t npairs;
+    uint32_t ndocs;
+    uint32_t H;
+    const uint32_t* term;
+    const uint32_t* sig;
+    uint32_t* shared;            /* ncand */
+    uint32_t* same;              /* ncand */
+    uint32_t* big_list;          /* [ncand] scratch (ncand < 2^32) */
+    uint32_t* big_count;         /* one word, zeroed by the launch */
+};
+int launch_dd_verify(const DdVerArgs& a, uint32_t ncu, hipStream_t s);
+
 #endif

@@ -68,6 +68,21 @@
  * One shard only: with --gpus or --shards above 1 the option is refused (the shards' term tables
  * differ, so they share no centroid matrix).
  *
+ * Near duplicates (MinHash signatures, LSH bands, exact Jaccard: tfidf_near_dups):
+ *   --near-dups T              after output.txt and the other files, and after the pruning and
+ *                              weighting options: the pairs of documents whose exact Jaccard over
+ *                              their resident terms is at least T (0..1; 0.8 is the usual choice).
+ *                              First one line per group of two or more,
+ *                              "g<i>\t<size>\tdoc<a> doc<b> ..", members in "docN@" order, groups by
+ *                              their first member; then one line per kept pair,
+ *                              "doc<A>\tdoc<B>\t<shared>\t<union>\t%.16f";
+ *   --near-dups-hashes H       hash functions, 1..TFIDF_MINHASH_MAX_H (default 128);
+ *   --near-dups-rows R         rows per band, a divisor of H (default 4);
+ *   --near-dups-seed S         the hash family's seed (default 1);
+ *   --near-dups-file FILE      the file (default dups.txt).
+ * With --ngrams the sets are shingle sets.  One shard only and not under --model (exit 2), like
+ * --clusters.
+ *
  * Transform (documents the run has not seen, scored with the run's vocabulary, df, N and idf,
  * tfidf_transform):
  *   --transform DIR        after output.txt (and the other files), DIR/doc1..docM are read under
@@ -515,6 +530,58 @@ static int run_clusters(tfidf_ctx* ctx) {
     return rc;
 }
 
+/* -------------------------------------------------------- near duplicates -- */
+
+static struct {
+    int on;             /* 0: no pass, behaviour and bytes as without the option */
+    double threshold;
+    uint32_t hashes, rows;
+    uint64_t seed;
+    const char* file;
+} g_dups = {0, 0.8, TFIDF_DEDUP_DEFAULT_H, TFIDF_DEDUP_DEFAULT_ROWS, TFIDF_DEDUP_DEFAULT_SEED, "dups.txt"};
+
+/* --near-dups: near-duplicate pairs and groups of the documents of ctx */
+static int run_dups(tfidf_ctx* ctx) {
+    if (!g_dups.on) return TFIDF_OK;
+    tfidf_dedup_params p;
+    memset(&p, 0, sizeof(p));
+    p.size = sizeof(p);
+    p.nhashes = g_dups.hashes;
+    p.rows = g_dups.rows;
+    p.seed = g_dups.seed;
+    p.threshold = g_dups.threshold;
+    tfidf_dups d;
+    memset(&d, 0, sizeof(d));
+    int rc = tfidf_near_dups(ctx, &p, &d);
+    if (rc == TFIDF_E_CAPACITY)
+        fprintf(stderr, "tfidf: --near-dups: the signatures and candidates exceed TFIDF_DEDUP_MB\n");
+    if (rc) return rc;
+    FILE* f = fopen(g_dups.file, "w");
+    if (!f) printf("Error Opening File: %s\n", g_dups.file);
+    /* the members of a group follow its first member in position order: count, then print */
+    uint32_t* size = (uint32_t*)calloc((size_t)d.ndocs + 1, sizeof(uint32_t));
+    if (!size) { if (f) fclose(f); tfidf_dups_free(&d); return TFIDF_E_NOMEM; }
+    for (uint32_t j = 0; j < d.ndocs; ++j) ++size[d.group[j]];
+    uint32_t g = 0;
+    for (uint32_t j = 0; f && j < d.ndocs; ++j) {
+        if (d.group[j] != j || size[j] < 2) continue;
+        fprintf(f, "g%u\t%u\t", g++, size[j]);
+        int first = 1;
+        for (uint32_t m = j; m < d.ndocs; ++m) {
+            if (d.group[m] != j) continue;
+            fprintf(f, first ? "doc%u" : " doc%u", d.doc[m]);
+            first = 0;
+        }
+        fputc('\n', f);
+    }
+    free(size);
+    for (uint64_t e = 0; f && e < d.nedges; ++e)
+        fprintf(f, "doc%u\tdoc%u\t%u\t%u\t%.16f\n", d.a_doc[e], d.b_doc[e], d.shared[e], d.uni[e], d.jaccard[e]);
+    if (f && fclose(f) != 0) rc = TFIDF_E_OUTPUT;
+    tfidf_dups_free(&d);
+    return rc;
+}
+
 /* -------------------------------------------------------------- transform -- */
 
 static struct {
@@ -728,6 +795,7 @@ static int run_single(int device, const char* indir, const char* outpath, int de
     if (!rc) rc = run_keywords(ctx, NULL);
     if (!rc) rc = run_similar(ctx, NULL);
     if (!rc) rc = run_clusters(ctx);
+    if (!rc) rc = run_dups(ctx);
     if (!rc) rc = run_transform(ctx, NULL);
     if (!rc) rc = save_model(ctx, NULL);
     tfidf_close(ctx);
@@ -858,6 +926,7 @@ static int usage(void) {
                     "[--keywords K [--keywords-file FILE]] "
                     "[--similar K [--similar-docs FILE] [--similar-file FILE]] "
                     "[--clusters K [--clusters-iter I] [--clusters-seeds FILE] [--clusters-terms T] [--clusters-file FILE]] "
+                    "[--near-dups T [--near-dups-hashes H] [--near-dups-rows R] [--near-dups-seed S] [--near-dups-file FILE]] "
                     "[--transform DIR [--transform-file FILE]] [--save-model FILE] "
                     "[--min-df X] [--max-df X] [--max-features M] "
                     "[--tf ratio|raw|log|binary] [--sublinear-tf] [--idf ref|smooth|plus1|none] [--norm none|l1|l2] "
@@ -950,6 +1019,31 @@ int main(int argc, char** argv) {
         else if (!strcmp(argv[i], "--transform") && i + 1 < argc) g_transform.dir = argv[++i];
         else if (!strcmp(argv[i], "--save-model") && i + 1 < argc) g_model.save = argv[++i];
         else if (!strcmp(argv[i], "--model") && i + 1 < argc) g_model.load = argv[++i];
+        else if (!strcmp(argv[i], "--near-dups-file") && i + 1 < argc) g_dups.file = argv[++i];
+        else if (!strcmp(argv[i], "--near-dups-hashes") && i + 1 < argc) {
+            char* end = NULL;
+            const long v = strtol(argv[++i], &end, 10);
+            if (!end || *end || v < 1 || v > (long)TFIDF_MINHASH_MAX_H) { fprintf(stderr, "tfidf: --near-dups-hashes takes 1..%u\n", TFIDF_MINHASH_MAX_H); return 2; }
+            g_dups.hashes = (uint32_t)v;
+        }
+        else if (!strcmp(argv[i], "--near-dups-rows") && i + 1 < argc) {
+            char* end = NULL;
+            const long v = strtol(argv[++i], &end, 10);
+            if (!end || *end || v < 1 || v > (long)TFIDF_MINHASH_MAX_H) { fprintf(stderr, "tfidf: --near-dups-rows takes 1..%u\n", TFIDF_MINHASH_MAX_H); return 2; }
+            g_dups.rows = (uint32_t)v;
+        }
+        else if (!strcmp(argv[i], "--near-dups-seed") && i + 1 < argc) {
+            char* end = NULL;
+            g_dups.seed = strtoull(argv[++i], &end, 0);
+            if (!end || *end) { fprintf(stderr, "tfidf: --near-dups-seed takes an unsigned integer\n"); return 2; }
+        }
+        else if (!strcmp(argv[i], "--near-dups") && i + 1 < argc) {
+            char* end = NULL;
+            const double v = strtod(argv[++i], &end);
+            if (!end || *end || end == argv[i] || !(v >= 0.0 && v <= 1.0)) { fprintf(stderr, "tfidf: --near-dups takes a threshold in 0..1\n"); return 2; }
+            g_dups.threshold = v;
+            g_dups.on = 1;
+        }
         else if (!strcmp(argv[i], "--clusters-seeds") && i + 1 < argc) g_clusters.seeds = argv[++i];
         else if (!strcmp(argv[i], "--clusters-file") && i + 1 < argc) g_clusters.file = argv[++i];
         else if (!strcmp(argv[i], "--clusters-iter") && i + 1 < argc) {
@@ -1025,13 +1119,17 @@ int main(int argc, char** argv) {
             return 2;
         }
     }
+    if (g_dups.on && g_dups.hashes % g_dups.rows != 0u) {
+        fprintf(stderr, "tfidf: --near-dups-rows must divide --near-dups-hashes (%u)\n", g_dups.hashes);
+        return 2;
+    }
     if (g_model.load) {   /* a model holds no pairs: nothing to rank, list or print */
         if (!g_transform.dir) {
             fprintf(stderr, "tfidf: --model needs --transform DIR\n");
             return 2;
         }
-        if (g_query.file || g_keywords.k || g_similar.k || g_clusters.k || g_model.save || debug) {
-            fprintf(stderr, "tfidf: --model cannot be combined with --query, --keywords, --similar, --clusters, --save-model or "
+        if (g_query.file || g_keywords.k || g_similar.k || g_clusters.k || g_dups.on || g_model.save || debug) {
+            fprintf(stderr, "tfidf: --model cannot be combined with --query, --keywords, --similar, --clusters, --near-dups, --save-model or "
                             "--debug-jobs: they need a run's pairs\n");
             return 2;
         }
@@ -1057,6 +1155,11 @@ int main(int argc, char** argv) {
     if (g_clusters.k && nshards != 1) {
         fprintf(stderr, "tfidf: --clusters runs on one shard only: the shards' term tables differ, so they share no "
                         "centroid matrix (drop --gpus / --shards)\n");
+        return 2;
+    }
+    if (g_dups.on && nshards != 1) {
+        fprintf(stderr, "tfidf: --near-dups runs on one shard only: a document's candidates are sought among the shard's "
+                        "own documents (drop --gpus / --shards)\n");
         return 2;
     }
     if (g_prune.max_features && nshards != 1) {

@@ -52,6 +52,8 @@ EXPORTS = [
     "tfidf_prune_check", "tfidf_prune", "tfidf_group_prune", "tfidf_last_prune_info", "tfidf_model_prune",
     "tfidf_weighting_check", "tfidf_reweight", "tfidf_weighting_get", "tfidf_group_reweight",
     "tfidf_last_reweight_info", "tfidf_result_reweight",
+    "tfidf_dedup_check", "tfidf_minhash", "tfidf_signatures_free", "tfidf_near_dups", "tfidf_dups_free",
+    "tfidf_last_dedup_info", "tfidf_result_minhash", "tfidf_result_near_dups", "tfidf_dedup_groups",
 ]
 QUERY_MAX_K = 1024  # TFIDF_QUERY_MAX_K
 TERMS_MAX_K = 1024  # TFIDF_TERMS_MAX_K
@@ -83,6 +85,7 @@ NG_SLOT_BATCH = 1  # TFIDF_NG_SLOT_BATCH
 TF_MODES = {"ratio": 0, "raw": 1, "log": 2, "binary": 3}  # TFIDF_TF_*
 IDF_MODES = {"ref": 0, "smooth": 1, "plus1": 2, "none": 3}  # TFIDF_IDF_*
 NORM_MODES = {"none": 0, "l2": 1, "l1": 2}  # TFIDF_NORM_*
+MINHASH_MAX_H = 256  # TFIDF_MINHASH_MAX_H
 
 
 class Corpus(C.Structure):
@@ -317,6 +320,39 @@ class ReweightInfo(C.Structure):
     ]
 
 
+class DedupParams(C.Structure):
+    _fields_ = [
+        ("size", C.c_uint64), ("nhashes", C.c_uint32), ("rows", C.c_uint32), ("seed", C.c_uint64),
+        ("threshold", C.c_double),
+    ]
+
+
+class Signatures(C.Structure):
+    _fields_ = [
+        ("ndocs", C.c_uint32), ("nhashes", C.c_uint32), ("doc", C.POINTER(C.c_uint32)),
+        ("npairs", C.POINTER(C.c_uint32)), ("sig", C.POINTER(C.c_uint32)),
+    ]
+
+
+class Dups(C.Structure):
+    _fields_ = [
+        ("ndocs", C.c_uint32), ("ngroups", C.c_uint32), ("ncand", C.c_uint64), ("nedges", C.c_uint64),
+        ("doc", C.POINTER(C.c_uint32)), ("group", C.POINTER(C.c_uint32)),
+        ("a_pos", C.POINTER(C.c_uint32)), ("b_pos", C.POINTER(C.c_uint32)), ("a_doc", C.POINTER(C.c_uint32)),
+        ("b_doc", C.POINTER(C.c_uint32)), ("shared", C.POINTER(C.c_uint32)), ("uni", C.POINTER(C.c_uint32)),
+        ("same", C.POINTER(C.c_uint32)), ("jaccard", C.POINTER(C.c_double)),
+    ]
+
+
+class DedupInfo(C.Structure):
+    _fields_ = [
+        ("size", C.c_uint64), ("ndocs", C.c_uint32), ("nhashes", C.c_uint32), ("rows", C.c_uint32),
+        ("clusterable", C.c_uint32), ("ncand", C.c_uint64), ("nedges", C.c_uint64), ("ngroups", C.c_uint32),
+        ("big_docs", C.c_uint32), ("sig_bytes", C.c_uint64), ("work_bytes", C.c_uint64), ("ms_hash", C.c_double),
+        ("ms_sig", C.c_double), ("ms_bands", C.c_double), ("ms_verify", C.c_double), ("ms_total", C.c_double),
+    ]
+
+
 class DirPlan(C.Structure):
     _fields_ = [
         ("ndocs", C.c_uint32), ("nshards", C.c_uint32), ("doc_ids", C.POINTER(C.c_uint32)),
@@ -442,6 +478,18 @@ def lib() -> C.CDLL:
         L.tfidf_group_reweight.argtypes = [C.c_void_p, C.POINTER(Weighting)]
         L.tfidf_last_reweight_info.argtypes = [C.c_void_p, C.POINTER(ReweightInfo)]
         L.tfidf_result_reweight.argtypes = [C.POINTER(Result), C.POINTER(Weighting)]
+        L.tfidf_dedup_check.argtypes = [C.POINTER(DedupParams)]
+        L.tfidf_minhash.argtypes = [C.c_void_p, C.POINTER(DedupParams), C.POINTER(Signatures)]
+        L.tfidf_signatures_free.argtypes = [C.POINTER(Signatures)]
+        L.tfidf_signatures_free.restype = None
+        L.tfidf_near_dups.argtypes = [C.c_void_p, C.POINTER(DedupParams), C.POINTER(Dups)]
+        L.tfidf_dups_free.argtypes = [C.POINTER(Dups)]
+        L.tfidf_dups_free.restype = None
+        L.tfidf_last_dedup_info.argtypes = [C.c_void_p, C.POINTER(DedupInfo)]
+        L.tfidf_result_minhash.argtypes = [C.POINTER(Result), C.POINTER(DedupParams), C.POINTER(Signatures)]
+        L.tfidf_result_near_dups.argtypes = [C.POINTER(Result), C.POINTER(DedupParams), C.POINTER(Dups)]
+        L.tfidf_dedup_groups.argtypes = [C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p,
+                                         C.POINTER(C.c_uint32)]
         if L.tfidf_abi_version() != ABI_VERSION:
             raise RuntimeError(f"{LIB_PATH}: ABI version {L.tfidf_abi_version()}, binding expects {ABI_VERSION} "
                                f"(stale build: rebuild with __graft_entry__.build())")
@@ -816,6 +864,93 @@ def result_reweight(res: dict, tf="ratio", idf="ref", norm="none", N: int = 0, p
     out["score"] = score
     out["output_txt"] = format_lines(out)
     return out
+
+
+def dedup_params(nhashes: int = 0, rows: int = 0, seed: int = 0, threshold: float = 0.8) -> DedupParams:
+    """tfidf_dedup_params; nhashes = 0 selects the defaults H = 128, r = 4, seed = 1"""
+    p = DedupParams()
+    p.size = C.sizeof(DedupParams)
+    p.nhashes, p.rows, p.seed, p.threshold = nhashes, rows, seed, threshold
+    return p
+
+
+def dedup_check(p: DedupParams) -> int:
+    """tfidf_dedup_check (host only): 0, or E_INVAL; None stands for a NULL pointer."""
+    return int(lib().tfidf_dedup_check(None if p is None else C.byref(p)))
+
+
+def _u32s(p, n: int) -> np.ndarray:
+    return np.ctypeslib.as_array(p, shape=(n,)).astype(np.uint32, copy=True) if n else np.zeros(0, dtype=np.uint32)
+
+
+def _signatures_dict(s: Signatures) -> dict:
+    N, H = int(s.ndocs), int(s.nhashes)
+    return {"ndocs": N, "nhashes": H, "doc": _u32s(s.doc, N), "npairs": _u32s(s.npairs, N),
+            "sig": _u32s(s.sig, N * H).reshape(N, H)}
+
+
+def _dups_dict(d: Dups) -> dict:
+    N, E = int(d.ndocs), int(d.nedges)
+    out = {"ndocs": N, "ngroups": int(d.ngroups), "ncand": int(d.ncand), "nedges": E, "doc": _u32s(d.doc, N),
+           "group": _u32s(d.group, N)}
+    for k in ("a_pos", "b_pos", "a_doc", "b_doc", "shared", "uni", "same"):
+        out[k] = _u32s(getattr(d, k), E)
+    out["jaccard"] = (np.ctypeslib.as_array(d.jaccard, shape=(E,)).astype(np.float64, copy=True) if E
+                      else np.zeros(0, dtype=np.float64))
+    return out
+
+
+def _dedup_result(res: dict, doc_ids):
+    """a tfidf_result for the host dedup calls from a result dict whose terms may be numbered in
+    any order (the oracle numbers them by first appearance): the term table in strcmp("word\t")
+    order, pair_term renumbered.  doc_ids: every document of the shard (res["doc_id"] when absent).
+    Returns (Result, the arrays that must outlive it)."""
+    words = res["terms"]
+    by_rank = sorted(range(len(words)), key=lambda i: words[i] + b"\t")
+    rank = np.zeros(len(words) + 1, dtype=np.uint32)
+    rank[np.array(by_rank, dtype=np.int64)] = np.arange(len(words), dtype=np.uint32)
+    P = int(res["npairs"])
+    doc = np.ascontiguousarray(res["doc"], dtype=np.uint32).copy()
+    term = np.ascontiguousarray(rank[np.asarray(res["term"], dtype=np.int64)], dtype=np.uint32)
+    ids = np.ascontiguousarray(res["doc_id"] if doc_ids is None else doc_ids, dtype=np.uint32).copy()
+    toff = np.zeros(len(words) + 1, dtype=np.uint64)
+    toff[1:] = np.cumsum([len(words[i]) for i in by_rank], dtype=np.uint64)
+    tb = np.frombuffer(b"".join(words[i] for i in by_rank) + b"\0", dtype=np.uint8).copy()
+    r = Result()
+    r.npairs, r.ndocs, r.nterms = P, len(ids), len(words)
+    u32 = C.POINTER(C.c_uint32)
+    if P:
+        r.pair_doc, r.pair_term = doc.ctypes.data_as(u32), term.ctypes.data_as(u32)
+    if len(ids):
+        r.doc_id = ids.ctypes.data_as(u32)
+    r.term_off = toff.ctypes.data_as(C.POINTER(C.c_uint64))
+    r.term_bytes = tb.ctypes.data_as(C.POINTER(C.c_uint8))
+    return r, (doc, term, ids, toff, tb)
+
+
+def result_minhash(res: dict, doc_ids=None, nhashes: int = 0, seed: int = 0, params: DedupParams = None) -> dict:
+    """tfidf_result_minhash (host only, plain C) on a result dict."""
+    p = params if params is not None else dedup_params(nhashes, 1 if nhashes else 0, seed, 0.0)
+    r, keep = _dedup_result(res, doc_ids)
+    s = Signatures()
+    _chk(lib().tfidf_result_minhash(C.byref(r), C.byref(p), C.byref(s)), "tfidf_result_minhash")
+    try:
+        return _signatures_dict(s)
+    finally:
+        lib().tfidf_signatures_free(C.byref(s))
+
+
+def result_near_dups(res: dict, doc_ids=None, nhashes: int = 0, rows: int = 0, seed: int = 0, threshold: float = 0.8,
+                     params: DedupParams = None) -> dict:
+    """tfidf_result_near_dups (host only, plain C) on a result dict."""
+    p = params if params is not None else dedup_params(nhashes, rows, seed, threshold)
+    r, keep = _dedup_result(res, doc_ids)
+    d = Dups()
+    _chk(lib().tfidf_result_near_dups(C.byref(r), C.byref(p), C.byref(d)), "tfidf_result_near_dups")
+    try:
+        return _dups_dict(d)
+    finally:
+        lib().tfidf_dups_free(C.byref(d))
 
 
 def synth_host(seed: int, V: int, mode: int, cdf, doc_ids, ntok):
@@ -1208,6 +1343,35 @@ class Engine:
         t.size = C.sizeof(ReweightInfo)
         _chk(lib().tfidf_last_reweight_info(self.h, C.byref(t)), "tfidf_last_reweight_info")
         return {k: getattr(t, k) for k, _ in ReweightInfo._fields_ if k not in ("size", "reserved")}
+
+    def minhash(self, nhashes: int = 0, seed: int = 0, params: DedupParams = None) -> dict:
+        """MinHash signatures of the resident documents in output order (tfidf_minhash)."""
+        p = params if params is not None else dedup_params(nhashes, 1 if nhashes else 0, seed, 0.0)
+        s = Signatures()
+        _chk(lib().tfidf_minhash(self.h, C.byref(p), C.byref(s)), "tfidf_minhash")
+        try:
+            return _signatures_dict(s)
+        finally:
+            lib().tfidf_signatures_free(C.byref(s))
+
+    def near_dups(self, threshold: float = 0.8, nhashes: int = 0, rows: int = 0, seed: int = 0,
+                  params: DedupParams = None) -> dict:
+        """Near-duplicate pairs and groups of the resident documents (tfidf_near_dups): LSH
+        candidates, every one verified by its exact Jaccard."""
+        p = params if params is not None else dedup_params(nhashes, rows, seed, threshold)
+        d = Dups()
+        _chk(lib().tfidf_near_dups(self.h, C.byref(p), C.byref(d)), "tfidf_near_dups")
+        try:
+            return _dups_dict(d)
+        finally:
+            lib().tfidf_dups_free(C.byref(d))
+
+    def dedup_info(self) -> dict:
+        """Counters and device times of the last minhash or near_dups (tfidf_last_dedup_info)."""
+        t = DedupInfo()
+        t.size = C.sizeof(DedupInfo)
+        _chk(lib().tfidf_last_dedup_info(self.h, C.byref(t)), "tfidf_last_dedup_info")
+        return {k: getattr(t, k) for k, _ in DedupInfo._fields_ if k != "size"}
 
     @contextlib.contextmanager
     def fetched(self):
