@@ -224,6 +224,14 @@ typedef struct tfidf_run_totals {
 int tfidf_run_totals_get(tfidf_ctx* ctx, tfidf_run_totals* out, int reset);
 /* The same device-allocation counters without a run (process-wide, cumulative). */
 int tfidf_alloc_stats(uint64_t* allocs, uint64_t* bytes);
+/* The CU count the context sizes its launches over the resident result by (tfidf_query,
+ * _query_bm25, _top_terms, _similar, _kmeans, _prune, _reweight, _transform's row norm, _minhash,
+ * _near_dups; tfidf_analyze's tile kernel too): each takes min(work, CUs x a per-kernel constant)
+ * workgroups that stride over the work.  The device's count, or env TFIDF_GRID_CUS (1..4096,
+ * read at tfidf_open; anything else: the device's), which exists so that tests reach the second
+ * and later trips of those loops on a small corpus.  No result depends on it.  The run's own
+ * kernels ask the device and ignore it.  TFIDF_E_INVAL: a NULL argument. */
+int tfidf_grid_cus(tfidf_ctx* ctx, uint32_t* ncu);
 const char* tfidf_stage_name(int stage);
 /* HIP event timing of a run's stages (tfidf_run_info.ms_stage / ms_tokcount / ms_total):
  * enable 0 none, 1 every stage (the default; ten event records per run), 2 the tokenize+count

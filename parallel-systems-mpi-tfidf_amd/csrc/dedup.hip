@@ -144,13 +144,10 @@ __global__ __launch_bounds__(NT) void k_dd_sig_big(const DdSigArgs a) {
 
 template <int HPL>
 int sig_launch(const DdSigArgs& a, uint32_t ncu, hipStream_t s) {
-    const uint32_t cu = ncu ? ncu : 256u;
     const uint32_t need = (a.ndocs + NT / 64 - 1) / (NT / 64);
-    const uint32_t cap = cu * 8u;
-    k_dd_sig<HPL><<<need < cap ? need : cap, NT, 0, s>>>(a);
+    k_dd_sig<HPL><<<cu_grid(need, ncu, DD_WG_PER_CU), NT, 0, s>>>(a);
     if (ok()) return -1;
-    const uint32_t capb = cu * 4u;
-    k_dd_sig_big<HPL><<<a.ndocs < capb ? a.ndocs : capb, NT, 0, s>>>(a);
+    k_dd_sig_big<HPL><<<cu_grid(a.ndocs, ncu, DD_BIG_WG_PER_CU), NT, 0, s>>>(a);
     return ok();
 }
 
@@ -336,12 +333,9 @@ int launch_dd_verify(const DdVerArgs& a, uint32_t ncu, hipStream_t s) {
     if (!a.ncand) return 0;
     if (a.ncand > 0xFFFFFFFFull) return -1;
     if (hipMemsetAsync(a.big_count, 0, 4, s) != hipSuccess) return -1;
-    const uint32_t cu = ncu ? ncu : 256u;
     const uint64_t need = (a.ncand + NT / 64 - 1) / (NT / 64);
-    const uint64_t cap = (uint64_t)cu * 8u;
-    k_dd_verify<<<(unsigned)(need < cap ? need : cap), NT, 0, s>>>(a);
+    k_dd_verify<<<cu_grid(need, ncu, DD_WG_PER_CU), NT, 0, s>>>(a);
     if (ok()) return -1;
-    const uint64_t capb = (uint64_t)cu * 4u;
-    k_dd_verify_big<<<(unsigned)(a.ncand < capb ? a.ncand : capb), NT, 0, s>>>(a);
+    k_dd_verify_big<<<cu_grid(a.ncand, ncu, DD_BIG_WG_PER_CU), NT, 0, s>>>(a);
     return ok();
 }

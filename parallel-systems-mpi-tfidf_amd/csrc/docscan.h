@@ -228,11 +228,10 @@ int launch_score(const typename P::Args& a, uint32_t ncu, hipStream_t s) {
     if (!a.ndocs || !a.nq || a.nq > QG_MAX) return a.nq > QG_MAX ? -1 : 0;
     if (hipMemsetAsync(a.big_count, 0, 4, s) != hipSuccess) return -1;
     /* every workgroup builds the filter once: no more of them than stay resident */
-    const uint32_t cap = (ncu ? ncu : 256u) * 3u;   /* ~52 KiB of LDS each: three per CU */
     const uint32_t want = (a.ndocs + (NT / 64) - 1) / (NT / 64);
-    k_doc_score<P><<<want < cap ? want : cap, NT, 0, s>>>(a);
+    k_doc_score<P><<<cu_grid(want, ncu, QS_WG_PER_CU), NT, 0, s>>>(a);   /* ~52 KiB of LDS each: three per CU */
     if (ok()) return -1;
-    k_doc_score_big<P><<<want < 256u ? want : 256u, NT, 0, s>>>(a);
+    k_doc_score_big<P><<<big_grid(want, ncu), NT, 0, s>>>(a);
     return ok();
 }
 

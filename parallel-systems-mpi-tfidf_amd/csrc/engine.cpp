@@ -208,6 +208,11 @@ int tfidf_open(int device, tfidf_ctx** out) {
         const unsigned long ag = strtoul(kag, nullptr, 0);
         if (ag >= 1 && ag <= 65536) ctx->an_grid = (uint32_t)ag;
     }
+    const char* kgc = getenv("TFIDF_GRID_CUS");
+    if (kgc) {
+        const unsigned long gc = strtoul(kgc, nullptr, 0);
+        if (gc >= 1 && gc <= 4096) ctx->grid_cus = (uint32_t)gc;
+    }
     const char* kn = getenv("TFIDF_TEST_XNOMEM_RANK");
     ctx->xnomem_rank = kn ? atoi(kn) : -1;
     /* diagnostics: initial vocabulary capacity (power of two) and the loads it may reach
@@ -1679,6 +1684,12 @@ extern "C" int tfidf_hbm_probe(tfidf_ctx* ctx, uint64_t nbytes, int iters, doubl
     (void)hipFree(b);
     (void)hipFree(sink);
     return rc;
+}
+
+extern "C" int tfidf_grid_cus(tfidf_ctx* ctx, uint32_t* ncu) {
+    if (!ctx || !ncu) return TFIDF_E_INVAL;
+    *ncu = ctx_ncu(ctx);
+    return TFIDF_OK;
 }
 
 extern "C" int tfidf_alloc_stats(uint64_t* allocs, uint64_t* bytes) {

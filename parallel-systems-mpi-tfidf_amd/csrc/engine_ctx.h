@@ -248,6 +248,7 @@ struct tfidf_ctx {
     uint64_t kmeans_bytes = 1024ull << 20;      /* env TFIDF_KMEANS_MB: budget of km_C + km_work */
     uint32_t kmeans_split = 0;                  /* env TFIDF_KMEANS_SPLIT: update workgroups per cluster (0: fill the GPU) */
     uint32_t an_grid = 0;                       /* env TFIDF_AN_GRID: at most that many workgroups of the analyzer's tile kernel (0: the resident ones) */
+    uint32_t grid_cus = 0;                      /* env TFIDF_GRID_CUS: the CU count `ncu` takes in place of the device's (0: the device's) */
     hipEvent_t ev_k[4] = {};                    /* assign / update / top-term bounds (created by the first call) */
     tfidf_kmeans_info kinfo{};
     /* unseen documents against the resident model (tfidf_transform, transform.hip): a host
@@ -417,16 +418,24 @@ static inline size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 /* ---- what every add-on call starts and ends with ---- */
 
+/* the CU count the launches over the result are sized by (kernels.h, *_WG_PER_CU): env
+ * TFIDF_GRID_CUS when it was set at tfidf_open, else the device's; settled once per context */
+static inline uint32_t ctx_ncu(tfidf_ctx* ctx) {
+    if (!ctx->ncu) {
+        int n = 0;
+        if (ctx->grid_cus) n = (int)ctx->grid_cus;
+        else if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, ctx->device) != hipSuccess || n <= 0) n = 256;
+        ctx->ncu = (uint32_t)n;
+    }
+    return ctx->ncu;
+}
+
 /* the context's device, the call's events (created by the first call) and the CU count */
 template <size_t NEV> static inline int call_begin(tfidf_ctx* ctx, hipEvent_t (&ev)[NEV]) {
     HIPCHK(hipSetDevice(ctx->device));
     for (hipEvent_t& e : ev)
         if (!e) HIPCHK(hipEventCreate(&e));
-    if (!ctx->ncu) {
-        int n = 0;
-        if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, ctx->device) != hipSuccess || n <= 0) n = 256;
-        ctx->ncu = (uint32_t)n;
-    }
+    ctx_ncu(ctx);
     return TFIDF_OK;
 }
 static inline double wall_ms(std::chrono::steady_clock::time_point t0) {

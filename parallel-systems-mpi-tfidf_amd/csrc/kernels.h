@@ -354,6 +354,26 @@ int launch_emit_write(const EmitLaunch& e, const uint64_t* doc_text, uint8_t* te
                       uint32_t d1 = 0xFFFFFFFFu);
 int launch_format_f64(const double* v, uint64_t n, uint8_t* out, uint32_t* status, hipStream_t s);
 
+/* ---- grids of the launches over the resident result ----
+ * Each is min(work, ncu * its multiplier) workgroups that stride over the work; ncu is the
+ * context's CU count (call_begin: the device's, or env TFIDF_GRID_CUS).  The launches that take
+ * one workgroup per big document (over QS_BIG / RW_BIG pairs) are bounded by BIG_WG_MAX as well:
+ * from BIG_WG_MAX / BIG_WG_PER_CU = 64 CUs on that bound alone holds.  tests/stride_corpus.py reads
+ * these to size a corpus on which every such loop makes several trips. */
+#define QS_WG_PER_CU       3u  /* k_doc_score (query, BM25): ~52 KiB of LDS each */
+#define SM_WG_PER_CU       8u  /* k_sim_score: no LDS, the waves a CU holds */
+#define KM_WG_PER_CU       8u  /* k_km_assign: as k_sim_score */
+#define RW_WG_PER_CU       8u  /* k_rw_docs */
+#define DD_WG_PER_CU       8u  /* k_dd_sig, k_dd_verify */
+#define DD_BIG_WG_PER_CU   4u  /* k_dd_sig_big, k_dd_verify_big */
+#define TM_LIST_WG_PER_CU  32u /* k_terms_select_list: one wave, the list in registers */
+#define TM_W512_WG_PER_CU  24u /* k_terms_select<64, 512>: 6 KiB of LDS per one-wave workgroup */
+#define TM_W2048_WG_PER_CU 6u  /* k_terms_select<64, 2048>: 24 KiB */
+#define TM_BIG_WG_PER_CU   3u  /* k_terms_select<256, 4096, BIG> */
+#define PR_WG_PER_CU       4u  /* k_pr_pairs (count and write) */
+#define BIG_WG_MAX         256u /* k_doc_score_big, k_sim_score_big, k_rw_docs_big: at most this many ... */
+#define BIG_WG_PER_CU      4u  /* ... and this many per CU */
+
 /* ---- top-k retrieval over the resident result (query.hip, tfidf_query) ---- */
 #define QG_MAX        64u      /* queries per scoring pass: one accumulator per lane of the owner wave */
 #define QS_BIG        4096u    /* documents over this many pairs: a workgroup each (K5_MAX_PAIRS's cut) */

@@ -351,9 +351,8 @@ int launch_km_assign(const KmArgs& a, uint32_t ncu, hipStream_t s) {
     if (hipMemsetAsync(a.changed, 0, 4, s) != hipSuccess) return -1;
     if (hipMemsetAsync(a.size, 0, (size_t)a.K * 4, s) != hipSuccess) return -1;
     if (!a.ndocs) return 0;
-    const uint32_t cap = (ncu ? ncu : 256u) * 8u;   /* no LDS: the waves a CU holds */
     const uint32_t want = (a.ndocs + (NT / 64) - 1) / (NT / 64);
-    const uint32_t grid = want < cap ? want : cap;
+    const uint32_t grid = cu_grid(want, ncu, KM_WG_PER_CU);   /* no LDS: the waves a CU holds */
     switch ((a.K + 63u) / 64u) {
         case 1: k_km_assign<1><<<grid, NT, 0, s>>>(a); break;
         case 2: k_km_assign<2><<<grid, NT, 0, s>>>(a); break;

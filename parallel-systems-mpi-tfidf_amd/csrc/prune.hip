@@ -218,7 +218,7 @@ __global__ __launch_bounds__(NT) void k_pr_emptied(const PrPairs a) {
 }
 
 unsigned pairs_grid(const PrPairs& a, uint32_t ncu) {
-    const uint64_t cap = (uint64_t)(ncu ? ncu : 256u) * 4u;
+    const uint64_t cap = (uint64_t)(ncu ? ncu : 256u) * PR_WG_PER_CU;
     return (unsigned)(a.ntiles < cap ? a.ntiles : cap);
 }
 

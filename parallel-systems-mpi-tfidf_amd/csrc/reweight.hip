@@ -245,11 +245,10 @@ __global__ __launch_bounds__(NT) void k_rw_docs_big(const RwArgs a) {
 
 template <int NORM>
 int rw_launch(const RwArgs& a, uint32_t ncu, hipStream_t s) {
-    const uint32_t cap = (ncu ? ncu : 256u) * 8u;
     const uint32_t want = (a.ndocs + (NT / 64) - 1) / (NT / 64);
-    k_rw_docs<NORM><<<want < cap ? want : cap, NT, 0, s>>>(a);
+    k_rw_docs<NORM><<<cu_grid(want, ncu, RW_WG_PER_CU), NT, 0, s>>>(a);
     if (ok()) return -1;
-    k_rw_docs_big<NORM><<<want < 256u ? want : 256u, NT, 0, s>>>(a);
+    k_rw_docs_big<NORM><<<big_grid(want, ncu), NT, 0, s>>>(a);
     return ok();
 }
 

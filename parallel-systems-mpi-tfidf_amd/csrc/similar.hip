@@ -341,11 +341,10 @@ int launch_sim_fill(const SimTabArgs& a, hipStream_t s) {
 int launch_sim_score(const SimScoreArgs& a, uint32_t ncu, hipStream_t s) {
     if (!a.ndocs || !a.nq || a.nq > SG_MAX) return a.nq > SG_MAX ? -1 : 0;
     if (hipMemsetAsync(a.big_count, 0, 4, s) != hipSuccess) return -1;
-    const uint32_t cap = (ncu ? ncu : 256u) * 8u;   /* no LDS: the waves a CU holds */
     const uint32_t want = (a.ndocs + (NT / 64) - 1) / (NT / 64);
-    k_sim_score<<<want < cap ? want : cap, NT, 0, s>>>(a);
+    k_sim_score<<<cu_grid(want, ncu, SM_WG_PER_CU), NT, 0, s>>>(a);   /* no LDS: the waves a CU holds */
     if (ok()) return -1;
-    k_sim_score_big<<<want < 256u ? want : 256u, NT, 0, s>>>(a);
+    k_sim_score_big<<<big_grid(want, ncu), NT, 0, s>>>(a);
     return ok();
 }
 

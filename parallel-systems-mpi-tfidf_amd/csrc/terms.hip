@@ -333,8 +333,7 @@ __global__ void k_terms_words(const TWordArgs a) {
 
 template <int TNT, uint32_t CAP, bool BIG>
 int select_launch(const TSelArgs& a, uint32_t per_cu, uint32_t ncu, hipStream_t s) {
-    const uint32_t cap = (ncu ? ncu : 256u) * per_cu;
-    k_terms_select<TNT, CAP, BIG><<<a.nrows < cap ? a.nrows : cap, TNT, 0, s>>>(a);
+    k_terms_select<TNT, CAP, BIG><<<cu_grid(a.nrows, ncu, per_cu), TNT, 0, s>>>(a);
     return ok();
 }
 
@@ -353,13 +352,12 @@ int launch_terms_select(const TSelArgs& a, uint32_t ncu, hipStream_t s) {
     /* by k: the register list, or the wave kernel with 6 or 24 KiB of LDS per one-wave workgroup */
     int rc;
     if (a.k <= 64u) {
-        const uint32_t cap = (ncu ? ncu : 256u) * 32u;
-        k_terms_select_list<<<a.nrows < cap ? a.nrows : cap, 64, 0, s>>>(a);
+        k_terms_select_list<<<cu_grid(a.nrows, ncu, TM_LIST_WG_PER_CU), 64, 0, s>>>(a);
         rc = ok();
-    } else if (a.k <= 256u) rc = select_launch<64, 512u, false>(a, 24u, ncu, s);
-    else rc = select_launch<64, 2048u, false>(a, 6u, ncu, s);
+    } else if (a.k <= 256u) rc = select_launch<64, 512u, false>(a, TM_W512_WG_PER_CU, ncu, s);
+    else rc = select_launch<64, 2048u, false>(a, TM_W2048_WG_PER_CU, ncu, s);
     if (rc) return rc;
-    return select_launch<256, 4096u, true>(a, 3u, ncu, s);
+    return select_launch<256, 4096u, true>(a, TM_BIG_WG_PER_CU, ncu, s);
 }
 
 int launch_terms_words(const TWordArgs& a, hipStream_t s) {

@@ -31,6 +31,7 @@ ABI_VERSION = 2  # TFIDF_ABI_VERSION of include/tfidf.h this binding is written 
 EXPORTS = [
     "tfidf_open", "tfidf_close", "tfidf_strerror", "tfidf_abi_version", "tfidf_comm_unique_id",
     "tfidf_comm_init", "tfidf_run", "tfidf_fetch", "tfidf_result_free", "tfidf_last_run_info", "tfidf_alloc_stats",
+    "tfidf_grid_cus",
     "tfidf_stage_name", "tfidf_set_timing", "tfidf_write_output", "tfidf_print_jobs",
     "tfidf_ingest_dir", "tfidf_free", "tfidf_synth_host", "tfidf_synth_device",
     "tfidf_format", "tfidf_copy_text", "tfidf_write_output_gpu", "tfidf_format_f64",
@@ -388,6 +389,7 @@ def lib() -> C.CDLL:
         L.tfidf_last_run_info.argtypes = [C.c_void_p, C.POINTER(RunInfo)]
         L.tfidf_run_totals_get.argtypes = [C.c_void_p, C.POINTER(RunTotals), C.c_int]
         L.tfidf_alloc_stats.argtypes = [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        L.tfidf_grid_cus.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
         L.tfidf_stage_name.restype = C.c_char_p
         L.tfidf_set_timing.argtypes = [C.c_void_p, C.c_int]
         L.tfidf_comm_unique_id.argtypes = [C.c_void_p]
@@ -1061,6 +1063,13 @@ class Engine:
         a, b = C.c_uint64(), C.c_uint64()
         _chk(lib().tfidf_alloc_stats(C.byref(a), C.byref(b)), "tfidf_alloc_stats")
         return int(a.value), int(b.value)
+
+    def grid_cus(self) -> int:
+        """the CU count this context sizes its launches over the result by: the device's, or env
+        TFIDF_GRID_CUS as tfidf_open read it."""
+        n = C.c_uint32()
+        _chk(lib().tfidf_grid_cus(self.h, C.byref(n)), "tfidf_grid_cus")
+        return int(n.value)
 
     def totals(self, reset: bool = False) -> dict:
         """sums over the successful runs since the last reset (tfidf_run_totals_get)"""

@@ -23,7 +23,7 @@ from helpers import device_corpus, docs_to_arrays, load_golden
 
 pytestmark = pytest.mark.gpu
 
-SHAPES = [(1, 1), (64, 1), (128, 4), (256, 8), (96, 96)]
+SHAPES = [(1, 1), (64, 1), (128, 4), (256, 8), (96, 96), (192, 3), (129, 1), (160, 5)]   # one to four hashes per lane
 THRESHOLDS = [0.0, 0.5, 1.0]
 
 
@@ -122,6 +122,8 @@ def test_both_sides_of_the_big_threshold(engine):
         want = check(engine, ref, 128, 4, 1, 0.5)
         assert engine.dedup_info()["big_docs"] == nbig, n
         check(engine, ref, 256, 256, 9, 0.0)
+        assert engine.dedup_info()["big_docs"] == nbig, n
+        check(engine, ref, 160, 5, 3, 0.5)                                  # three hashes per lane: k_dd_sig<3> / k_dd_sig_big<3>
         assert engine.dedup_info()["big_docs"] == nbig, n
         check_sig(engine, ref, 128, 1, want["sig"])
         assert engine.dedup_info()["big_docs"] == nbig, n

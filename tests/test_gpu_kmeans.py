@@ -170,7 +170,7 @@ def test_pair_count_boundaries(engine):
     assert rc_of(engine.kmeans, 2, seeds=[where[0], where[1]]) == tfidf_abi.E_INVAL
 
 
-@pytest.mark.parametrize("k", [1, 2, 63, 64, 65, 128, 129, 256])
+@pytest.mark.parametrize("k", [1, 2, 63, 64, 65, 100, 128, 129, 130, 256])
 def test_k_boundaries(engine, topical, k):
     """lane ownership (K against the 64 lanes) and one to four accumulators per lane"""
     ref = topical["ref"]
