@@ -1446,6 +1446,158 @@ int tfidf_result_near_dups(const tfidf_result* r, const tfidf_dedup_params* para
 int tfidf_dedup_groups(uint32_t ndocs, const uint32_t* a_pos, const uint32_t* b_pos, uint64_t n, uint32_t* group,
                        uint32_t* ngroups);
 
+/* ---------------------------------------------------------------- classify -- */
+
+/* Naive Bayes text classification over the resident result: a fit on the documents the caller
+ * labels, then the label of resident documents or of the rows of a tfidf_transform.  Multinomial
+ * NB and the complement variant (Rennie et al. 2003).  The features are the pairs' counts, so the
+ * sums are integers, exact in any order; every logarithm is the host's libm.  All floating-point
+ * arithmetic is IEEE binary64, round to nearest; fl() marks every rounding; no product is fused
+ * into an add.  The reference has no such pass.
+ *
+ *   classes      0..K-1, 1 <= K <= TFIDF_NB_MAX_CLASSES.  The labelled documents are the
+ *                (global doc id, class) entries of the parameters; the context's other documents
+ *                are unlabelled and take no part in the fit
+ *   x(d,t)       the pair's wordCount (TFIDF_NB_COUNT) or 1 (TFIDF_NB_BINARY)
+ *   counts       u64, exact: FC[c][t] = the sum of x(d,t) over the documents labelled c;
+ *                T[c] = sum_t FC[c][t]; F[t] = sum_c FC[c][t]; Ttot = sum_c T[c];
+ *                n_c = the documents labelled c (empty ones included), n = sum_c n_c
+ *   smoothing    V = the context's current term count (after a tfidf_prune: the kept terms);
+ *                aV = fl(alpha * (double)V)
+ *   multinomial  W[c][t] = fl( log(fl((double)FC[c][t] + alpha)) - log(fl((double)T[c] + aV)) )
+ *                prior(c) = fl( log((double)n_c) - log((double)n) ), or +0.0 with uniform_prior
+ *   complement   W[c][t] = fl( log(fl((double)(Ttot - T[c]) + aV))
+ *                             - log(fl((double)(F[t] - FC[c][t]) + alpha)) );  prior(c) = +0.0
+ *   score(d,c)   ((prior(c) + fl((double)x1 * W[c][t1])) + fl((double)x2 * W[c][t2])) + ..
+ *                over d's pairs in pair order (term-table order); a document without pairs
+ *                scores prior(c)
+ *   label(d)     the c with the largest score(d,c) by value, the lowest c among equals.  Scores
+ *                are finite and of either sign
+ * Consequence: a fixed sequence of IEEE operations per (document, class); nothing depends on grid,
+ * launch shape or budget, and the device equals the plain-C twin below bit for bit.
+ *
+ * `size` is set by the caller to sizeof(tfidf_nb_params).  alpha == 0 selects the default 1.0;
+ * otherwise it must be finite, > 0 and <= TFIDF_NB_MAX_ALPHA, so that every log argument is
+ * positive and finite. */
+#define TFIDF_NB_MAX_CLASSES 256u    /* four accumulators per lane of the owner wave, as k-means */
+#define TFIDF_NB_MAX_ALPHA   0x1p+900
+#define TFIDF_NB_MULTINOMIAL 0u
+#define TFIDF_NB_COMPLEMENT  1u
+#define TFIDF_NB_COUNT       0u
+#define TFIDF_NB_BINARY      1u
+#define TFIDF_NB_ALL_SCORES  1u      /* predict flag: also every class's score per row */
+#define TFIDF_NO_CLASS       0xFFFFFFFFu
+typedef struct tfidf_nb_params {
+    uint64_t size;
+    uint32_t nclasses;        /* K */
+    uint32_t variant;         /* TFIDF_NB_MULTINOMIAL / TFIDF_NB_COMPLEMENT */
+    uint32_t feature;         /* TFIDF_NB_COUNT / TFIDF_NB_BINARY */
+    uint32_t uniform_prior;   /* non-zero: prior(c) = +0.0 (multinomial; the complement's always is) */
+    double   alpha;           /* 0: 1.0 */
+    uint64_t nlabelled;
+    const uint32_t* doc;      /* nlabelled global document ids */
+    const uint32_t* label;    /* nlabelled classes */
+} tfidf_nb_params;
+/* Host only, no GPU.  TFIDF_E_INVAL for: NULL; size < sizeof(tfidf_nb_params); K == 0 or
+ * K > TFIDF_NB_MAX_CLASSES; an unknown variant or feature; an alpha that is NaN, infinite,
+ * negative or > TFIDF_NB_MAX_ALPHA; nlabelled >= 2^32, or > 0 with a NULL doc or label; a label
+ * >= K; a repeated id; a class without a labelled document. */
+int tfidf_nb_check(const tfidf_nb_params* params);
+
+/* The fitted model on the host.  The matrices are term-major like the device's: entry (t, c) is
+ * at t * nclasses + c, t = term rank.  Arrays are owned by the library and released by
+ * tfidf_nb_model_free(). */
+typedef struct tfidf_nb_model {
+    uint64_t  size;
+    uint32_t  nclasses;       /* K */
+    uint32_t  nterms;         /* V */
+    uint32_t  variant;
+    uint32_t  feature;
+    uint32_t  uniform_prior;
+    uint32_t  reserved;
+    double    alpha;          /* the value used (1.0 for the default) */
+    uint64_t  nlabelled;      /* n */
+    uint64_t* class_docs;     /* K: n_c */
+    uint64_t* class_total;    /* K: T[c] */
+    uint64_t* feature_count;  /* V * K: FC */
+    double*   prior;          /* K */
+    double*   weight;         /* V * K: W */
+} tfidf_nb_model;
+void tfidf_nb_model_free(tfidf_nb_model* m);
+
+/* Per row the label and its score; with TFIDF_NB_ALL_SCORES scores[r * nclasses + c] as well
+ * (NULL otherwise).  A row of a document the context does not hold has pos = UINT32_MAX, label
+ * TFIDF_NO_CLASS and scores of +0.0.  Arrays are owned by the library and released by
+ * tfidf_nb_labels_free(). */
+typedef struct tfidf_nb_labels {
+    uint32_t  ndocs;
+    uint32_t  nclasses;
+    uint32_t* doc;            /* per row: global document id (tfidf_nb_predict); the row's index (the row calls) */
+    uint32_t* pos;            /* per row: output position, as tfidf_doc_terms.pos; the row's index (the row calls) */
+    uint32_t* label;
+    double*   score;          /* score(d, label(d)) */
+    double*   scores;         /* ndocs * nclasses, or NULL */
+} tfidf_nb_labels;
+void tfidf_nb_labels_free(tfidf_nb_labels* l);
+
+/* Fits the model over the resident result of the last run, in HBM; it stays in the context until
+ * the next tfidf_run, tfidf_prune or tfidf_model_import (term ranks change there) or the next
+ * tfidf_nb_fit.  tfidf_reweight keeps it: the model reads counts only.  One shard; with a
+ * communicator attached the call is local.  The run's result is not disturbed.
+ * TFIDF_E_INVAL: NULL arguments, parameters that fail tfidf_nb_check, an id the context does not
+ * hold.  TFIDF_E_STATE: before a successful run, and on a context that holds only an imported
+ * model.  TFIDF_E_CAPACITY, before any device work: when the two dense matrices (FC as u64, W as
+ * f64, both [V][K] with 64-bit offsets) and the per-term and per-class words exceed TFIDF_NB_MB
+ * MiB (environment, read by tfidf_open; default 1024, a guess that nobody has measured).  All
+ * device buffers belong to the context: a repeated identical call allocates nothing
+ * (tfidf_alloc_stats).  A call refused by the check, the state or the budget leaves an earlier
+ * model in place; one that fails later (an id the context does not hold, a device error) leaves
+ * the context without a model. */
+int tfidf_nb_fit(tfidf_ctx* ctx, const tfidf_nb_params* params);
+/* Labels of resident documents, with the row rules of tfidf_top_terms: doc_ids == NULL gives one
+ * row per document in output order (ndocs is ignored); otherwise one row per entry in the
+ * caller's order, duplicates allowed.  TFIDF_E_STATE without a fitted model; TFIDF_E_INVAL for
+ * NULL ctx or out or unknown flag bits.  On an error *out is zeroed. */
+int tfidf_nb_predict(tfidf_ctx* ctx, const uint32_t* doc_ids, uint32_t ndocs, uint32_t flags, tfidf_nb_labels* out);
+/* Labels of the rows of a tfidf_transform of this context: row_off, term and count are uploaded
+ * (the call is independent of transform's slices); df, score and the words are not read.
+ * TFIDF_E_INVAL for a non-monotone row_off, row_off[0] != 0, row_off[ndocs] != npairs or a term >= V (a merged
+ * tfidf_group_transform carries UINT32_MAX and is refused). */
+int tfidf_nb_predict_rows(tfidf_ctx* ctx, const tfidf_rows* rows, uint32_t flags, tfidf_nb_labels* out);
+/* The fitted model copied to the host.  TFIDF_E_STATE without one. */
+int tfidf_nb_export(tfidf_ctx* ctx, tfidf_nb_model* out);
+/* Counters of the last tfidf_nb_fit, with the times of the last predict call added (the caller
+ * sets `size` = sizeof, as tfidf_query_info). */
+typedef struct tfidf_nb_info {
+    uint64_t size;
+    uint32_t nclasses;
+    uint32_t nterms;
+    uint64_t nlabelled;
+    uint64_t matrix_bytes;    /* FC + W */
+    uint64_t nlogs;           /* log() calls of the fit, all on the host */
+    uint64_t nlisted;         /* distinct log arguments above the table (the sorted list) */
+    uint32_t predict_rows;    /* rows of the last predict call */
+    uint32_t reserved;
+    double   ms_logs_host;    /* host time of the fit's logs */
+    double   ms_count;        /* device times (HIP events): the count pass and its reductions */
+    double   ms_weights;      /* the weight pass */
+    double   ms_predict;      /* the last predict call's kernel */
+    double   ms_total;        /* host wall time of the fit */
+} tfidf_nb_info;
+int tfidf_last_nb_info(const tfidf_ctx* ctx, tfidf_nb_info* info);
+/* Host only, plain C (nb_host.c): the same definition, the second opinion on the device.
+ * tfidf_result_nb_fit reads a fetched result: a document is a maximal run of equal pair_doc, its
+ * feature values pair_count, V = r->nterms, the documents r->doc_id.  TFIDF_E_INVAL for NULL
+ * arguments, parameters that fail the check, a labelled id that is not among doc_id, a pair_term
+ * outside the term table or a pair_doc that is not among doc_id; *out is zeroed then.
+ * tfidf_nb_model_predict scores nrows rows (row r = pairs [row_off[r], row_off[r + 1]) of term and
+ * count) against a model, from tfidf_nb_export or tfidf_result_nb_fit; doc and pos of the answer
+ * are the row's index.  TFIDF_E_INVAL for NULL arguments, a model without its arrays, a
+ * non-monotone row_off or a term >= nterms. */
+int tfidf_result_nb_fit(const tfidf_result* r, const tfidf_nb_params* params, tfidf_nb_model* out);
+int tfidf_nb_model_predict(const tfidf_nb_model* m, uint32_t nrows, const uint64_t* row_off, const uint32_t* term,
+                           const uint32_t* count, uint32_t flags, tfidf_nb_labels* out);
+
 /* ---------------------------------------------------------------- ingest ---- */
 
 /* Reference input contract (TFIDF.c:98-110,130-147): N = number of entries of `dir`

@@ -193,6 +193,11 @@ int tfidf_open(int device, tfidf_ctx** out) {
         const unsigned long long mb = strtoull(kdd, nullptr, 0);
         if (mb >= 1 && mb <= (1ull << 20)) ctx->dedup_bytes = mb << 20;
     }
+    const char* knb = getenv("TFIDF_NB_MB");
+    if (knb) {
+        const unsigned long long mb = strtoull(knb, nullptr, 0);
+        if (mb >= 1 && mb <= (1ull << 20)) ctx->nb_bytes = mb << 20;
+    }
     const char* kkm = getenv("TFIDF_KMEANS_MB");
     if (kkm) {
         const unsigned long long mb = strtoull(kkm, nullptr, 0);
@@ -305,6 +310,11 @@ void tfidf_close(tfidf_ctx* ctx) {
     for (hipEvent_t e : ctx->ev_dd)
         if (e) (void)hipEventDestroy(e);
     for (DevBuf* b : {&ctx->dd_h0, &ctx->dd_sig, &ctx->dd_fam, &ctx->dd_misc, &ctx->dd_work}) b->release();
+    for (hipEvent_t e : ctx->ev_nb)
+        if (e) (void)hipEventDestroy(e);
+    for (DevBuf* b : {&ctx->nb_FC, &ctx->nb_W, &ctx->nb_work, &ctx->nb_lut, &ctx->nb_list, &ctx->nb_ids, &ctx->nb_rows,
+                      &ctx->nb_out})
+        b->release();
     for (hipEvent_t e : ctx->ev_tr)
         if (e) (void)hipEventDestroy(e);
     for (DevBuf* b : {&ctx->tr_bytes, &ctx->tr_off, &ctx->tr_a, &ctx->tr_b}) b->release();
@@ -1550,6 +1560,7 @@ extern "C" int tfidf_run(tfidf_ctx* ctx, const tfidf_corpus* in) {
     ctx->tmeta_valid = false;
     ctx->norm_valid = false;
     ctx->h0_valid = false;
+    ctx->nb_valid = false;
     ctx->bm25_L_valid = false;
     CorpusDev c{};
     const uint32_t* dev_ids = nullptr;

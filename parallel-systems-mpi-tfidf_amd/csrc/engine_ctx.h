@@ -17,6 +17,8 @@
  *   engine_similar.cpp    tfidf_similar, the halves of tfidf_group_similar; sim_norms
  *   engine_kmeans.cpp     tfidf_kmeans
  *   engine_dedup.cpp      tfidf_minhash, tfidf_near_dups (dedup.hip; the groups: dedup_host.c)
+ *   engine_nb.cpp         tfidf_nb_fit, tfidf_nb_predict, tfidf_nb_predict_rows, tfidf_nb_export
+ *                         (nb.hip; the check and the host twin: nb_host.c)
  * The add-on calls run between runs on the context's stream and use the run's arena as scratch
  * only; none of them is on the path tfidf_run times.
  */
@@ -316,6 +318,22 @@ struct tfidf_ctx {
     hipEvent_t ev_dd[3] = {};                   /* hash / signature, bands / verify bounds (created by the first call) */
     bool h0_valid = false;                      /* dd_h0 holds this result's term hashes */
     tfidf_dedup_info ddinfo{};
+    /* Naive Bayes (tfidf_nb_fit / tfidf_nb_predict, nb.hip): the two dense matrices [V][K] (feature
+     * counts, weights); the per-term and per-class words (F, T, the classes' logarithms, the priors,
+     * the counters, the labels by output position); the logarithm table and the sorted list behind
+     * it; the fit's or a predict call's ids and positions; uploaded rows; a predict batch's labels
+     * and scores.  The model stays until the next run, prune, import or fit (nb_valid). */
+    DevBuf nb_FC, nb_W, nb_work, nb_lut, nb_list, nb_ids, nb_rows, nb_out;
+    uint64_t nb_bytes = 1024ull << 20;          /* env TFIDF_NB_MB: budget of nb_FC + nb_W + nb_work */
+    hipEvent_t ev_nb[4] = {};                   /* count / weights or predict bounds (created by the first call) */
+    bool nb_valid = false;
+    uint32_t nb_K = 0, nb_V = 0, nb_variant = 0, nb_feature = 0, nb_uniform = 0;
+    double nb_alpha = 0;
+    uint64_t nb_n = 0;
+    const double* nb_prior_dev = nullptr;       /* points into nb_work */
+    const uint64_t* nb_T_dev = nullptr;
+    std::vector<uint64_t> nb_class_docs;        /* n_c, kept for tfidf_nb_export */
+    tfidf_nb_info nbinfo{};
 #define WR_NBUF 8
 #define WR_BUF (16ull << 20)
 #define WR_GROUPS 8

@@ -107,6 +107,7 @@ extern "C" int tfidf_model_import(tfidf_ctx* ctx, const tfidf_model* m) {
     ctx->tmeta_valid = false;
     ctx->norm_valid = false;
     ctx->h0_valid = false;
+    ctx->nb_valid = false;
     ctx->bm25_L_valid = false;
     if (const int q = idf_pin_quiesce(ctx)) return q;
     ctx->vcap = cap;

@@ -147,6 +147,7 @@ extern "C" int tfidf_prune(tfidf_ctx* ctx, const tfidf_prune_params* params) {
     ctx->text_valid = false;
     ctx->tmeta_valid = false;
     ctx->h0_valid = false;
+    ctx->nb_valid = false;     /* the classifier's matrices are indexed by the old ranks */
     ctx->norm_valid = false;   /* bm25_L stays: docSize is unchanged */
     pi.nterms_after = V2;
     pi.npairs_after = P2;

@@ -371,6 +371,8 @@ int launch_format_f64(const double* v, uint64_t n, uint8_t* out, uint32_t* statu
 #define TM_W2048_WG_PER_CU 6u  /* k_terms_select<64, 2048>: 24 KiB */
 #define TM_BIG_WG_PER_CU   3u  /* k_terms_select<256, 4096, BIG> */
 #define PR_WG_PER_CU       4u  /* k_pr_pairs (count and write) */
+#define NB_WG_PER_CU       8u  /* k_nb_count, k_nb_sums, k_nb_predict: a wave per document or row, as k_km_assign */
+#define NB_EL_WG_PER_CU    8u  /* k_nb_argmax, k_nb_list, k_nb_weights: a thread per matrix entry */
 #define BIG_WG_MAX         256u /* k_doc_score_big, k_sim_score_big, k_rw_docs_big: at most this many ... */
 #define BIG_WG_PER_CU      4u  /* ... and this many per CU */
 
@@ -1011,5 +1013,71 @@ struct DdVerArgs {
     uint32_t* big_count;         /* one word, zeroed by the launch */
 };
 int launch_dd_verify(const DdVerArgs& a, uint32_t ncu, hipStream_t s);
+
+/* ---- Naive Bayes classification (nb.hip, tfidf_nb_fit / tfidf_nb_predict) ---- */
+#define NB_MAX_K    256u           /* TFIDF_NB_MAX_CLASSES: four accumulators per lane of the owner wave */
+#define NB_NO_CLASS 0xFFFFFFFFu
+#define NB_LUT_MAX  (1u << 16)     /* the host tabulates log(fl((double)m + alpha)) for m = 0..min(max, NB_LUT_MAX) */
+/* The fit's device side.  The matrices are term-major: entry (t, c) at t * K + c (64-bit), so a
+ * term's K values are one contiguous row.  An entry's log argument m is FC (multinomial) or
+ * F[t] - FC (complement); its logarithm comes from lut[m] up to lut_n - 1 and beyond from the
+ * sorted list (list_key ascending and distinct, list_val beside it). */
+struct NbFitArgs {
+    const uint64_t* off;         /* ndocs + 1: pairs of the document at an output position */
+    const uint32_t* term;
+    const uint32_t* cnt;
+    uint64_t npairs;
+    uint32_t ndocs;
+    uint32_t V;
+    uint32_t K;
+    uint32_t complement, binary;
+    const uint32_t* lab;         /* [ndocs] class by output position, NB_NO_CLASS: unlabelled */
+    uint64_t* FC;                /* [V][K] */
+    uint64_t* F;                 /* [V] */
+    uint64_t* T;                 /* [K] */
+    uint64_t* misc;              /* [0] the largest log argument, [1] arguments >= lut_n, [2] the list's cursor */
+    uint64_t* list;              /* the arguments >= lut_n, unordered, with repeats (nb_list fills it) */
+    uint64_t list_cap;
+    const double* lut;
+    uint64_t lut_n;
+    const uint64_t* list_key;
+    const double* list_val;
+    uint64_t list_n;
+    const double* lc;            /* [K] the class's own logarithm */
+    double* W;                   /* [V][K] */
+};
+/* FC = 0, then the document-major pass: a wave per labelled document adds x into FC[t * K + label]
+ * with 64-bit integer atomics (exact in any order) */
+int launch_nb_count(const NbFitArgs& a, uint32_t ncu, hipStream_t s);
+/* F[t] and T[c] (a wave per term row; the waves' column sums end in 64-bit integer atomics), then
+ * misc[0] and misc[1] for the table of lut_n entries the host is about to build */
+int launch_nb_sums(const NbFitArgs& a, uint32_t ncu, hipStream_t s);
+int launch_nb_argmax(const NbFitArgs& a, uint32_t ncu, hipStream_t s);
+/* the arguments >= lut_n into list (at most list_cap) */
+int launch_nb_list(const NbFitArgs& a, uint32_t ncu, hipStream_t s);
+/* W: one rounded subtraction per entry */
+int launch_nb_weights(const NbFitArgs& a, uint32_t ncu, hipStream_t s);
+/* Prediction, the shape of k_km_assign: a wave per row, lane l owns the scores of the classes
+ * l + 64 * i.  Row r < nrows is the pairs [off[j], off[j + 1]) with j = pos ? pos[r] : r, clamped to
+ * npairs; pos[r] >= ndocs (a document the context does not hold) gives NB_NO_CLASS and +0.0.
+ * One kernel serves the resident pairs (off = out_off, ndocs = the context's) and uploaded rows
+ * (pos null, ndocs = nrows). */
+struct NbPredictArgs {
+    const uint64_t* off;
+    const uint32_t* term;
+    const uint32_t* cnt;
+    uint64_t npairs;
+    uint32_t ndocs;
+    const uint32_t* pos;         /* null: row r is position r */
+    uint32_t nrows;
+    uint32_t V, K;
+    uint32_t binary;
+    const double* W;             /* [V][K] */
+    const double* prior;         /* [K] */
+    uint32_t* label;             /* [nrows] */
+    double* score;               /* [nrows] */
+    double* all;                 /* [nrows][K] or null */
+};
+int launch_nb_predict(const NbPredictArgs& a, uint32_t ncu, hipStream_t s);
 
 #endif

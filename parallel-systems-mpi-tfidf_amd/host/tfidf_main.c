@@ -94,6 +94,24 @@
  *   --transform-file FILE  the file (default transform.txt).
  * With several shards the ranks' rows are merged by word (tfidf_group_transform).
  *
+ * Classification (Naive Bayes fitted on the documents a file labels: tfidf_nb_fit and
+ * tfidf_nb_predict / tfidf_nb_predict_rows):
+ *   --labels FILE          lines "doc<N>\t<name>": document N of input/ belongs to class <name>.  The
+ *                          classes are the distinct names in byte order (host/labels_file.h).  The fit
+ *                          runs after output.txt and the other files, on the pairs the pruning
+ *                          options left; the weighting options play no part (counts only).
+ *                          With it exactly one of:
+ *   --classify DIR         DIR/doc1..docM go through the analyzer and n-gram options like the
+ *                          documents of --transform DIR, then tfidf_transform, and are classified;
+ *   --classify-unlabelled  the documents of input/ that FILE does not label are classified;
+ *   --classify-file FILE   the file (default classes.txt): a line "doc<M>\t<name>\t%.16f" per
+ *                          classified document, the class and its score, documents in "docN@" order;
+ *   --nb-alpha X           the smoothing, finite and > 0 (default 1);
+ *   --nb-complement        complement NB in place of multinomial NB;
+ *   --nb-binary            a word counts once per document;
+ *   --nb-uniform-prior     no class prior (the complement never has one).
+ * One shard only and not under --model (exit 2), like --clusters.
+ *
  * Model (the term table, the global df and N as a file: fit once, serve from the file):
  *   --save-model FILE      after output.txt and the other files, the run's model is written to
  *                          FILE (tfidf_model_export + tfidf_model_save; with several shards
@@ -176,6 +194,7 @@
 #include <time.h>
 
 #include "../../include/tfidf.h"
+#include "labels_file.h"
 
 static double wall_ms(void) {
     struct timespec ts;
@@ -630,6 +649,117 @@ static int run_transform(tfidf_ctx* ctx, tfidf_group* g) {
     return rc;
 }
 
+/* --------------------------------------------------------------- classify -- */
+
+static struct {
+    const char* labels;   /* NULL: no classification, behaviour and bytes as without the options */
+    const char* dir;
+    int unlabelled;
+    int opts;             /* an --nb-* option was given */
+    const char* file;
+    tfidf_nb_params p;
+    labels_file lf;       /* parsed before anything touches the GPU */
+} g_nb = {NULL, NULL, 0, 0, "classes.txt", {sizeof(tfidf_nb_params), 0, TFIDF_NB_MULTINOMIAL, TFIDF_NB_COUNT, 0, 0.0, 0, NULL, NULL},
+          {0, 0, NULL, NULL, NULL}};
+
+/* --labels FILE: 0, or 2 after a line on stderr */
+static int load_labels(void) {
+    FILE* f = fopen(g_nb.labels, "rb");
+    if (!f) { fprintf(stderr, "tfidf: --labels: cannot open %s\n", g_nb.labels); return 2; }
+    size_t cap = 1 << 16, n = 0;
+    uint8_t* b = (uint8_t*)malloc(cap);
+    for (;;) {
+        if (!b) { fclose(f); return fail(TFIDF_E_NOMEM); }
+        const size_t got = fread(b + n, 1, cap - n, f);
+        n += got;
+        if (got == 0) break;
+        if (n == cap) { cap *= 2; b = (uint8_t*)realloc(b, cap); }
+    }
+    fclose(f);
+    size_t bad = 0;
+    const int rc = labels_parse(b, n, &g_nb.lf, &bad);
+    free(b);
+    if (rc) {
+        if (bad) fprintf(stderr, "tfidf: --labels: %s line %zu is not \"doc<N>\\t<name>\"\n", g_nb.labels, bad);
+        else fprintf(stderr, "tfidf: --labels: %s holds no line, or more than %u classes\n", g_nb.labels, LABELS_MAX_CLASSES);
+        return 2;
+    }
+    g_nb.p.nclasses = g_nb.lf.k;
+    g_nb.p.nlabelled = g_nb.lf.n;
+    g_nb.p.doc = g_nb.lf.doc;
+    g_nb.p.label = g_nb.lf.label;
+    if (tfidf_nb_check(&g_nb.p) != TFIDF_OK) {
+        fprintf(stderr, "tfidf: --labels: %s names a document twice, or --nb-alpha is not finite and > 0\n", g_nb.labels);
+        return 2;
+    }
+    return 0;
+}
+
+static int u32_cmp(const void* a, const void* b) {
+    const uint32_t x = *(const uint32_t*)a, y = *(const uint32_t*)b;
+    return x < y ? -1 : (x > y ? 1 : 0);
+}
+
+/* --labels: the fit on ctx's documents, then the labels of --classify DIR or of the unlabelled */
+static int run_classify(tfidf_ctx* ctx) {
+    if (!g_nb.labels) return TFIDF_OK;
+    int rc = tfidf_nb_fit(ctx, &g_nb.p);
+    if (rc == TFIDF_E_INVAL) fprintf(stderr, "tfidf: --labels: %s names a document that input/ does not hold\n", g_nb.labels);
+    if (rc == TFIDF_E_CAPACITY) fprintf(stderr, "tfidf: --labels: the classifier's matrices exceed TFIDF_NB_MB\n");
+    if (rc) return rc;
+    tfidf_nb_labels out;
+    memset(&out, 0, sizeof(out));
+    uint32_t* ids = NULL;       /* --classify: the batch's documents in "docN@" order */
+    uint32_t* sorted = NULL;    /* --classify-unlabelled: the labelled ids, ascending */
+    if (g_nb.dir) {
+        tfidf_corpus b;
+        memset(&b, 0, sizeof(b));
+        uint8_t* bytes = NULL;
+        uint64_t* off = NULL;
+        uint32_t bad = 0;
+        rc = tfidf_ingest_dir(g_nb.dir, &bytes, &b.nbytes, &off, &b.ndocs, &bad);
+        if (rc == TFIDF_E_NOINPUT) { printf("Directory failed to open\n"); return TFIDF_OK; }
+        if (rc == TFIDF_E_NODOC) { (void)missing_doc(g_nb.dir, bad, b.ndocs); return TFIDF_OK; }
+        if (!rc) rc = analyze_host_batch(bytes, b.nbytes, off, b.ndocs);
+        if (!rc) rc = ngram_host_batch(&bytes, &b.nbytes, &off, b.ndocs);
+        b.bytes = bytes;
+        b.doc_off = off;
+        tfidf_rows t;
+        memset(&t, 0, sizeof(t));
+        ids = (uint32_t*)malloc(((size_t)b.ndocs + 1) * sizeof(uint32_t));
+        if (!rc) rc = ids ? tfidf_doc_name_order(b.ndocs, ids) : TFIDF_E_NOMEM;
+        if (!rc) rc = tfidf_transform(ctx, &b, &t);
+        if (!rc) rc = tfidf_nb_predict_rows(ctx, &t, 0, &out);
+        tfidf_rows_free(&t);
+        tfidf_free(bytes);
+        tfidf_free(off);
+    } else {
+        rc = tfidf_nb_predict(ctx, NULL, 0, 0, &out);
+        sorted = (uint32_t*)malloc(((size_t)g_nb.lf.n + 1) * sizeof(uint32_t));
+        if (!rc && !sorted) rc = TFIDF_E_NOMEM;
+        if (!rc) {
+            memcpy(sorted, g_nb.lf.doc, (size_t)g_nb.lf.n * sizeof(uint32_t));
+            qsort(sorted, g_nb.lf.n, sizeof(uint32_t), u32_cmp);
+        }
+    }
+    if (!rc) {
+        FILE* f = fopen(g_nb.file, "w");
+        if (!f) printf("Error Opening File: %s\n", g_nb.file);
+        for (uint32_t i = 0; f && i < out.ndocs; ++i) {
+            const uint32_t r = ids ? ids[i] - 1 : i;                  /* rows are in batch order, resident ones in "docN@" order */
+            const uint32_t id = ids ? ids[i] : out.doc[i];
+            if (sorted && bsearch(&id, sorted, g_nb.lf.n, sizeof(uint32_t), u32_cmp)) continue;
+            if (out.label[r] >= g_nb.lf.k) continue;
+            fprintf(f, "doc%u\t%s\t%.16f\n", id, g_nb.lf.name[out.label[r]], out.score[r]);
+        }
+        if (f && fclose(f) != 0) rc = TFIDF_E_OUTPUT;
+    }
+    tfidf_nb_labels_free(&out);
+    free(ids);
+    free(sorted);
+    return rc;
+}
+
 /* ------------------------------------------------------------------ model -- */
 
 static struct {
@@ -797,6 +927,7 @@ static int run_single(int device, const char* indir, const char* outpath, int de
     if (!rc) rc = run_clusters(ctx);
     if (!rc) rc = run_dups(ctx);
     if (!rc) rc = run_transform(ctx, NULL);
+    if (!rc) rc = run_classify(ctx);
     if (!rc) rc = save_model(ctx, NULL);
     tfidf_close(ctx);
     if (rc) return fail(rc);
@@ -928,6 +1059,8 @@ static int usage(void) {
                     "[--clusters K [--clusters-iter I] [--clusters-seeds FILE] [--clusters-terms T] [--clusters-file FILE]] "
                     "[--near-dups T [--near-dups-hashes H] [--near-dups-rows R] [--near-dups-seed S] [--near-dups-file FILE]] "
                     "[--transform DIR [--transform-file FILE]] [--save-model FILE] "
+                    "[--labels FILE (--classify DIR | --classify-unlabelled) [--classify-file FILE] [--nb-alpha X] "
+                    "[--nb-complement] [--nb-binary] [--nb-uniform-prior]] "
                     "[--min-df X] [--max-df X] [--max-features M] "
                     "[--tf ratio|raw|log|binary] [--sublinear-tf] [--idf ref|smooth|plus1|none] [--norm none|l1|l2] "
                     "[--lower] [--strip-punct] [--min-token N] [--stopwords FILE] [--stem] [--utf8] [--ngrams SPEC [--ngram-joiner C]]\n"
@@ -1019,6 +1152,20 @@ int main(int argc, char** argv) {
         else if (!strcmp(argv[i], "--transform") && i + 1 < argc) g_transform.dir = argv[++i];
         else if (!strcmp(argv[i], "--save-model") && i + 1 < argc) g_model.save = argv[++i];
         else if (!strcmp(argv[i], "--model") && i + 1 < argc) g_model.load = argv[++i];
+        else if (!strcmp(argv[i], "--labels") && i + 1 < argc) g_nb.labels = argv[++i];
+        else if (!strcmp(argv[i], "--classify-file") && i + 1 < argc) g_nb.file = argv[++i];
+        else if (!strcmp(argv[i], "--classify-unlabelled")) g_nb.unlabelled = 1;
+        else if (!strcmp(argv[i], "--classify") && i + 1 < argc) g_nb.dir = argv[++i];
+        else if (!strcmp(argv[i], "--nb-complement")) { g_nb.p.variant = TFIDF_NB_COMPLEMENT; g_nb.opts = 1; }
+        else if (!strcmp(argv[i], "--nb-binary")) { g_nb.p.feature = TFIDF_NB_BINARY; g_nb.opts = 1; }
+        else if (!strcmp(argv[i], "--nb-uniform-prior")) { g_nb.p.uniform_prior = 1; g_nb.opts = 1; }
+        else if (!strcmp(argv[i], "--nb-alpha") && i + 1 < argc) {
+            char* end = NULL;
+            const double v = strtod(argv[++i], &end);
+            if (!end || *end || end == argv[i] || !(v > 0.0 && v <= TFIDF_NB_MAX_ALPHA)) { fprintf(stderr, "tfidf: --nb-alpha takes a finite number above 0\n"); return 2; }
+            g_nb.p.alpha = v;
+            g_nb.opts = 1;
+        }
         else if (!strcmp(argv[i], "--near-dups-file") && i + 1 < argc) g_dups.file = argv[++i];
         else if (!strcmp(argv[i], "--near-dups-hashes") && i + 1 < argc) {
             char* end = NULL;
@@ -1123,13 +1270,28 @@ int main(int argc, char** argv) {
         fprintf(stderr, "tfidf: --near-dups-rows must divide --near-dups-hashes (%u)\n", g_dups.hashes);
         return 2;
     }
+    if (!g_nb.labels ? (g_nb.dir || g_nb.unlabelled || g_nb.opts) : ((g_nb.dir != NULL) + g_nb.unlabelled != 1)) {
+        fprintf(stderr, "tfidf: --labels FILE goes with exactly one of --classify DIR and --classify-unlabelled, and these and the "
+                        "--nb-* options need --labels FILE\n");
+        return 2;
+    }
+    /* asked of the options as given, before the device count: --gpus / --shards above 1 */
+    if (g_nb.labels && (nshards > 1 || (nshards <= 0 && ngpus > 1 && device < 0))) {
+        fprintf(stderr, "tfidf: --labels runs on one shard only: the shards' term tables differ, so they share no "
+                        "weight matrix (drop --gpus / --shards)\n");
+        return 2;
+    }
+    if (g_nb.labels && !g_model.load) {
+        const int bad = load_labels();
+        if (bad) return bad;
+    }
     if (g_model.load) {   /* a model holds no pairs: nothing to rank, list or print */
         if (!g_transform.dir) {
             fprintf(stderr, "tfidf: --model needs --transform DIR\n");
             return 2;
         }
-        if (g_query.file || g_keywords.k || g_similar.k || g_clusters.k || g_dups.on || g_model.save || debug) {
-            fprintf(stderr, "tfidf: --model cannot be combined with --query, --keywords, --similar, --clusters, --near-dups, --save-model or "
+        if (g_query.file || g_keywords.k || g_similar.k || g_clusters.k || g_dups.on || g_nb.labels || g_model.save || debug) {
+            fprintf(stderr, "tfidf: --model cannot be combined with --query, --keywords, --similar, --clusters, --near-dups, --labels, --save-model or "
                             "--debug-jobs: they need a run's pairs\n");
             return 2;
         }

@@ -55,6 +55,8 @@ EXPORTS = [
     "tfidf_last_reweight_info", "tfidf_result_reweight",
     "tfidf_dedup_check", "tfidf_minhash", "tfidf_signatures_free", "tfidf_near_dups", "tfidf_dups_free",
     "tfidf_last_dedup_info", "tfidf_result_minhash", "tfidf_result_near_dups", "tfidf_dedup_groups",
+    "tfidf_nb_check", "tfidf_nb_model_free", "tfidf_nb_labels_free", "tfidf_nb_fit", "tfidf_nb_predict",
+    "tfidf_nb_predict_rows", "tfidf_nb_export", "tfidf_last_nb_info", "tfidf_result_nb_fit", "tfidf_nb_model_predict",
 ]
 QUERY_MAX_K = 1024  # TFIDF_QUERY_MAX_K
 TERMS_MAX_K = 1024  # TFIDF_TERMS_MAX_K
@@ -87,6 +89,12 @@ TF_MODES = {"ratio": 0, "raw": 1, "log": 2, "binary": 3}  # TFIDF_TF_*
 IDF_MODES = {"ref": 0, "smooth": 1, "plus1": 2, "none": 3}  # TFIDF_IDF_*
 NORM_MODES = {"none": 0, "l2": 1, "l1": 2}  # TFIDF_NORM_*
 MINHASH_MAX_H = 256  # TFIDF_MINHASH_MAX_H
+NB_MAX_CLASSES = 256  # TFIDF_NB_MAX_CLASSES
+NB_MAX_ALPHA = float.fromhex("0x1p+900")  # TFIDF_NB_MAX_ALPHA
+NB_VARIANTS = {"multinomial": 0, "complement": 1}  # TFIDF_NB_MULTINOMIAL / TFIDF_NB_COMPLEMENT
+NB_FEATURES = {"count": 0, "binary": 1}  # TFIDF_NB_COUNT / TFIDF_NB_BINARY
+NB_ALL_SCORES = 1  # TFIDF_NB_ALL_SCORES
+NO_CLASS = 0xFFFFFFFF  # TFIDF_NO_CLASS: tfidf_nb_labels.label of a document the context does not hold
 
 
 class Corpus(C.Structure):
@@ -354,6 +362,39 @@ class DedupInfo(C.Structure):
     ]
 
 
+class NbParams(C.Structure):
+    _fields_ = [
+        ("size", C.c_uint64), ("nclasses", C.c_uint32), ("variant", C.c_uint32), ("feature", C.c_uint32),
+        ("uniform_prior", C.c_uint32), ("alpha", C.c_double), ("nlabelled", C.c_uint64),
+        ("doc", C.POINTER(C.c_uint32)), ("label", C.POINTER(C.c_uint32)),
+    ]
+
+
+class NbModel(C.Structure):
+    _fields_ = [
+        ("size", C.c_uint64), ("nclasses", C.c_uint32), ("nterms", C.c_uint32), ("variant", C.c_uint32),
+        ("feature", C.c_uint32), ("uniform_prior", C.c_uint32), ("reserved", C.c_uint32), ("alpha", C.c_double),
+        ("nlabelled", C.c_uint64), ("class_docs", C.POINTER(C.c_uint64)), ("class_total", C.POINTER(C.c_uint64)),
+        ("feature_count", C.POINTER(C.c_uint64)), ("prior", C.POINTER(C.c_double)), ("weight", C.POINTER(C.c_double)),
+    ]
+
+
+class NbLabels(C.Structure):
+    _fields_ = [
+        ("ndocs", C.c_uint32), ("nclasses", C.c_uint32), ("doc", C.POINTER(C.c_uint32)), ("pos", C.POINTER(C.c_uint32)),
+        ("label", C.POINTER(C.c_uint32)), ("score", C.POINTER(C.c_double)), ("scores", C.POINTER(C.c_double)),
+    ]
+
+
+class NbInfo(C.Structure):
+    _fields_ = [
+        ("size", C.c_uint64), ("nclasses", C.c_uint32), ("nterms", C.c_uint32), ("nlabelled", C.c_uint64),
+        ("matrix_bytes", C.c_uint64), ("nlogs", C.c_uint64), ("nlisted", C.c_uint64), ("predict_rows", C.c_uint32),
+        ("reserved", C.c_uint32), ("ms_logs_host", C.c_double), ("ms_count", C.c_double), ("ms_weights", C.c_double),
+        ("ms_predict", C.c_double), ("ms_total", C.c_double),
+    ]
+
+
 class DirPlan(C.Structure):
     _fields_ = [
         ("ndocs", C.c_uint32), ("nshards", C.c_uint32), ("doc_ids", C.POINTER(C.c_uint32)),
@@ -492,6 +533,19 @@ def lib() -> C.CDLL:
         L.tfidf_result_near_dups.argtypes = [C.POINTER(Result), C.POINTER(DedupParams), C.POINTER(Dups)]
         L.tfidf_dedup_groups.argtypes = [C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p,
                                          C.POINTER(C.c_uint32)]
+        L.tfidf_nb_check.argtypes = [C.POINTER(NbParams)]
+        L.tfidf_nb_model_free.argtypes = [C.POINTER(NbModel)]
+        L.tfidf_nb_model_free.restype = None
+        L.tfidf_nb_labels_free.argtypes = [C.POINTER(NbLabels)]
+        L.tfidf_nb_labels_free.restype = None
+        L.tfidf_nb_fit.argtypes = [C.c_void_p, C.POINTER(NbParams)]
+        L.tfidf_nb_predict.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(NbLabels)]
+        L.tfidf_nb_predict_rows.argtypes = [C.c_void_p, C.POINTER(Rows), C.c_uint32, C.POINTER(NbLabels)]
+        L.tfidf_nb_export.argtypes = [C.c_void_p, C.POINTER(NbModel)]
+        L.tfidf_last_nb_info.argtypes = [C.c_void_p, C.POINTER(NbInfo)]
+        L.tfidf_result_nb_fit.argtypes = [C.POINTER(Result), C.POINTER(NbParams), C.POINTER(NbModel)]
+        L.tfidf_nb_model_predict.argtypes = [C.POINTER(NbModel), C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                             C.c_uint32, C.POINTER(NbLabels)]
         if L.tfidf_abi_version() != ABI_VERSION:
             raise RuntimeError(f"{LIB_PATH}: ABI version {L.tfidf_abi_version()}, binding expects {ABI_VERSION} "
                                f"(stale build: rebuild with __graft_entry__.build())")
@@ -955,6 +1009,110 @@ def result_near_dups(res: dict, doc_ids=None, nhashes: int = 0, rows: int = 0, s
         lib().tfidf_dups_free(C.byref(d))
 
 
+def nb_params(docs, labels, nclasses: int, variant="multinomial", feature="count", alpha: float = 0.0,
+              uniform_prior: bool = False, size=None):
+    """tfidf_nb_params over the labelled (global doc id, class) entries; alpha = 0 selects 1.0.
+    Returns (NbParams, the arrays it points into)."""
+    d = np.ascontiguousarray(docs, dtype=np.uint32)
+    lb = np.ascontiguousarray(labels, dtype=np.uint32)
+    assert len(d) == len(lb)
+    p = NbParams()
+    p.size = C.sizeof(NbParams) if size is None else size
+    p.nclasses, p.variant, p.feature = nclasses, _mode(NB_VARIANTS, variant), _mode(NB_FEATURES, feature)
+    p.uniform_prior, p.alpha, p.nlabelled = int(bool(uniform_prior)), alpha, len(d)
+    if len(d):
+        p.doc, p.label = d.ctypes.data_as(C.POINTER(C.c_uint32)), lb.ctypes.data_as(C.POINTER(C.c_uint32))
+    return p, (d, lb)
+
+
+def nb_check(p) -> int:
+    """tfidf_nb_check (host only): 0, or E_INVAL; None stands for a NULL pointer; a (NbParams, keep)
+    pair as nb_params returns it is accepted."""
+    if isinstance(p, tuple):
+        p = p[0]
+    return int(lib().tfidf_nb_check(None if p is None else C.byref(p)))
+
+
+def _nb_model_dict(m: NbModel) -> dict:
+    """A library-filled tfidf_nb_model as a dict of copies; the matrices as [V, K] arrays."""
+    K, V = int(m.nclasses), int(m.nterms)
+
+    def arr(p, n, dt):
+        return np.ctypeslib.as_array(p, shape=(n,)).astype(dt, copy=True) if n else np.zeros(0, dtype=dt)
+
+    return {"nclasses": K, "nterms": V, "variant": int(m.variant), "feature": int(m.feature),
+            "uniform_prior": int(m.uniform_prior), "alpha": float(m.alpha), "nlabelled": int(m.nlabelled),
+            "class_docs": arr(m.class_docs, K, np.uint64), "class_total": arr(m.class_total, K, np.uint64),
+            "feature_count": arr(m.feature_count, V * K, np.uint64).reshape(V, K), "prior": arr(m.prior, K, np.float64),
+            "weight": arr(m.weight, V * K, np.float64).reshape(V, K)}
+
+
+def _nb_model_struct(model: dict):
+    """tfidf_nb_model over a dict as _nb_model_dict returns it.  Returns (NbModel, keep)."""
+    K, V = int(model["nclasses"]), int(model["nterms"])
+    keep = [np.ascontiguousarray(model[k], dtype=dt).reshape(-1).copy()
+            for k, dt in (("class_docs", np.uint64), ("class_total", np.uint64), ("feature_count", np.uint64),
+                          ("prior", np.float64), ("weight", np.float64))]
+    keep = [a if len(a) else np.zeros(1, dtype=a.dtype) for a in keep]
+    m = NbModel()
+    m.size = C.sizeof(NbModel)
+    m.nclasses, m.nterms, m.variant, m.feature = K, V, int(model["variant"]), int(model["feature"])
+    m.uniform_prior, m.alpha, m.nlabelled = int(model["uniform_prior"]), float(model["alpha"]), int(model["nlabelled"])
+    u64, f64 = C.POINTER(C.c_uint64), C.POINTER(C.c_double)
+    m.class_docs, m.class_total, m.feature_count = (a.ctypes.data_as(u64) for a in keep[:3])
+    m.prior, m.weight = (a.ctypes.data_as(f64) for a in keep[3:])
+    return m, keep
+
+
+def _nb_labels_dict(t: NbLabels) -> dict:
+    R, K = int(t.ndocs), int(t.nclasses)
+    out = {"ndocs": R, "nclasses": K, "doc": _u32s(t.doc, R), "pos": _u32s(t.pos, R), "label": _u32s(t.label, R),
+           "score": np.ctypeslib.as_array(t.score, shape=(R,)).astype(np.float64, copy=True) if R else np.zeros(0)}
+    if t.scores:
+        out["scores"] = (np.ctypeslib.as_array(t.scores, shape=(R * K,)).astype(np.float64, copy=True).reshape(R, K)
+                         if R * K else np.zeros((R, K)))
+    return out
+
+
+def _nb_result(res: dict, doc_ids):
+    """_dedup_result with the pairs' counts: what tfidf_result_nb_fit reads"""
+    r, keep = _dedup_result(res, doc_ids)
+    cnt = np.ascontiguousarray(res["count"], dtype=np.uint32).copy()
+    if len(cnt):
+        r.pair_count = cnt.ctypes.data_as(C.POINTER(C.c_uint32))
+    return r, keep + (cnt,)
+
+
+def result_nb_fit(res: dict, docs, labels, nclasses: int, doc_ids=None, params=None, **kw) -> dict:
+    """tfidf_result_nb_fit (host only, plain C) on a result dict; term ranks are the strcmp("word\t")
+    order of the result's words.  kw: nb_params' options."""
+    p, keep_p = params if params is not None else nb_params(docs, labels, nclasses, **kw)
+    r, keep = _nb_result(res, doc_ids)
+    m = NbModel()
+    _chk(lib().tfidf_result_nb_fit(C.byref(r), C.byref(p), C.byref(m)), "tfidf_result_nb_fit")
+    try:
+        return _nb_model_dict(m)
+    finally:
+        lib().tfidf_nb_model_free(C.byref(m))
+
+
+def nb_model_predict(model: dict, row_off, term, count, all_scores: bool = True) -> dict:
+    """tfidf_nb_model_predict (host only, plain C): rows of (term rank, count) pairs against a
+    model dict."""
+    m, keep = _nb_model_struct(model)
+    ro = np.ascontiguousarray(row_off, dtype=np.uint64)
+    tm = np.ascontiguousarray(term, dtype=np.uint32)
+    ct = np.ascontiguousarray(count, dtype=np.uint32)
+    t = NbLabels()
+    _chk(lib().tfidf_nb_model_predict(C.byref(m), len(ro) - 1, _ptr(ro), _ptr(tm) if len(tm) else None,
+                                      _ptr(ct) if len(ct) else None, NB_ALL_SCORES if all_scores else 0, C.byref(t)),
+         "tfidf_nb_model_predict")
+    try:
+        return _nb_labels_dict(t)
+    finally:
+        lib().tfidf_nb_labels_free(C.byref(t))
+
+
 def synth_host(seed: int, V: int, mode: int, cdf, doc_ids, ntok):
     """Host generation (csrc/synth.h).  Returns (bytes uint8, doc_off uint64)."""
     ntok = np.ascontiguousarray(ntok, dtype=np.uint64)
@@ -1381,6 +1539,65 @@ class Engine:
         t.size = C.sizeof(DedupInfo)
         _chk(lib().tfidf_last_dedup_info(self.h, C.byref(t)), "tfidf_last_dedup_info")
         return {k: getattr(t, k) for k, _ in DedupInfo._fields_ if k != "size"}
+
+    def nb_fit(self, docs, labels, nclasses: int, params=None, **kw) -> None:
+        """Fits the Naive Bayes model on the labelled resident documents (tfidf_nb_fit): docs are
+        global ids, labels their classes 0..nclasses-1.  kw: variant ("multinomial" /
+        "complement"), feature ("count" / "binary"), alpha (0: 1.0), uniform_prior."""
+        p, keep = params if params is not None else nb_params(docs, labels, nclasses, **kw)
+        _chk(lib().tfidf_nb_fit(self.h, C.byref(p)), "tfidf_nb_fit")
+
+    def nb_predict(self, docs=None, all_scores: bool = False) -> dict:
+        """Labels of resident documents (tfidf_nb_predict): every document in output order, or the
+        listed global ids.  Returns numpy arrays doc, pos (NO_POS: not held), label (NO_CLASS
+        then), score and with all_scores scores[ndocs, nclasses]."""
+        ids = None if docs is None else np.ascontiguousarray(docs, dtype=np.uint32)
+        n = 0 if ids is None else len(ids)
+        if ids is not None and not n:
+            ids = np.zeros(1, dtype=np.uint32)                                   # an empty list is a list
+        t = NbLabels()
+        _chk(lib().tfidf_nb_predict(self.h, _ptr(ids), n, NB_ALL_SCORES if all_scores else 0, C.byref(t)),
+             "tfidf_nb_predict")
+        try:
+            return _nb_labels_dict(t)
+        finally:
+            lib().tfidf_nb_labels_free(C.byref(t))
+
+    def nb_predict_rows(self, rows: dict, all_scores: bool = False) -> dict:
+        """Labels of the rows of a transform of this context (tfidf_nb_predict_rows): rows is the
+        dict Engine.transform returns; row_off, term and count are read."""
+        ro = np.ascontiguousarray(rows["row_off"], dtype=np.uint64)
+        tm = np.ascontiguousarray(rows["term"], dtype=np.uint32)
+        ct = np.ascontiguousarray(rows["count"], dtype=np.uint32)
+        r = Rows()
+        r.ndocs, r.npairs = len(ro) - 1, len(tm)
+        r.row_off = ro.ctypes.data_as(C.POINTER(C.c_uint64))
+        if len(tm):
+            r.term, r.count = tm.ctypes.data_as(C.POINTER(C.c_uint32)), ct.ctypes.data_as(C.POINTER(C.c_uint32))
+        t = NbLabels()
+        _chk(lib().tfidf_nb_predict_rows(self.h, C.byref(r), NB_ALL_SCORES if all_scores else 0, C.byref(t)),
+             "tfidf_nb_predict_rows")
+        try:
+            return _nb_labels_dict(t)
+        finally:
+            lib().tfidf_nb_labels_free(C.byref(t))
+
+    def nb_export(self) -> dict:
+        """The fitted model on the host (tfidf_nb_export): class_docs, class_total, prior [K],
+        feature_count and weight [V, K], and the parameters."""
+        m = NbModel()
+        _chk(lib().tfidf_nb_export(self.h, C.byref(m)), "tfidf_nb_export")
+        try:
+            return _nb_model_dict(m)
+        finally:
+            lib().tfidf_nb_model_free(C.byref(m))
+
+    def nb_info(self) -> dict:
+        """Counters and times of the last nb_fit and predict call (tfidf_last_nb_info)."""
+        t = NbInfo()
+        t.size = C.sizeof(NbInfo)
+        _chk(lib().tfidf_last_nb_info(self.h, C.byref(t)), "tfidf_last_nb_info")
+        return {k: getattr(t, k) for k, _ in NbInfo._fields_ if k not in ("size", "reserved")}
 
     @contextlib.contextmanager
     def fetched(self):
