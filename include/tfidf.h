@@ -203,6 +203,11 @@ typedef struct tfidf_run_info {
     uint64_t idf_logs;        /* libm log() calls made for this run's table (every run builds its own) */
     double   ms_idf_host;     /* wall time of those calls (host threads) */
     double   ms_idf_wait;     /* time the run waited for them before the score stage */
+    /* the grid of the run's last tokenize+count launch: min(nchunks, CUs x 4) persistent
+     * workgroups (CUs: tfidf_grid_cus), nchunks for the general kernel, 0 when none was
+     * launched (an empty corpus) */
+    uint32_t k1_workgroups;
+    uint32_t reserved2;
 } tfidf_run_info;
 #define TFIDF_RUN_K1_VS   2u  /* slot-keyed tokenize+count kernel (the default path; the general
                                  kernel of TFIDF_K1=general or an unaligned corpus leaves it clear) */
@@ -230,7 +235,10 @@ int tfidf_alloc_stats(uint64_t* allocs, uint64_t* bytes);
  * workgroups that stride over the work.  The device's count, or env TFIDF_GRID_CUS (1..4096,
  * read at tfidf_open; anything else: the device's), which exists so that tests reach the second
  * and later trips of those loops on a small corpus.  No result depends on it.  The run's own
- * kernels ask the device and ignore it.  TFIDF_E_INVAL: a NULL argument. */
+ * persistent kernels follow it as well: the tokenize+count kernels (CUs x 4 workgroups that claim
+ * chunks; tfidf_run_info.k1_workgroups reports the grid), the score stage, and the formatter
+ * behind tfidf_format / tfidf_write_output_gpu (CUs x 8 workgroups, a wave per document).
+ * TFIDF_E_INVAL: a NULL argument. */
 int tfidf_grid_cus(tfidf_ctx* ctx, uint32_t* ncu);
 const char* tfidf_stage_name(int stage);
 /* HIP event timing of a run's stages (tfidf_run_info.ms_stage / ms_tokcount / ms_total):

@@ -348,34 +348,35 @@ int launch_term_meta(const uint4* vkeys, const uint64_t* vrep, const uint32_t* s
     return ok();
 }
 
-static unsigned emit_grid(uint32_t ndocs) {
+/* ncu_ctx: the caller's CU count (0: the device's) */
+static unsigned emit_grid(uint32_t ndocs, uint32_t ncu_ctx) {
     static int ncu = 0;
-    if (!ncu) {
+    if (!ncu_ctx && !ncu) {
         int dev = 0;
         if (hipGetDevice(&dev) != hipSuccess ||
             hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || ncu <= 0)
             ncu = 256;
     }
     const uint32_t need = (ndocs + NT / 64 - 1) / (NT / 64);
-    const uint32_t cap = (uint32_t)ncu * 8u;
+    const uint32_t cap = (ncu_ctx ? ncu_ctx : (uint32_t)ncu) * 8u;
     return need < cap ? (need ? need : 1u) : cap;
 }
 
-int launch_emit_bytes(const EmitLaunch& e, uint64_t* doc_bytes, hipStream_t s) {
+int launch_emit_bytes(const EmitLaunch& e, uint64_t* doc_bytes, hipStream_t s, uint32_t ncu) {
     if (!e.ndocs) return 0;
     EmitArgs a{e.order, e.doc_ids, e.out_off, e.term, e.score, e.tkey, e.tlen, e.corpus, 0u, e.ndocs,
                doc_bytes, nullptr, nullptr, e.status};
-    k_doc_text_bytes<<<emit_grid(e.ndocs), NT, 0, s>>>(a);
+    k_doc_text_bytes<<<emit_grid(e.ndocs, ncu), NT, 0, s>>>(a);
     return ok();
 }
 
 int launch_emit_write(const EmitLaunch& e, const uint64_t* doc_text, uint8_t* text, hipStream_t s, uint32_t d0,
-                      uint32_t d1) {
+                      uint32_t d1, uint32_t ncu) {
     if (d1 > e.ndocs) d1 = e.ndocs;
     if (d0 >= d1) return 0;
     EmitArgs a{e.order, e.doc_ids, e.out_off, e.term, e.score, e.tkey, e.tlen, e.corpus, d0, d1,
                nullptr, doc_text, text, e.status};
-    k_doc_text_write<<<emit_grid(d1 - d0), NT, 0, s>>>(a);
+    k_doc_text_write<<<emit_grid(d1 - d0, ncu), NT, 0, s>>>(a);
     return ok();
 }
 

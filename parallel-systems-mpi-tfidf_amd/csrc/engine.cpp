@@ -906,6 +906,9 @@ static int run_local(tfidf_ctx* ctx, const CorpusDev& c, const uint32_t* dev_ids
         HIPCHK(hipMemsetAsync(ctx->stamps.p, 0, 8 * K1_DEBUG_WORDS, s));
         o.stamps = ctx->stamps.as<unsigned long long>();
     }
+    /* the persistent kernels size their grids by the context's CU count and report them; the
+     * general kernel takes a workgroup per chunk */
+    uint32_t k1_wgs = 0;
     if (nchunks && ctx->k1_sl) {
         /* pinned source: the copy is stream-ordered before the launch, and the block is not
          * rewritten before the next run (every run synchronises with the host after K1) */
@@ -916,11 +919,15 @@ static int run_local(tfidf_ctx* ctx, const CorpusDev& c, const uint32_t* dev_ids
             ctx->k1out_valid = true;
         }
         LCHK(launch_tokcount_sl(c, ctx->chunk_start.as<uint64_t>(), ctx->chunk_doc.as<uint32_t>(), 0, nchunks, vd,
-                                ctx->k1out_dev.as<K1Out>(), s));
+                                ctx->k1out_dev.as<K1Out>(), s, ctx_ncu(ctx), &k1_wgs));
     } else if (nchunks && ctx->k1_vs)
-        LCHK(launch_tokcount_vs(c, ctx->chunk_start.as<uint64_t>(), ctx->chunk_doc.as<uint32_t>(), 0, nchunks, vd, o, s));
-    else if (nchunks)
+        LCHK(launch_tokcount_vs(c, ctx->chunk_start.as<uint64_t>(), ctx->chunk_doc.as<uint32_t>(), 0, nchunks, vd, o, s,
+                                ctx_ncu(ctx), &k1_wgs));
+    else if (nchunks) {
         LCHK(launch_tokcount(c, ctx->chunk_start.as<uint64_t>(), ctx->chunk_doc.as<uint32_t>(), 0, nchunks, vd, o, s));
+        k1_wgs = (uint32_t)nchunks;
+    }
+    ctx->k1_workgroups = k1_wgs;
     mark(ctx, S_VOCAB);
     /* the vocabulary's used-slot flags and count are enqueued before the host reads K1's
      * counters: one host round trip for both */
@@ -1455,7 +1462,7 @@ static int run_post(tfidf_ctx* ctx, uint64_t Nt) {
     a.out_term = ctx->out_term.as<uint32_t>();
     a.out_cnt = ctx->out_cnt.as<uint32_t>();
     a.out_score = ctx->out_score.as<double>();
-    XCHK(launch_score_order(a, ar, s, ctx->stream2, ctx->ev_fork, ctx->ev_order));
+    XCHK(launch_score_order(a, ar, s, ctx->stream2, ctx->ev_fork, ctx->ev_order, ctx_ncu(ctx)));
     mark(ctx, S_NSTAGES);
     {   /* the final status, the pair total and (with a transport) global V: one launch */
         WordList wl{};
@@ -1738,6 +1745,7 @@ extern "C" int tfidf_last_run_info(tfidf_ctx* ctx, tfidf_run_info* out) {
     info->idf_logs = ctx->idf_logs;
     info->ms_idf_host = ctx->ms_idf_host;
     info->ms_idf_wait = ctx->ms_idf_wait;
+    info->k1_workgroups = ctx->k1_workgroups;
     full.size = want;
     memcpy(out, &full, want);
     return TFIDF_OK;
@@ -1951,7 +1959,7 @@ static int format_prepare(tfidf_ctx* ctx, EmitLaunch& e, uint64_t& total) {
                    status};
     total = 0;
     if (N) {
-        if (launch_emit_bytes(e, ctx->doc_tbytes.as<uint64_t>(), s)) return TFIDF_E_HIP;
+        if (launch_emit_bytes(e, ctx->doc_tbytes.as<uint64_t>(), s, ctx_ncu(ctx))) return TFIDF_E_HIP;
         ctx->arena.used = 0;
         if (scan_excl_u64(ctx->doc_tbytes.as<uint64_t>(), ctx->doc_toff.as<uint64_t>(), N, ctx->arena, s))
             return TFIDF_E_HIP;
@@ -1986,7 +1994,8 @@ extern "C" int tfidf_format(tfidf_ctx* ctx, uint64_t* nbytes) {
     uint64_t total = 0;
     int rc = format_prepare(ctx, e, total);
     if (rc) return rc;
-    if (total && launch_emit_write(e, ctx->doc_toff.as<uint64_t>(), ctx->text.as<uint8_t>(), ctx->stream))
+    if (total && launch_emit_write(e, ctx->doc_toff.as<uint64_t>(), ctx->text.as<uint8_t>(), ctx->stream, 0, 0xFFFFFFFFu,
+                                   ctx_ncu(ctx)))
         return TFIDF_E_HIP;
     rc = format_finish(ctx, total);
     if (!rc) *nbytes = total;
@@ -2056,7 +2065,7 @@ extern "C" int tfidf_write_output_gpu(tfidf_ctx* ctx, const char* path, int appe
             const uint32_t d0 = (uint32_t)((uint64_t)N * g / ng), d1 = (uint32_t)((uint64_t)N * (g + 1) / ng);
             gb[g] = toff[d0];
             gb[g + 1] = toff[d1];
-            if (launch_emit_write(e, ctx->doc_toff.as<uint64_t>(), ctx->text.as<uint8_t>(), s, d0, d1))
+            if (launch_emit_write(e, ctx->doc_toff.as<uint64_t>(), ctx->text.as<uint8_t>(), s, d0, d1, ctx_ncu(ctx)))
                 return TFIDF_E_HIP;
             HIPCHK(hipEventRecord(ctx->wr_fmt[g], s));
         }

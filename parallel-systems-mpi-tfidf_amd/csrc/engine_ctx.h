@@ -20,7 +20,8 @@
  *   engine_nb.cpp         tfidf_nb_fit, tfidf_nb_predict, tfidf_nb_predict_rows, tfidf_nb_export
  *                         (nb.hip; the check and the host twin: nb_host.c)
  * The add-on calls run between runs on the context's stream and use the run's arena as scratch
- * only; none of them is on the path tfidf_run times.
+ * only; none of them is on the path tfidf_run times.  The add-on launches and the run's own
+ * persistent kernels alike take their CU count from ctx_ncu below.
  */
 #ifndef TFIDF_ENGINE_CTX_H
 #define TFIDF_ENGINE_CTX_H
@@ -250,7 +251,7 @@ struct tfidf_ctx {
     uint64_t kmeans_bytes = 1024ull << 20;      /* env TFIDF_KMEANS_MB: budget of km_C + km_work */
     uint32_t kmeans_split = 0;                  /* env TFIDF_KMEANS_SPLIT: update workgroups per cluster (0: fill the GPU) */
     uint32_t an_grid = 0;                       /* env TFIDF_AN_GRID: at most that many workgroups of the analyzer's tile kernel (0: the resident ones) */
-    uint32_t grid_cus = 0;                      /* env TFIDF_GRID_CUS: the CU count `ncu` takes in place of the device's (0: the device's) */
+    uint32_t grid_cus = 0;                      /* env TFIDF_GRID_CUS: the CU count `ncu` takes in place of the device's (0: the device's), for the run's kernels too */
     hipEvent_t ev_k[4] = {};                    /* assign / update / top-term bounds (created by the first call) */
     tfidf_kmeans_info kinfo{};
     /* unseen documents against the resident model (tfidf_transform, transform.hip): a host
@@ -356,6 +357,7 @@ struct tfidf_ctx {
     const uint32_t* dev_ids = nullptr;
     uint64_t npairs = 0, ntokens = 0, nchunks = 0, nrec_part = 0, ndocs_total = 0;
     uint32_t ndocs = 0, V = 0, Vg = 0;
+    uint32_t k1_workgroups = 0;   /* the grid of the last K1 launch (0: none was launched) */
     double ms_stage[S_NSTAGES] = {0};
     double ms_total = 0;
     hipError_t last_err = hipSuccess;
@@ -436,8 +438,9 @@ static inline size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 /* ---- what every add-on call starts and ends with ---- */
 
-/* the CU count the launches over the result are sized by (kernels.h, *_WG_PER_CU): env
- * TFIDF_GRID_CUS when it was set at tfidf_open, else the device's; settled once per context */
+/* the CU count the launches over the result (kernels.h, *_WG_PER_CU) and the run's own persistent
+ * kernels (K1, the score stage, emit.hip) are sized by: env TFIDF_GRID_CUS when it was set at
+ * tfidf_open, else the device's; settled once per context */
 static inline uint32_t ctx_ncu(tfidf_ctx* ctx) {
     if (!ctx->ncu) {
         int n = 0;

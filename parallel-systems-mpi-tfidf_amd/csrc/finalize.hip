@@ -2176,7 +2176,7 @@ static void launch_score_large(const K5Args& a, uint32_t grid, hipStream_t s) {
     }
 }
 int launch_score_order(const K5Args& a, Arena& ar, hipStream_t s, hipStream_t s2, hipEvent_t ev_fork,
-                       hipEvent_t ev_join) {
+                       hipEvent_t ev_join, uint32_t ncu_ctx) {
     if (!a.ndocs) return 0;
     {   /* the handed-off list's and the chunk tasks' counters, one launch */
         FillList fl{};
@@ -2193,13 +2193,14 @@ int launch_score_order(const K5Args& a, Arena& ar, hipStream_t s, hipStream_t s2
     if (!a.idf_by_df)
         k_idf_of_rank<<<grid_for(a.nterms ? a.nterms : 1), NT, 0, s>>>(a.df_of_rank, a.idf_idx, a.idf, a.nterms,
                                                                       a.idf_rank);
-    static int ncu = 0;
-    if (!ncu) {
+    static int ncu_dev = 0;   /* the device's, for a caller that passes no count */
+    if (!ncu_ctx && !ncu_dev) {
         int dev = 0;
         if (hipGetDevice(&dev) != hipSuccess ||
-            hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || ncu <= 0)
-            ncu = 256;
+            hipDeviceGetAttribute(&ncu_dev, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || ncu_dev <= 0)
+            ncu_dev = 256;
     }
+    const int ncu = ncu_ctx ? (int)ncu_ctx : ncu_dev;
     const uint32_t wg_need = (a.ndocs + NT / 64 - 1) / (NT / 64);
     const bool wide = a.rank_bits + K5_IDX_BITS > 32;
     const uint32_t wg_cu = wide ? (uint32_t)K5_WPS_WIDE : 4u;   /* 40 KB LDS: 4 per CU; wide: its registers */

@@ -115,10 +115,15 @@ int launch_plan_chunks(const CorpusDev& c, uint64_t nchunks, uint32_t chunk_byte
 int launch_tokcount(const CorpusDev& c, const uint64_t* chunk_start, const uint32_t* chunk_doc,
                     uint64_t c0, uint64_t c1, const VocabDev& v, const K1Out& o, hipStream_t s);
 
+/* The two persistent K1 kernels below launch min(chunks, ncu * 4) workgroups that claim chunks
+ * from a global counter.  ncu: the context's CU count (ctx_ncu: the device's, or env
+ * TFIDF_GRID_CUS), 0: the launcher asks the device; *grid (when not null) receives the
+ * workgroups launched (0: none). */
 /* K1 round-1 path (tokcount_vs.hip): 16-byte aligned corpus base; returns -3 when the
  * vocabulary capacity exceeds the LDS entry's slot field */
 int launch_tokcount_vs(const CorpusDev& c, const uint64_t* chunk_start, const uint32_t* chunk_doc, uint64_t c0,
-                       uint64_t c1, const VocabDev& v, const K1Out& o, hipStream_t s);
+                       uint64_t c1, const VocabDev& v, const K1Out& o, hipStream_t s, uint32_t ncu = 0,
+                       uint32_t* grid = nullptr);
 #define K1_VS_MAX_CAP (1ull << 28)
 
 #define K1_ST_MAX_CAP (1ull << 22)   /* tokcount_sl past this vocabulary capacity: half-size chunks */
@@ -128,7 +133,8 @@ int launch_tokcount_vs(const CorpusDev& c, const uint64_t* chunk_start, const ui
  * block is read from device memory (o_dev: a K1Out the engine copies there per run).
  * 16-byte aligned corpus base; -3 when the vocabulary exceeds K1_SL_MAX_CAP slots */
 int launch_tokcount_sl(const CorpusDev& c, const uint64_t* chunk_start, const uint32_t* chunk_doc, uint64_t c0,
-                       uint64_t c1, const VocabDev& v, const K1Out* o_dev, hipStream_t s);
+                       uint64_t c1, const VocabDev& v, const K1Out* o_dev, hipStream_t s, uint32_t ncu = 0,
+                       uint32_t* grid = nullptr);
 
 
 /* vocabulary finalisation */
@@ -243,8 +249,10 @@ struct K5Args {
     uint32_t* out_cnt;           /*               wordCount */
     double* out_score;           /*               tf * idf */
 };
+/* ncu sizes the persistent score kernels (k_score_small, the wave kernel, the chunk tasks): the
+ * context's CU count, 0: the launcher asks the device */
 int launch_score_order(const K5Args& a, Arena& ar, hipStream_t s, hipStream_t s2, hipEvent_t ev_fork,
-                       hipEvent_t ev_join);
+                       hipEvent_t ev_join, uint32_t ncu = 0);
 
 /* multi-GPU vocabulary agreement */
 int launch_keys_by_rank(const uint4* vkeys, const uint32_t* slot_of_rank, uint32_t V, uint4* out, hipStream_t s);
@@ -348,10 +356,12 @@ struct EmitLaunch {
 };
 int launch_term_meta(const uint4* vkeys, const uint64_t* vrep, const uint32_t* slot_of_rank, uint32_t V,
                      uint4* tkey, uint32_t* tlen, hipStream_t s);
-int launch_emit_bytes(const EmitLaunch& e, uint64_t* doc_bytes, hipStream_t s);
+/* both take min(documents / 4, ncu * 8) workgroups of four waves, a wave per document, that
+ * stride over the documents; ncu: the context's CU count, 0: the launcher asks the device */
+int launch_emit_bytes(const EmitLaunch& e, uint64_t* doc_bytes, hipStream_t s, uint32_t ncu = 0);
 /* formats the output positions [d0, d1) (default: all) */
 int launch_emit_write(const EmitLaunch& e, const uint64_t* doc_text, uint8_t* text, hipStream_t s, uint32_t d0 = 0,
-                      uint32_t d1 = 0xFFFFFFFFu);
+                      uint32_t d1 = 0xFFFFFFFFu, uint32_t ncu = 0);
 int launch_format_f64(const double* v, uint64_t n, uint8_t* out, uint32_t* status, hipStream_t s);
 
 /* ---- grids of the launches over the resident result ----
@@ -359,7 +369,9 @@ int launch_format_f64(const double* v, uint64_t n, uint8_t* out, uint32_t* statu
  * context's CU count (call_begin: the device's, or env TFIDF_GRID_CUS).  The launches that take
  * one workgroup per big document (over QS_BIG / RW_BIG pairs) are bounded by BIG_WG_MAX as well:
  * from BIG_WG_MAX / BIG_WG_PER_CU = 64 CUs on that bound alone holds.  tests/stride_corpus.py reads
- * these to size a corpus on which every such loop makes several trips. */
+ * these to size a corpus on which every such loop makes several trips.  The run's own persistent
+ * kernels (launch_tokcount_sl / _vs, launch_score_order, launch_emit_bytes / _write) take the same
+ * count as their ncu argument; tests/run_stride_corpus.py is their corpus. */
 #define QS_WG_PER_CU       3u  /* k_doc_score (query, BM25): ~52 KiB of LDS each */
 #define SM_WG_PER_CU       8u  /* k_sim_score: no LDS, the waves a CU holds */
 #define KM_WG_PER_CU       8u  /* k_km_assign: as k_sim_score */

@@ -1158,22 +1158,25 @@ __global__ __launch_bounds__(NT, WG_PER_CU * NT / 256) void k_tokcount_sl(Corpus
 }
 
 int launch_tokcount_sl(const CorpusDev& c, const uint64_t* chunk_start, const uint32_t* chunk_doc, uint64_t c0,
-                       uint64_t c1, const VocabDev& v, const K1Out* o_dev, hipStream_t s) {
+                       uint64_t c1, const VocabDev& v, const K1Out* o_dev, hipStream_t s, uint32_t ncu_ctx,
+                       uint32_t* grid_out) {
+    if (grid_out) *grid_out = 0;
     if (c1 <= c0) return 0;
     if (v.mask >= (1ull << SLOT_BITS)) return -3;
     static_assert(sizeof(SlShared) * WG_PER_CU <= 163840, "LDS of WG_PER_CU workgroups per CU");
     static_assert(TB % NT == 0 && TB % BW == 0, "table rows");
     const uint32_t sbits = (uint32_t)__builtin_popcountll(v.mask);
     const uint32_t gcap = (1u << (31u - sbits)) >= (uint32_t)GCAP ? (uint32_t)GCAP : (1u << (31u - sbits));
-    static int ncu = 0;
-    if (!ncu) {
+    static int ncu = 0;   /* the device's, for a caller that passes no count */
+    if (!ncu_ctx && !ncu) {
         int dev = 0;
         if (hipGetDevice(&dev) != hipSuccess ||
             hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || ncu <= 0)
             ncu = 256;
     }
-    const uint64_t wgs = (uint64_t)ncu * WG_PER_CU;
+    const uint64_t wgs = (uint64_t)(ncu_ctx ? ncu_ctx : (uint32_t)ncu) * WG_PER_CU;
     const uint64_t grid = (c1 - c0) < wgs ? (c1 - c0) : wgs;
+    if (grid_out) *grid_out = (uint32_t)grid;
     /* Past K1_ST_MAX_CAP slots nearly every token is a new pair and every group runs into
      * overflow mode: the preferred-slot count has few hits to settle there, and the keys still
      * deferred when the budget is crossed turn earlier documents into partial records (c4:

@@ -633,11 +633,13 @@ __global__ __launch_bounds__(NT, K1_WAVES_PER_SIMD) void k_tokcount_vs(CorpusDev
 }
 
 int launch_tokcount_vs(const CorpusDev& c, const uint64_t* chunk_start, const uint32_t* chunk_doc, uint64_t c0,
-                       uint64_t c1, const VocabDev& v, const K1Out& o, hipStream_t s) {
+                       uint64_t c1, const VocabDev& v, const K1Out& o, hipStream_t s, uint32_t ncu_ctx,
+                       uint32_t* grid_out) {
+    if (grid_out) *grid_out = 0;
     if (c1 <= c0) return 0;
     if (v.mask >= (1ull << SLOT_BITS)) return -3; /* slot must fit the LDS entry */
-    static int ncu = 0;
-    if (!ncu) {
+    static int ncu = 0;   /* the device's, for a caller that passes no count */
+    if (!ncu_ctx && !ncu) {
         int dev = 0;
         if (hipGetDevice(&dev) != hipSuccess ||
             hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || ncu <= 0)
@@ -646,8 +648,9 @@ int launch_tokcount_vs(const CorpusDev& c, const uint64_t* chunk_start, const ui
 #ifndef K1_WGS_PER_CU
 #define K1_WGS_PER_CU 4
 #endif
-    const uint64_t wgs = (uint64_t)ncu * K1_WGS_PER_CU;
+    const uint64_t wgs = (uint64_t)(ncu_ctx ? ncu_ctx : (uint32_t)ncu) * K1_WGS_PER_CU;
     const uint64_t grid = (c1 - c0) < wgs ? (c1 - c0) : wgs;
+    if (grid_out) *grid_out = (uint32_t)grid;
     k_tokcount_vs<<<(unsigned)grid, NT, 0, s>>>(c, chunk_start, chunk_doc, c0, c1, v, o);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }

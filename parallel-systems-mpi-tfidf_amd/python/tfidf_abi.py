@@ -124,6 +124,7 @@ class RunInfo(C.Structure):
         ("ms_tokcount", C.c_double), ("ms_stage", C.c_double * 16), ("nstages", C.c_uint32), ("flags", C.c_uint32),
         ("device_allocs", C.c_uint64), ("device_alloc_bytes", C.c_uint64),
         ("idf_logs", C.c_uint64), ("ms_idf_host", C.c_double), ("ms_idf_wait", C.c_double),
+        ("k1_workgroups", C.c_uint32), ("reserved2", C.c_uint32),
     ]
 
 
@@ -1236,10 +1237,12 @@ class Engine:
         return {k: getattr(t, k) for k, _ in RunTotals._fields_}
 
     def info(self) -> dict:
+        """Counters of the last run (tfidf_last_run_info); k1_workgroups is the grid of its last
+        tokenize+count launch."""
         r = RunInfo()
         r.size = C.sizeof(RunInfo)
         _chk(lib().tfidf_last_run_info(self.h, C.byref(r)), "tfidf_last_run_info")
-        d = {k: getattr(r, k) for k, _ in RunInfo._fields_ if k not in ("ms_stage", "size")}
+        d = {k: getattr(r, k) for k, _ in RunInfo._fields_ if k not in ("ms_stage", "size", "reserved2")}
         d["stages"] = {lib().tfidf_stage_name(i).decode(): r.ms_stage[i] for i in range(r.nstages)}
         return d
 

@@ -8,6 +8,8 @@ accumulators, a barrier before shared words are rewritten, a `continue` in front
 document, per-document minima) ran untested.  With one CU every loop here makes 3 to 67 trips
 (test_stride_corpus_cpu.py establishes that, and the transitions a wave meets, without a GPU).
 The references know nothing of the grid, so equality at every setting is grid independence.
+tfidf_run's own persistent kernels follow the same count, so the result each setting starts from is
+built at the small grid too (test_gpu_run_stride.py is the run's own test).
 
 All comparisons are exact: integers, u64 bit patterns of doubles, bytes."""
 import ctypes as C
