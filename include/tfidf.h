@@ -229,6 +229,10 @@ typedef struct tfidf_run_totals {
 int tfidf_run_totals_get(tfidf_ctx* ctx, tfidf_run_totals* out, int reset);
 /* The same device-allocation counters without a run (process-wide, cumulative). */
 int tfidf_alloc_stats(uint64_t* allocs, uint64_t* bytes);
+/* The engine's device allocations that are still held: allocations minus frees, and their bytes
+ * (process-wide).  Equal before tfidf_open and after tfidf_close of every context and group: a
+ * closed context leaves no device memory behind. */
+int tfidf_alloc_live(uint64_t* allocs, uint64_t* bytes);
 /* The CU count the context sizes its launches over the resident result by (tfidf_query,
  * _query_bm25, _top_terms, _similar, _kmeans, _prune, _reweight, _transform's row norm, _minhash,
  * _near_dups; tfidf_analyze's tile kernel too): each takes min(work, CUs x a per-kernel constant)

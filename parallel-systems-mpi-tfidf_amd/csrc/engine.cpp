@@ -31,6 +31,7 @@
 #include <atomic>
 #include <chrono>
 #include <condition_variable>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <thread>
@@ -42,6 +43,7 @@
 #include "analyze_tab.h"
 #include "synth.h"
 #include "xport.h"
+#include "knobs.h"
 #include "engine_ctx.h"
 
 extern "C" void tfidf_synth_spec(syn_spec* s, uint64_t seed, uint32_t V, uint32_t mode, const double* cdf);
@@ -49,8 +51,10 @@ extern "C" void tfidf_synth_spec(syn_spec* s, uint64_t seed, uint32_t V, uint32_
 namespace {
 
 /* every device allocation of the engine goes through dev_malloc: the counters behind
- * tfidf_run_info.device_allocs / device_alloc_bytes (a steady-state run makes none) */
+ * tfidf_run_info.device_allocs / device_alloc_bytes (a steady-state run makes none); and every
+ * release of one through dev_free: allocations minus frees is tfidf_alloc_live */
 std::atomic<uint64_t> g_dev_allocs{0}, g_dev_alloc_bytes{0};
+std::atomic<uint64_t> g_dev_frees{0}, g_dev_free_bytes{0};
 
 }  // namespace
 
@@ -61,6 +65,12 @@ hipError_t tfidf_dev_malloc(void** p, size_t bytes) {
         g_dev_alloc_bytes.fetch_add(bytes, std::memory_order_relaxed);
     }
     return e;
+}
+void tfidf_dev_free(void* p, size_t bytes) {
+    if (!p) return;
+    (void)hipFree(p);
+    g_dev_frees.fetch_add(1, std::memory_order_relaxed);
+    g_dev_free_bytes.fetch_add(bytes, std::memory_order_relaxed);
 }
 
 namespace {
@@ -73,6 +83,16 @@ static bool idf_done(tfidf_ctx* ctx);
 /* open contexts in this process: the idf workers of all of them share IDF_POOL threads' worth
  * of work (a group of K shards in one process would otherwise start 8 K of them) */
 static std::atomic<int> g_live_ctx{0};
+
+/* what needs an order; the members release the rest (engine_ctx.h) */
+tfidf_ctx::~tfidf_ctx() {
+    (void)hipSetDevice(device);
+    for (Stream* st : {&stream, &stream2, &stream3})
+        if (*st) (void)hipStreamSynchronize(*st);
+    delete xp;
+    idf_pool_stop(this);   /* the workers write into idf_pin */
+    if (live) g_live_ctx.fetch_sub(1);
+}
 
 /* a wait for the run's stream once collectives may be in it: through the transport, so
  * that a failed peer cannot leave this rank waiting (xport.h, comm_rank.h) */
@@ -148,17 +168,14 @@ int tfidf_open(int device, tfidf_ctx** out) {
         return TFIDF_E_NODEV;
     }
     if (hipSetDevice(device) != hipSuccess) return TFIDF_E_NODEV;
-    tfidf_ctx* ctx = new tfidf_ctx();
+    /* owned here until the last step: every failure return below deletes it, and the context
+     * releases what it had got by then */
+    std::unique_ptr<tfidf_ctx> ctx(new tfidf_ctx());
     ctx->device = device;
     const char* km = getenv("TFIDF_K1");
     if (km && !strcmp(km, "general")) ctx->k1_mode = 2;
     if (km && !strcmp(km, "vs")) ctx->k1_mode = 1;
     if (km && !strcmp(km, "sl")) ctx->k1_mode = 3;
-    {
-        const char* sm = getenv("TFIDF_SL_MAXCAP");
-        const unsigned long long v = sm ? strtoull(sm, nullptr, 0) : 0ull;
-        if (v >= 1024 && v <= K1_SL_MAX_CAP) ctx->sl_maxcap = v;
-    }
     const char* ks = getenv("TFIDF_STAMPS");
     ctx->stamps_on = ks && ks[0] == '1';
     const char* kx = getenv("TFIDF_TEST_XFAIL_RANK");
@@ -173,195 +190,50 @@ int tfidf_open(int device, tfidf_ctx** out) {
     ctx->xb_stage_max = kxb ? (uint32_t)atoi(kxb) : ~0u;
     const char* kds = getenv("TFIDF_DF_SPLIT");
     ctx->df_split = !(kds && !strcmp(kds, "0"));
-    const char* kq = getenv("TFIDF_QUERY_ACC_MB");
-    if (kq) {
-        const unsigned long long mb = strtoull(kq, nullptr, 0);
-        if (mb >= 1 && mb <= (1ull << 20)) ctx->query_acc_bytes = mb << 20;
-    }
-    const char* kt = getenv("TFIDF_TERMS_MB");
-    if (kt) {
-        const unsigned long long mb = strtoull(kt, nullptr, 0);
-        if (mb >= 1 && mb <= (1ull << 20)) ctx->terms_bytes = mb << 20;
-    }
-    const char* ktr = getenv("TFIDF_TRANSFORM_MB");
-    if (ktr) {
-        const unsigned long long mb = strtoull(ktr, nullptr, 0);
-        if (mb >= 1 && mb <= (1ull << 20)) ctx->transform_bytes = mb << 20;
-    }
-    const char* kdd = getenv("TFIDF_DEDUP_MB");
-    if (kdd) {
-        const unsigned long long mb = strtoull(kdd, nullptr, 0);
-        if (mb >= 1 && mb <= (1ull << 20)) ctx->dedup_bytes = mb << 20;
-    }
-    const char* knb = getenv("TFIDF_NB_MB");
-    if (knb) {
-        const unsigned long long mb = strtoull(knb, nullptr, 0);
-        if (mb >= 1 && mb <= (1ull << 20)) ctx->nb_bytes = mb << 20;
-    }
-    const char* kkm = getenv("TFIDF_KMEANS_MB");
-    if (kkm) {
-        const unsigned long long mb = strtoull(kkm, nullptr, 0);
-        if (mb >= 1 && mb <= (1ull << 20)) ctx->kmeans_bytes = mb << 20;
-    }
-    const char* kks = getenv("TFIDF_KMEANS_SPLIT");
-    if (kks) {
-        const unsigned long sp = strtoul(kks, nullptr, 0);
-        if (sp >= 1 && sp <= 1024) ctx->kmeans_split = (uint32_t)sp;
-    }
-    const char* kag = getenv("TFIDF_AN_GRID");
-    if (kag) {
-        const unsigned long ag = strtoul(kag, nullptr, 0);
-        if (ag >= 1 && ag <= 65536) ctx->an_grid = (uint32_t)ag;
-    }
-    const char* kgc = getenv("TFIDF_GRID_CUS");
-    if (kgc) {
-        const unsigned long gc = strtoul(kgc, nullptr, 0);
-        if (gc >= 1 && gc <= 4096) ctx->grid_cus = (uint32_t)gc;
-    }
     const char* kn = getenv("TFIDF_TEST_XNOMEM_RANK");
     ctx->xnomem_rank = kn ? atoi(kn) : -1;
-    /* diagnostics: initial vocabulary capacity (power of two) and the loads it may reach
-     * before the run is repeated with a larger table (TFIDF_VLOAD percent below 16M slots,
-     * default 12; TFIDF_VLOAD_BIG from 16M slots on, default 45) */
-    const char* kv = getenv("TFIDF_VCAP");
-    if (kv) {
-        uint64_t c = strtoull(kv, nullptr, 0);
-        if (c >= 1024 && (c & (c - 1)) == 0) ctx->vcap = c;
+    /* the numeric range knobs (knobs.h): unset or rejected, the member's default stays */
+    static_assert(K1_SL_MAX_CAP == 1ull << 25, "knobs.h: TFIDF_SL_MAXCAP's upper bound");
+    for (int i = 0; i < KNOB_COUNT; ++i) {
+        uint64_t v = 0;
+        if (!knob_parse(kKnobs[i], getenv(kKnobs[i].name), &v)) continue;
+        switch (i) {
+            case KNOB_SL_MAXCAP: ctx->sl_maxcap = v; break;
+            case KNOB_QUERY_ACC_MB: ctx->query_acc_bytes = v; break;
+            case KNOB_TERMS_MB: ctx->terms_bytes = v; break;
+            case KNOB_TRANSFORM_MB: ctx->transform_bytes = v; break;
+            case KNOB_DEDUP_MB: ctx->dedup_bytes = v; break;
+            case KNOB_NB_MB: ctx->nb_bytes = v; break;
+            case KNOB_KMEANS_MB: ctx->kmeans_bytes = v; break;
+            case KNOB_KMEANS_SPLIT: ctx->kmeans_split = (uint32_t)v; break;
+            case KNOB_AN_GRID: ctx->an_grid = (uint32_t)v; break;
+            case KNOB_GRID_CUS: ctx->grid_cus = (uint32_t)v; break;
+            case KNOB_VCAP: ctx->vcap = v; break;
+            case KNOB_VLOAD_BIG: ctx->vload_big_pct = (uint32_t)v; break;
+            case KNOB_VLOAD: ctx->vload_pct = (uint32_t)v; break;
+        }
     }
-    const char* kb = getenv("TFIDF_VLOAD_BIG");
-    if (kb) {
-        uint32_t l = (uint32_t)strtoul(kb, nullptr, 0);
-        if (l >= 10 && l <= 90) ctx->vload_big_pct = l;
-    }
-    const char* kl = getenv("TFIDF_VLOAD");
-    if (kl) {
-        uint32_t l = (uint32_t)strtoul(kl, nullptr, 0);
-        if (l >= 10 && l <= 90) ctx->vload_pct = l;
-    }
-    HIPCHK(hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking));
-    HIPCHK(hipStreamCreateWithFlags(&ctx->stream2, hipStreamNonBlocking));
-    HIPCHK(hipStreamCreateWithFlags(&ctx->stream3, hipStreamNonBlocking));
-    HIPCHK(hipEventCreateWithFlags(&ctx->ev_fork, hipEventDisableTiming));
-    HIPCHK(hipEventCreateWithFlags(&ctx->ev_order, hipEventDisableTiming));
-    HIPCHK(hipEventCreateWithFlags(&ctx->ev_spin, hipEventDisableTiming));
-    HIPCHK(hipEventCreateWithFlags(&ctx->ev_idf_up, hipEventDisableTiming));
-    HIPCHK(hipEventCreateWithFlags(&ctx->ev_vrank, hipEventDisableTiming));
-    HIPCHK(hipEventCreateWithFlags(&ctx->ev_dfmain, hipEventDisableTiming));
-    for (int i = 0; i <= S_NSTAGES; ++i) HIPCHK(hipEventCreate(&ctx->ev[i]));
-    if (arena_reset(ctx, 64ull << 20) != 0) { delete ctx; return TFIDF_E_NOMEM; }
-    if (ctx->counters.ensure(256) != 0) { delete ctx; return TFIDF_E_NOMEM; }
+    HIPCHK(ctx->stream.create());
+    HIPCHK(ctx->stream2.create());
+    HIPCHK(ctx->stream3.create());
+    for (Event* e : {&ctx->ev_fork, &ctx->ev_order, &ctx->ev_spin, &ctx->ev_idf_up, &ctx->ev_vrank, &ctx->ev_dfmain})
+        HIPCHK(e->create_untimed());
+    for (Event& e : ctx->ev) HIPCHK(e.create());
+    if (arena_reset(ctx.get(), 64ull << 20) != 0) return TFIDF_E_NOMEM;
+    if (ctx->counters.ensure(256) != 0) return TFIDF_E_NOMEM;
     /* coherent: the status words a kernel writes (and its completion token) reach the host
      * without a cache flush at the kernel's end */
-    if (hipHostMalloc((void**)&ctx->hpin, 256, hipHostMallocCoherent) != hipSuccess) { delete ctx; return TFIDF_E_NOMEM; }
-    if (hipHostGetDevicePointer((void**)&ctx->hpin_dev, ctx->hpin, 0) != hipSuccess || !ctx->hpin_dev) {
-        delete ctx;
-        return TFIDF_E_NOMEM;
-    }
-    if (hipHostMalloc((void**)&ctx->k1out_host, sizeof(K1Out), hipHostMallocDefault) != hipSuccess ||
-        ctx->k1out_dev.ensure(sizeof(K1Out)) != 0) { delete ctx; return TFIDF_E_NOMEM; }
+    if (ctx->hpin.alloc(256, hipHostMallocCoherent) != hipSuccess) return TFIDF_E_NOMEM;
+    if (hipHostGetDevicePointer((void**)&ctx->hpin_dev, ctx->hpin, 0) != hipSuccess || !ctx->hpin_dev) return TFIDF_E_NOMEM;
+    if (ctx->k1out_host.alloc(sizeof(K1Out)) != hipSuccess || ctx->k1out_dev.ensure(sizeof(K1Out)) != 0) return TFIDF_E_NOMEM;
     g_live_ctx.fetch_add(1);
-    *out = ctx;
+    ctx->live = true;
+    *out = ctx.release();
     return TFIDF_OK;
 }
 
 void tfidf_close(tfidf_ctx* ctx) {
-    if (!ctx) return;
-    (void)hipSetDevice(ctx->device);
-    (void)hipStreamSynchronize(ctx->stream);
-    delete ctx->xp;
-    if (ctx->stream2) { (void)hipStreamSynchronize(ctx->stream2); (void)hipStreamDestroy(ctx->stream2); }
-    if (ctx->stream3) { (void)hipStreamSynchronize(ctx->stream3); (void)hipStreamDestroy(ctx->stream3); }
-    if (ctx->ev_idf_up) (void)hipEventDestroy(ctx->ev_idf_up);
-    if (ctx->ev_vrank) (void)hipEventDestroy(ctx->ev_vrank);
-    if (ctx->ev_dfmain) (void)hipEventDestroy(ctx->ev_dfmain);
-    if (ctx->ev_fork) (void)hipEventDestroy(ctx->ev_fork);
-    if (ctx->ev_spin) (void)hipEventDestroy(ctx->ev_spin);
-    if (ctx->ev_order) (void)hipEventDestroy(ctx->ev_order);
-    idf_pool_stop(ctx);
-    g_live_ctx.fetch_sub(1);
-    if (ctx->idf_pin) (void)hipHostFree(ctx->idf_pin);
-    for (int i = 0; i < WR_NBUF; ++i) {
-        if (ctx->wr_buf[i]) (void)hipHostFree(ctx->wr_buf[i]);
-        if (ctx->wr_ev[i]) (void)hipEventDestroy(ctx->wr_ev[i]);
-    }
-    for (int i = 0; i < WR_GROUPS; ++i)
-        if (ctx->wr_fmt[i]) (void)hipEventDestroy(ctx->wr_fmt[i]);
-    ctx->arena2_buf.release();
-    ctx->df_scratch.release();
-    for (hipEvent_t e : ctx->ev_q)
-        if (e) (void)hipEventDestroy(e);
-    for (DevBuf* b : {&ctx->q_terms, &ctx->q_rank, &ctx->q_tab, &ctx->q_acc, &ctx->q_cnt, &ctx->q_big, &ctx->q_cand0,
-                      &ctx->q_cand1, &ctx->q_misc})
-        b->release();
-    for (hipEvent_t e : ctx->ev_t)
-        if (e) (void)hipEventDestroy(e);
-    for (DevBuf* b : {&ctx->tm_ids, &ctx->tm_rows, &ctx->tm_score, &ctx->tm_pair, &ctx->tm_term, &ctx->tm_cnt, &ctx->tm_woff,
-                      &ctx->tm_words, &ctx->tm_big})
-        b->release();
-    for (hipEvent_t e : ctx->ev_s)
-        if (e) (void)hipEventDestroy(e);
-    for (DevBuf* b : {&ctx->sm_norm, &ctx->sm_ids, &ctx->sm_rows, &ctx->sm_mask, &ctx->sm_cnt, &ctx->sm_off, &ctx->sm_pw,
-                      &ctx->sm_res, &ctx->sm_escore, &ctx->sm_xterm, &ctx->sm_xscore, &ctx->sm_xwoff, &ctx->sm_xwords,
-                      &ctx->sm_xoff})
-        b->release();
-    for (hipEvent_t e : ctx->ev_k)
-        if (e) (void)hipEventDestroy(e);
-    for (DevBuf* b : {&ctx->km_C, &ctx->km_work, &ctx->km_top, &ctx->km_words}) b->release();
-    for (hipEvent_t e : ctx->ev_dd)
-        if (e) (void)hipEventDestroy(e);
-    for (DevBuf* b : {&ctx->dd_h0, &ctx->dd_sig, &ctx->dd_fam, &ctx->dd_misc, &ctx->dd_work}) b->release();
-    for (hipEvent_t e : ctx->ev_nb)
-        if (e) (void)hipEventDestroy(e);
-    for (DevBuf* b : {&ctx->nb_FC, &ctx->nb_W, &ctx->nb_work, &ctx->nb_lut, &ctx->nb_list, &ctx->nb_ids, &ctx->nb_rows,
-                      &ctx->nb_out})
-        b->release();
-    for (hipEvent_t e : ctx->ev_tr)
-        if (e) (void)hipEventDestroy(e);
-    for (DevBuf* b : {&ctx->tr_bytes, &ctx->tr_off, &ctx->tr_a, &ctx->tr_b}) b->release();
-    for (hipEvent_t e : ctx->ev_m)
-        if (e) (void)hipEventDestroy(e);
-    for (DevBuf* b : {&ctx->m_off, &ctx->m_blob, &ctx->m_stat}) b->release();
-    for (hipEvent_t e : ctx->ev_an)
-        if (e) (void)hipEventDestroy(e);
-    for (DevBuf* b : {&ctx->an_in, &ctx->an_bytes[0], &ctx->an_bytes[1], &ctx->an_off[0], &ctx->an_off[1], &ctx->an_ids[0],
-                      &ctx->an_ids[1], &ctx->an_dstart, &ctx->an_tab, &ctx->an_cnt})
-        b->release();
-    for (hipEvent_t e : ctx->ev_ng)
-        if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : ctx->ev_pr)
-        if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : ctx->ev_rw)
-        if (e) (void)hipEventDestroy(e);
-    for (DevBuf* b : {&ctx->rw_idf, &ctx->rw_lut, &ctx->rw_list, &ctx->rw_listv, &ctx->rw_big, &ctx->rw_misc}) b->release();
-    for (DevBuf* b : {&ctx->pr_flag, &ctx->pr_bits, &ctx->pr_k0, &ctx->pr_k1, &ctx->pr_v0, &ctx->pr_v1, &ctx->pr_tcnt,
-                      &ctx->pr_tdoc, &ctx->pr_misc, &ctx->pr_sor, &ctx->pr_df, &ctx->pr_term, &ctx->pr_cnt, &ctx->pr_score,
-                      &ctx->pr_off})
-        b->release();
-    for (DevBuf* b : {&ctx->ng_in, &ctx->ng_inoff, &ctx->ng_bytes[0], &ctx->ng_bytes[1], &ctx->ng_off[0], &ctx->ng_off[1],
-                      &ctx->ng_ids[0], &ctx->ng_ids[1], &ctx->ng_a, &ctx->ng_b, &ctx->ng_tseg})
-        b->release();
-    DevBuf* bufs[] = {&ctx->arena_buf, &ctx->in_bytes, &ctx->in_off, &ctx->in_ids, &ctx->syn_bytes, &ctx->syn_off,
-                      &ctx->syn_ids, &ctx->syn_ntok, &ctx->syn_blkfirst, &ctx->syn_blkbytes, &ctx->syn_cdf,
-                      &ctx->chunk_start, &ctx->chunk_doc, &ctx->vkeys, &ctx->vrep, &ctx->rec_slot, &ctx->rec_cnt,
-                      &ctx->part_doc, &ctx->part_slot, &ctx->part_cnt, &ctx->doc_recoff, &ctx->doc_npairs,
-                      &ctx->doc_size, &ctx->doc_flags, &ctx->counters, &ctx->dense, &ctx->vslot, &ctx->skey0,
-                      &ctx->skey1, &ctx->seq0, &ctx->seq1, &ctx->rank_of_slot, &ctx->slot_of_rank, &ctx->rank16, &ctx->pkey0,
-                      &ctx->pkey1, &ctx->pseq0, &ctx->pseq1, &ctx->phead, &ctx->df_local, &ctx->df_global,
-                      &ctx->present, &ctx->idf_vals, &ctx->dkey0, &ctx->dkey1, &ctx->dseq0, &ctx->dseq1,
-                      &ctx->npairs_ord, &ctx->out_off, &ctx->doc_meta, &ctx->t_key, &ctx->t_len, &ctx->doc_tbytes,
-                      &ctx->doc_toff, &ctx->text, &ctx->out_term, &ctx->out_cnt,
-                      &ctx->out_score, &ctx->idf_rank, &ctx->large_list, &ctx->split_tasks, &ctx->cls_off, &ctx->x_mine, &ctx->x_srec,
-                      &ctx->x_sidx, &ctx->x_back, &ctx->x_cnt, &ctx->x_rrec, &ctx->x_rslot, &ctx->x_reply, &ctx->x_gkeys,
-                      &ctx->x_pos, &ctx->x_dense, &ctx->x_lloc, &ctx->x_lsend, &ctx->x_lgath, &ctx->x_ltab,
-                      &ctx->x_tkey, &ctx->x_tdf, &ctx->stamps, &ctx->big_list, &ctx->big_idx, &ctx->dense_cnt, &ctx->kcnt,
-                      &ctx->tile_cnt};
-    for (DevBuf* b : bufs) b->release();
-    for (int i = 0; i <= S_NSTAGES; ++i) (void)hipEventDestroy(ctx->ev[i]);
-    if (ctx->hpin) (void)hipHostFree(ctx->hpin);
-    if (ctx->k1out_host) (void)hipHostFree(ctx->k1out_host);
-    ctx->k1out_dev.release();
-    (void)hipStreamDestroy(ctx->stream);
-    delete ctx;
+    if (ctx) delete ctx;   /* ~tfidf_ctx and its members' destructors: engine_ctx.h */
 }
 
 int tfidf_set_timing(tfidf_ctx* ctx, int enable) {
@@ -1289,14 +1161,7 @@ static int idf_start(tfidf_ctx* ctx, uint64_t Nt) {
     ctx->ms_idf_host = ctx->ms_idf_wait = 0;
     if (Nt > IDF_FULL_MAX) return TFIDF_OK;                          /* distinct-df path in run_post */
     if (const int q = idf_pin_quiesce(ctx)) return q;   /* a failed run left an upload of idf_pin unwaited */
-    const size_t n = (size_t)Nt + 1;
-    if (ctx->idf_pin_n < n) {
-        if (ctx->idf_pin) (void)hipHostFree(ctx->idf_pin);
-        ctx->idf_pin = nullptr;
-        ctx->idf_pin_n = 0;
-        if (hipHostMalloc((void**)&ctx->idf_pin, n * 8, hipHostMallocDefault) != hipSuccess) return TFIDF_E_NOMEM;
-        ctx->idf_pin_n = n;
-    }
+    if (idf_pin_reserve(ctx, (size_t)Nt + 1)) return TFIDF_E_NOMEM;
     ctx->idf_full_n = 0;   /* idf_vals is rewritten by this run */
     ctx->idf_pin[0] = 0.0;   /* df >= 1 for every term that occurs */
     idf_post(ctx, ctx->idf_pin, Nt, nullptr, Nt);
@@ -1389,14 +1254,7 @@ static int run_post(tfidf_ctx* ctx, uint64_t Nt) {
         ENSURE(ctx->idf_vals, (size_t)K * 8 + 8);
         /* the distinct df values' logs on the context's workers, into pinned memory */
         if (const int q = idf_pin_quiesce(ctx)) return q;   /* a failed run left an upload of idf_pin unwaited */
-        if (ctx->idf_pin_n < (size_t)K + 1) {
-            if (ctx->idf_pin) (void)hipHostFree(ctx->idf_pin);
-            ctx->idf_pin = nullptr;
-            ctx->idf_pin_n = 0;
-            if (hipHostMalloc((void**)&ctx->idf_pin, ((size_t)K + 1) * 8, hipHostMallocDefault) != hipSuccess)
-                return TFIDF_E_NOMEM;
-            ctx->idf_pin_n = (size_t)K + 1;
-        }
+        if (idf_pin_reserve(ctx, (size_t)K + 1)) return TFIDF_E_NOMEM;
         if (K) {
             if (K < 2 * 16384) {   /* one worker's share: on this thread, no hand-off and wake-up */
                 const auto t0 = std::chrono::steady_clock::now();
@@ -1559,16 +1417,7 @@ static int run_prepare(tfidf_ctx* ctx, const tfidf_corpus* in, CorpusDev& c, con
 
 extern "C" int tfidf_run(tfidf_ctx* ctx, const tfidf_corpus* in) {
     if (!ctx) return TFIDF_E_INVAL;
-    ctx->have_result = false;
-    ctx->have_model = false;   /* an imported model goes as a previous run's does */
-    ctx->model_only = false;
-    ctx->have_info = false;
-    ctx->text_valid = false;
-    ctx->tmeta_valid = false;
-    ctx->norm_valid = false;
-    ctx->h0_valid = false;
-    ctx->nb_valid = false;
-    ctx->bm25_L_valid = false;
+    result_changed(ctx, RC_SCORES | RC_TERMS | RC_NEW | RC_RUN);   /* an imported model goes as a previous run's does */
     CorpusDev c{};
     const uint32_t* dev_ids = nullptr;
     uint64_t Nt = 0;
@@ -1666,11 +1515,10 @@ extern "C" int tfidf_hbm_probe(tfidf_ctx* ctx, uint64_t nbytes, int iters, doubl
     HIPCHK(hipSetDevice(ctx->device));
     nbytes &= ~(uint64_t)4095;
     hipStream_t s = ctx->stream;
-    void *a = nullptr, *b = nullptr;
-    uint32_t* sink = nullptr;
-    if (tfidf_dev_malloc(&a, nbytes) != hipSuccess) return TFIDF_E_NOMEM;
-    if (tfidf_dev_malloc(&b, nbytes) != hipSuccess) { (void)hipFree(a); return TFIDF_E_NOMEM; }
-    if (tfidf_dev_malloc((void**)&sink, 256) != hipSuccess) { (void)hipFree(a); (void)hipFree(b); return TFIDF_E_NOMEM; }
+    DevBuf abuf, bbuf, sbuf;   /* released on every return */
+    if (abuf.exact(nbytes) || bbuf.exact(nbytes) || sbuf.exact(256)) return TFIDF_E_NOMEM;
+    void *a = abuf.p, *b = bbuf.p;
+    uint32_t* sink = sbuf.as<uint32_t>();
     int ncu = 256, dev = 0;
     if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
     const unsigned grid = (unsigned)(ncu > 0 ? ncu : 256) * 16u;
@@ -1698,9 +1546,6 @@ extern "C" int tfidf_hbm_probe(tfidf_ctx* ctx, uint64_t nbytes, int iters, doubl
     (void)hipEventDestroy(e0);
     (void)hipEventDestroy(e1);
     (void)hipStreamSynchronize(s);
-    (void)hipFree(a);
-    (void)hipFree(b);
-    (void)hipFree(sink);
     return rc;
 }
 
@@ -1714,6 +1559,13 @@ extern "C" int tfidf_alloc_stats(uint64_t* allocs, uint64_t* bytes) {
     if (!allocs || !bytes) return TFIDF_E_INVAL;
     *allocs = g_dev_allocs.load(std::memory_order_relaxed);
     *bytes = g_dev_alloc_bytes.load(std::memory_order_relaxed);
+    return TFIDF_OK;
+}
+
+extern "C" int tfidf_alloc_live(uint64_t* allocs, uint64_t* bytes) {
+    if (!allocs || !bytes) return TFIDF_E_INVAL;
+    *allocs = g_dev_allocs.load(std::memory_order_relaxed) - g_dev_frees.load(std::memory_order_relaxed);
+    *bytes = g_dev_alloc_bytes.load(std::memory_order_relaxed) - g_dev_free_bytes.load(std::memory_order_relaxed);
     return TFIDF_OK;
 }
 
@@ -1942,18 +1794,13 @@ extern "C" int tfidf_synth_device(tfidf_ctx* ctx, uint64_t seed, uint32_t V, uin
 static int format_prepare(tfidf_ctx* ctx, EmitLaunch& e, uint64_t& total) {
     HIPCHK(hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
-    const uint32_t N = ctx->ndocs, V = ctx->V;
+    const uint32_t N = ctx->ndocs;
     unsigned long long* cnt = ctx->counters.as<unsigned long long>();
     uint32_t* status = (uint32_t*)(cnt + 3);
     HIPCHK(hipMemsetAsync(status, 0, 4, s));
-    ENSURE(ctx->t_key, (size_t)V * 16 + 16);
-    ENSURE(ctx->t_len, (size_t)V * 4 + 4);
+    if (const int rc = ensure_term_meta(ctx)) return rc;
     ENSURE(ctx->doc_tbytes, ((size_t)N + 1) * 8);
     ENSURE(ctx->doc_toff, ((size_t)N + 1) * 8);
-    if (launch_term_meta(ctx->vkeys.as<uint4>(), ctx->vrep.as<uint64_t>(), ctx->slot_of_rank.as<uint32_t>(), V,
-                         ctx->t_key.as<uint4>(), ctx->t_len.as<uint32_t>(), s))
-        return TFIDF_E_HIP;
-    ctx->tmeta_valid = true;
     e = EmitLaunch{ctx->order, ctx->dev_ids, ctx->out_off.as<uint64_t>(), ctx->out_term.as<uint32_t>(),
                    ctx->out_score.as<double>(), ctx->t_key.as<uint4>(), ctx->t_len.as<uint32_t>(), ctx->dev_bytes, N,
                    status};
@@ -2021,14 +1868,13 @@ extern "C" int tfidf_copy_text(tfidf_ctx* ctx, uint64_t off, void* dst, uint64_t
 static int wr_ring_init(tfidf_ctx* ctx) {
     if (ctx->wr_buf[0]) return TFIDF_OK;
     for (int i = 0; i < WR_NBUF; ++i) {
-        if (hipHostMalloc((void**)&ctx->wr_buf[i], WR_BUF, hipHostMallocDefault) != hipSuccess) {
-            ctx->wr_buf[i] = nullptr;
-            for (int j = 0; j < i; ++j) { (void)hipHostFree(ctx->wr_buf[j]); ctx->wr_buf[j] = nullptr; }
+        if (ctx->wr_buf[i].alloc(WR_BUF) != hipSuccess) {
+            for (int j = 0; j < i; ++j) ctx->wr_buf[j].release();
             return TFIDF_E_NOMEM;
         }
     }
-    for (int i = 0; i < WR_NBUF; ++i) HIPCHK(hipEventCreateWithFlags(&ctx->wr_ev[i], hipEventDisableTiming));
-    for (int i = 0; i < WR_GROUPS; ++i) HIPCHK(hipEventCreateWithFlags(&ctx->wr_fmt[i], hipEventDisableTiming));
+    for (Event& e : ctx->wr_ev) HIPCHK(e.create_untimed());
+    for (Event& e : ctx->wr_fmt) HIPCHK(e.create_untimed());
     return TFIDF_OK;
 }
 
@@ -2190,8 +2036,8 @@ extern "C" int tfidf_format_f64(tfidf_ctx* ctx, const double* vals, uint64_t n, 
     if (!n) return TFIDF_OK;
     HIPCHK(hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
-    DevBuf v, o;
-    if (v.ensure(n * 8) || o.ensure(n * 32)) { v.release(); o.release(); return TFIDF_E_NOMEM; }
+    DevBuf v, o;   /* released on every return */
+    if (v.ensure(n * 8) || o.ensure(n * 32)) return TFIDF_E_NOMEM;
     unsigned long long* cnt = ctx->counters.as<unsigned long long>();
     uint32_t* status = (uint32_t*)(cnt + 3);
     uint32_t st = 0;
@@ -2203,8 +2049,6 @@ extern "C" int tfidf_format_f64(tfidf_ctx* ctx, const double* vals, uint64_t n, 
         hipMemcpyAsync(&st, status, 4, hipMemcpyDeviceToHost, s) != hipSuccess ||
         hipStreamSynchronize(s) != hipSuccess)
         rc = TFIDF_E_HIP;
-    v.release();
-    o.release();
     if (!rc && (st & ST_BOUNDS)) rc = TFIDF_E_INVAL;
     return rc;
 }

@@ -13,7 +13,7 @@
  *   engine_model.cpp      tfidf_model_export, tfidf_model_import
  *   engine_prune.cpp      tfidf_prune; ensure_spare
  *   engine_weight.cpp     tfidf_reweight (reweight.hip); the rw_* helpers tfidf_transform shares
- *   engine_terms.cpp      tfidf_top_terms
+ *   engine_terms.cpp      tfidf_top_terms; ensure_term_meta, lookup_ids
  *   engine_similar.cpp    tfidf_similar, the halves of tfidf_group_similar; sim_norms
  *   engine_kmeans.cpp     tfidf_kmeans
  *   engine_dedup.cpp      tfidf_minhash, tfidf_near_dups (dedup.hip; the groups: dedup_host.c)
@@ -22,6 +22,16 @@
  * The add-on calls run between runs on the context's stream and use the run's arena as scratch
  * only; none of them is on the path tfidf_run times.  The add-on launches and the run's own
  * persistent kernels alike take their CU count from ctx_ncu below.
+ *   devbuf.h              tfidf_dev_malloc / tfidf_dev_free and DevBuf (group.cpp's transports too)
+ *   knobs.h               the table of tfidf_open's numeric environment knobs and its parser
+ *
+ * Ownership: every member of tfidf_ctx that holds a device buffer, a stream, an event or pinned
+ * memory is of a type that releases it (DevBuf, Stream, Event, Pinned), so a member added to the
+ * context needs no line elsewhere: tfidf_close is `delete ctx`, and tfidf_open's failure returns
+ * leak nothing.  ~tfidf_ctx does only what needs an order.  tfidf_alloc_live (allocations minus
+ * frees of the process) is the test's check that nothing outlives a context.
+ * Invalidation: a call that changes the result says so once, through result_changed below, whose
+ * table lists every cache kept per result.
  */
 #ifndef TFIDF_ENGINE_CTX_H
 #define TFIDF_ENGINE_CTX_H
@@ -41,53 +51,61 @@
 #include "../../include/tfidf.h"
 #include "kernels.h"
 #include "xport.h"
+#include "devbuf.h"
 
-struct DevBuf {
-    void* p = nullptr;
-    size_t cap = 0;
-    int ensure(size_t bytes) {
-        if (bytes <= cap && p) return 0;
-        const bool regrow = p != nullptr;
-        if (p) { (void)hipFree(p); p = nullptr; cap = 0; }
-        /* 1/8 headroom (at least 4 KiB) on the first allocation, 1/2 on a regrowth: sizes
-         * that vary from run to run (the record totals after K1's overflow records, the
-         * partial-record sort buffers: K1's overflow mode depends on the order in which
-         * workgroups claim LDS entries) must not reallocate in steady state — hipFree
-         * synchronises the device and a 1 GB hipMalloc inside a stage left the GPU idle for
-         * ~0.7 ms (the bench counts allocations in its timed steps).  Near the HBM capacity
-         * the headroom is dropped rather than failing a size that fits exactly. */
-        const size_t head = regrow ? bytes / 2 : bytes / 8;
-        const size_t want = bytes < 256 ? 256 : bytes + (head > 4096 ? head : 4096);
-        if (tfidf_dev_malloc(&p, want) == hipSuccess) { cap = want; return 0; }
-        (void)hipGetLastError();
-        p = nullptr;
-        if (want != bytes && tfidf_dev_malloc(&p, bytes) == hipSuccess) { cap = bytes; return 0; }
-        (void)hipGetLastError();
-        p = nullptr;
-        return -1;
+/* ---- owning handles.  Each destroys what it holds when it holds something, so a member added to
+ * the context needs no line elsewhere: tfidf_close is `delete ctx`.  They convert to the raw
+ * handle, so the use sites read as they did with raw members. ---- */
+struct Stream {
+    hipStream_t s = nullptr;
+    Stream() = default;
+    Stream(const Stream&) = delete;
+    Stream& operator=(const Stream&) = delete;
+    ~Stream() { if (s) (void)hipStreamDestroy(s); }
+    operator hipStream_t() const { return s; }
+    hipError_t create() { return hipStreamCreateWithFlags(&s, hipStreamNonBlocking); }
+};
+/* one event; the calls' event sets are arrays of them (call_begin creates what is missing) */
+struct Event {
+    hipEvent_t e = nullptr;
+    Event() = default;
+    Event(const Event&) = delete;
+    Event& operator=(const Event&) = delete;
+    ~Event() { if (e) (void)hipEventDestroy(e); }
+    operator hipEvent_t() const { return e; }
+    hipError_t create() { return hipEventCreate(&e); }
+    hipError_t create_untimed() { return hipEventCreateWithFlags(&e, hipEventDisableTiming); }
+};
+/* pinned host memory */
+template <typename T> struct Pinned {
+    T* p = nullptr;
+    Pinned() = default;
+    Pinned(const Pinned&) = delete;
+    Pinned& operator=(const Pinned&) = delete;
+    ~Pinned() { release(); }
+    operator T*() const { return p; }
+    T* operator->() const { return p; }
+    /* `bytes` anew: what it held is freed first */
+    hipError_t alloc(size_t bytes, unsigned flags = hipHostMallocDefault) {
+        release();
+        const hipError_t e = hipHostMalloc((void**)&p, bytes, flags);
+        if (e != hipSuccess) p = nullptr;
+        return e;
     }
-    /* grow preserving the first `keep` bytes */
-    int grow_keep(size_t bytes, size_t keep, hipStream_t s) {
-        if (bytes <= cap && p) return 0;
-        void* q = nullptr;
-        if (tfidf_dev_malloc(&q, bytes) != hipSuccess) return -1;
-        if (p && keep) {
-            if (hipMemcpyAsync(q, p, keep, hipMemcpyDeviceToDevice, s) != hipSuccess) return -1;
-            if (hipStreamSynchronize(s) != hipSuccess) return -1;
-        }
-        if (p) (void)hipFree(p);
-        p = q;
-        cap = bytes;
-        return 0;
+    void release() {
+        if (p) (void)hipHostFree(p);
+        p = nullptr;
     }
-    void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
-    template <typename T> T* as() const { return (T*)p; }
 };
 enum Stage { S_PREP, S_TOKCOUNT, S_VOCAB, S_MERGE, S_DF, S_EXCHANGE, S_IDF, S_ORDER, S_SCORE, S_NSTAGES };
 
 struct tfidf_ctx {
+    /* engine.cpp: only what needs an order (the device, the three streams drained, xp, the idf
+     * workers, the live count); every member below releases what it owns by its own destructor */
+    ~tfidf_ctx();
+    bool live = false;      /* counted among the process's open contexts (tfidf_open's last step) */
     int device = 0;
-    hipStream_t stream = nullptr;
+    Stream stream;
     Xport* xp = nullptr;    /* peers of the DF exchange (RCCL or in-process); owned */
     int rank = 0, nranks = 1;
     int timing = 1;         /* tfidf_set_timing: 0 none, 1 every stage, 2 K1 and the whole run only */
@@ -106,25 +124,25 @@ struct tfidf_ctx {
     bool k1_vs = false;     /* last run used the slot-keyed kernel (default) */
     bool k1_sl = false;     /* ... or tokcount_sl (else tokcount_vs) */
     uint64_t sl_maxcap = K1_SL_MAX_CAP;   /* env TFIDF_SL_MAXCAP: tokcount_sl up to this many vocabulary slots */
-    K1Out* k1out_host = nullptr;   /* pinned: tokcount_sl's output block, copied to k1out_dev per run */
+    Pinned<K1Out> k1out_host;      /* pinned: tokcount_sl's output block, copied to k1out_dev per run */
     DevBuf k1out_dev;
     bool k1out_valid = false;      /* k1out_dev holds *k1out_host (the copy is skipped when a run's block is the same) */
-    hipEvent_t ev[S_NSTAGES + 1];
+    Event ev[S_NSTAGES + 1];
     Arena arena;
     DevBuf arena_buf;
     /* side stream: the document-order sort (needs only the document ids) runs beside the
      * vocabulary / merge / DF stages, after K1 (K1's persistent grid wants every CU) */
-    hipStream_t stream2 = nullptr;
-    hipEvent_t ev_fork = nullptr, ev_order = nullptr;
-    hipEvent_t ev_spin = nullptr;   /* the run's host waits (spin_sync) */
+    Stream stream2;
+    Event ev_fork, ev_order;
+    Event ev_spin;                  /* the run's host waits (spin_sync) */
     uint64_t wait_token = 0;        /* the last completion token of a status-words kernel (words_wait) */
-    hipStream_t stream3 = nullptr;  /* the idf table's upload, beside the merge / DF stages */
-    hipEvent_t ev_idf_up = nullptr;
+    Stream stream3;                 /* the idf table's upload, beside the merge / DF stages */
+    Event ev_idf_up;
     bool idf_early = false;         /* this run's table is on its way up stream3 (run_post waits on ev_idf_up) */
     /* split DF (runs with partial records): the main records' histogram runs on stream2
      * beside the merge stage, the merged records' is added on the main stream after it */
     bool df_split = true;           /* env TFIDF_DF_SPLIT=0: one DF pass after the merge */
-    hipEvent_t ev_vrank = nullptr, ev_dfmain = nullptr;
+    Event ev_vrank, ev_dfmain;
     DevBuf df_scratch;
     size_t df_scratch_min = 0;      /* grown when the split DF pass reported a shortfall (retried) */
     Arena arena2;
@@ -153,7 +171,7 @@ struct tfidf_ctx {
     /* pinned host words for the per-run device-to-host reads (corpus bounds, K1 counters,
      * final status): asynchronous copies on the stream and one synchronisation each, instead
      * of pageable or synchronous copies (two round trips per run saved) */
-    uint64_t* hpin = nullptr;
+    Pinned<uint64_t> hpin;
     uint64_t* hpin_dev = nullptr;   /* hpin as the device addresses it (status words written by kernels) */
     DevBuf dense, vslot, skey0, skey1, seq0, seq1, rank_of_slot, slot_of_rank, rank16;
     DevBuf pkey0, pkey1, pseq0, pseq1, phead;
@@ -163,7 +181,7 @@ struct tfidf_ctx {
     /* the per-run idf table (N <= IDF_FULL_MAX): host threads fill the pinned idf_pin with
      * log(N/df) for df = 0..N while the device runs the stages before the score; run_post
      * joins them and uploads it (every run: round 4's per-N cache was retired in round 6) */
-    double* idf_pin = nullptr;
+    Pinned<double> idf_pin;
     size_t idf_pin_n = 0;
     bool idf_pin_busy = false;            /* an upload from idf_pin is enqueued and not known complete (the
                                              run's final wait clears it; no event record: each costs
@@ -215,7 +233,7 @@ struct tfidf_ctx {
      * long documents, the top-k rounds' two candidate buffers, per-query counters */
     DevBuf q_terms, q_rank, q_tab, q_acc, q_cnt, q_big, q_cand0, q_cand1, q_misc;
     uint64_t query_acc_bytes = 1024ull << 20;   /* env TFIDF_QUERY_ACC_MB: accumulator budget of a query group */
-    hipEvent_t ev_q[3] = {};                    /* lookup / score / top-k bounds (created by the first query) */
+    Event ev_q[3];                              /* lookup / score / top-k bounds (created by the first query) */
     uint32_t ncu = 0;
     tfidf_query_info qinfo{};
     /* BM25 ranking (tfidf_query_bm25, bm25.hip): tfidf_query's buffers; L = the sum of doc_size
@@ -229,7 +247,7 @@ struct tfidf_ctx {
      * documents */
     DevBuf tm_ids, tm_rows, tm_score, tm_pair, tm_term, tm_cnt, tm_woff, tm_words, tm_big;
     uint64_t terms_bytes = 256ull << 20;        /* env TFIDF_TERMS_MB: device result buffers of a batch of rows */
-    hipEvent_t ev_t[5] = {};                    /* lookup or select / scan / gather bounds (created by the first call) */
+    Event ev_t[5];                              /* lookup or select / scan / gather bounds (created by the first call) */
     bool tmeta_valid = false;                   /* t_key / t_len hold this run's term metadata */
     tfidf_terms_info tinfo{};
     /* top-k similar documents (tfidf_similar, similar.hip): sq and norm by output position
@@ -240,7 +258,7 @@ struct tfidf_ctx {
      * accumulators, candidates and counters are tfidf_query's (q_acc .. q_misc). */
     DevBuf sm_norm, sm_ids, sm_rows, sm_mask, sm_cnt, sm_off, sm_pw, sm_res, sm_escore;
     DevBuf sm_xterm, sm_xscore, sm_xwoff, sm_xwords, sm_xoff;
-    hipEvent_t ev_s[6] = {};                    /* norms / table / score / top-k bounds (created by the first call) */
+    Event ev_s[6];                              /* norms / table / score / top-k bounds (created by the first call) */
     bool norm_valid = false;                    /* sm_norm holds this run's norms */
     tfidf_similar_info sinfo{};
     /* spherical k-means (tfidf_kmeans, kmeans.hip): the dense centroid matrix [V][K] (the update's
@@ -252,14 +270,14 @@ struct tfidf_ctx {
     uint32_t kmeans_split = 0;                  /* env TFIDF_KMEANS_SPLIT: update workgroups per cluster (0: fill the GPU) */
     uint32_t an_grid = 0;                       /* env TFIDF_AN_GRID: at most that many workgroups of the analyzer's tile kernel (0: the resident ones) */
     uint32_t grid_cus = 0;                      /* env TFIDF_GRID_CUS: the CU count `ncu` takes in place of the device's (0: the device's), for the run's kernels too */
-    hipEvent_t ev_k[4] = {};                    /* assign / update / top-term bounds (created by the first call) */
+    Event ev_k[4];                              /* assign / update / top-term bounds (created by the first call) */
     tfidf_kmeans_info kinfo{};
     /* unseen documents against the resident model (tfidf_transform, transform.hip): a host
      * batch's bytes and offsets, a slice's boundary scratch (document-start bitmap, per-tile
      * counts, per-document words) and its token and pair arrays */
     DevBuf tr_bytes, tr_off, tr_a, tr_b;
     uint64_t transform_bytes = 512ull << 20;    /* env TFIDF_TRANSFORM_MB: device scratch of a slice */
-    hipEvent_t ev_tr[5] = {};                   /* tokens / resolve / sort / pairs bounds (created by the first call) */
+    Event ev_tr[5];                             /* tokens / resolve / sort / pairs bounds (created by the first call) */
     tfidf_transform_info trinfo{};
     /* the portable model (tfidf_model_import / tfidf_model_export, model.hip).  have_model: the
      * context holds what tfidf_transform reads (table, ranks, df, idf, V, N), from a run or from
@@ -269,20 +287,20 @@ struct tfidf_ctx {
     bool have_model = false, model_only = false;
     DevBuf m_off, m_blob, m_stat;
     uint64_t m_blob_bytes = 0;
-    hipEvent_t ev_m[2] = {};                    /* clear + build bounds (created by the first import) */
+    Event ev_m[2];                              /* clear + build bounds (created by the first import) */
     tfidf_model_info minfo{};
     /* the analyzer (tfidf_analyze, analyze.hip): a host input's staged bytes; per slot the
      * analyzed bytes and the context's copies of the offsets and ids; the document-start bitmap,
      * the stop-word table and the blanked-token counter of the call in flight */
     DevBuf an_in, an_bytes[2], an_off[2], an_ids[2], an_dstart, an_tab, an_cnt;
-    hipEvent_t ev_an[2] = {};                   /* the kernels' bounds (created by the first call) */
+    Event ev_an[2];                             /* the kernels' bounds (created by the first call) */
     tfidf_analyze_info aninfo{};
     /* word n-grams (tfidf_ngrams, ngram.hip): a host input's staged bytes and offsets; per slot
      * the output bytes, the new offsets and the context's copy of the ids; the boundary scratch
      * (status, gram counter, bitmap, per-tile counts), the 24 bytes per token (start, end,
      * segment offset) and the write kernel's tile index of the call in flight */
     DevBuf ng_in, ng_inoff, ng_bytes[2], ng_off[2], ng_ids[2], ng_a, ng_b, ng_tseg;
-    hipEvent_t ev_ng[4] = {};                   /* bounds / sizes / write bounds (created by the first call) */
+    Event ev_ng[4];                             /* bounds / sizes / write bounds (created by the first call) */
     tfidf_ngram_info nginfo{};
     /* vocabulary pruning (tfidf_prune, prune.hip): the keep flags (then the new ranks), the keep
      * bitmap, the max_features sort's ping-pong buffers, the per-tile counts and first documents,
@@ -291,7 +309,7 @@ struct tfidf_ctx {
      * rank, out_term, out_cnt, out_score, out_off), each as large as the buffer it stands in for */
     DevBuf pr_flag, pr_bits, pr_k0, pr_k1, pr_v0, pr_v1, pr_tcnt, pr_tdoc, pr_misc;
     DevBuf pr_sor, pr_df, pr_term, pr_cnt, pr_score, pr_off;
-    hipEvent_t ev_pr[4] = {};                   /* select / terms / pairs bounds (created by the first call) */
+    Event ev_pr[4];                             /* select / terms / pairs bounds (created by the first call) */
     tfidf_prune_info pinfo{};
     uint64_t info_npairs = 0;                   /* the run's P and V as tfidf_last_run_info reports them (a prune */
     uint32_t info_V = 0;                        /* changes npairs and V, not what the run was) */
@@ -308,7 +326,7 @@ struct tfidf_ctx {
     std::vector<double> rw_lut_host;
     std::vector<uint32_t> rw_list_host;
     std::vector<double> rw_listv_host;
-    hipEvent_t ev_rw[3] = {};                   /* tables / pairs bounds (created by the first call) */
+    Event ev_rw[3];                             /* tables / pairs bounds (created by the first call) */
     tfidf_reweight_info rwinfo{};
     /* near duplicates (tfidf_minhash / tfidf_near_dups, dedup.hip): h0 by term rank (kept until the
      * next run, prune or import), the signatures by output position, the hash family, the counter
@@ -316,7 +334,7 @@ struct tfidf_ctx {
      * buffer (keys, values, flags, candidates, the positions with pairs) */
     DevBuf dd_h0, dd_sig, dd_fam, dd_misc, dd_work;
     uint64_t dedup_bytes = 1024ull << 20;       /* env TFIDF_DEDUP_MB: signatures + the bound on candidate scratch */
-    hipEvent_t ev_dd[3] = {};                   /* hash / signature, bands / verify bounds (created by the first call) */
+    Event ev_dd[3];                             /* hash / signature, bands / verify bounds (created by the first call) */
     bool h0_valid = false;                      /* dd_h0 holds this result's term hashes */
     tfidf_dedup_info ddinfo{};
     /* Naive Bayes (tfidf_nb_fit / tfidf_nb_predict, nb.hip): the two dense matrices [V][K] (feature
@@ -326,7 +344,7 @@ struct tfidf_ctx {
      * and scores.  The model stays until the next run, prune, import or fit (nb_valid). */
     DevBuf nb_FC, nb_W, nb_work, nb_lut, nb_list, nb_ids, nb_rows, nb_out;
     uint64_t nb_bytes = 1024ull << 20;          /* env TFIDF_NB_MB: budget of nb_FC + nb_W + nb_work */
-    hipEvent_t ev_nb[4] = {};                   /* count / weights or predict bounds (created by the first call) */
+    Event ev_nb[4];                             /* count / weights or predict bounds (created by the first call) */
     bool nb_valid = false;
     uint32_t nb_K = 0, nb_V = 0, nb_variant = 0, nb_feature = 0, nb_uniform = 0;
     double nb_alpha = 0;
@@ -338,9 +356,9 @@ struct tfidf_ctx {
 #define WR_NBUF 8
 #define WR_BUF (16ull << 20)
 #define WR_GROUPS 8
-    uint8_t* wr_buf[WR_NBUF] = {};   /* pinned output staging ring */
-    hipEvent_t wr_ev[WR_NBUF] = {};
-    hipEvent_t wr_fmt[WR_GROUPS] = {};
+    Pinned<uint8_t> wr_buf[WR_NBUF];   /* pinned output staging ring */
+    Event wr_ev[WR_NBUF];
+    Event wr_fmt[WR_GROUPS];
 #define WR_WRITERS 8   /* page-cache writes run ~3 GB/s per thread (profiles/r04_cli_c2.json) */
     tfidf_output_info out_info{};
     uint64_t text_bytes = 0;
@@ -452,12 +470,45 @@ static inline uint32_t ctx_ncu(tfidf_ctx* ctx) {
 }
 
 /* the context's device, the call's events (created by the first call) and the CU count */
-template <size_t NEV> static inline int call_begin(tfidf_ctx* ctx, hipEvent_t (&ev)[NEV]) {
+template <size_t NEV> static inline int call_begin(tfidf_ctx* ctx, Event (&ev)[NEV]) {
     HIPCHK(hipSetDevice(ctx->device));
-    for (hipEvent_t& e : ev)
-        if (!e) HIPCHK(hipEventCreate(&e));
+    for (Event& e : ev)
+        if (!e) HIPCHK(e.create());
     ctx_ncu(ctx);
     return TFIDF_OK;
+}
+
+/* ---- what a change of the result makes stale.  Every cache kept per result is a row here, and
+ * every call that changes the result says which kind of change it made; a new cache adds its row
+ * and its flag below and touches no other file.
+ *
+ *   cache (flag)                      SCORES   TERMS    NEW      RUN     filled by
+ *   text, text_bytes (text_valid)       x                                 tfidf_format, write_output
+ *   sm_norm (norm_valid)                x                                 sim_norms
+ *   t_key, t_len (tmeta_valid)                   x                        ensure_term_meta
+ *   dd_h0 (h0_valid)                             x                        dd_signatures
+ *   nb_* model (nb_valid)                        x                        tfidf_nb_fit (which also resets it)
+ *   bm25_L (bm25_L_valid)                                 x               tfidf_ctx_bm25_lengths
+ *   have_result, have_model, model_only                   x               tfidf_run, tfidf_model_import
+ *   have_info                                                      x      tfidf_run
+ *
+ *   tfidf_reweight      RC_SCORES                        (docSize, the ranks and the classifier's counts stay)
+ *   tfidf_prune         RC_SCORES | RC_TERMS             (docSize stays: bm25_L does)
+ *   tfidf_model_import  RC_SCORES | RC_TERMS | RC_NEW    (the last run's counters stay readable)
+ *   tfidf_run           RC_SCORES | RC_TERMS | RC_NEW | RC_RUN
+ * rw_idf (rw_idf_mode) and the active scheme (wt_*) are not caches of that kind: a run and an
+ * import reset them where they succeed, tfidf_reweight sets them. ---- */
+enum : unsigned {
+    RC_SCORES = 1u,   /* the pairs' scores were rewritten */
+    RC_TERMS = 2u,    /* terms were renumbered or removed, and pairs with them */
+    RC_NEW = 4u,      /* another corpus or model takes the context: the old result is gone, also when the call fails */
+    RC_RUN = 8u,      /* ... through tfidf_run, whose counters and timings go with it */
+};
+static inline void result_changed(tfidf_ctx* ctx, unsigned what) {
+    if (what & RC_SCORES) ctx->text_valid = ctx->norm_valid = false;
+    if (what & RC_TERMS) ctx->tmeta_valid = ctx->h0_valid = ctx->nb_valid = false;
+    if (what & RC_NEW) ctx->have_result = ctx->have_model = ctx->model_only = ctx->bm25_L_valid = false;
+    if (what & RC_RUN) ctx->have_info = false;
 }
 static inline double wall_ms(std::chrono::steady_clock::time_point t0) {
     return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
@@ -481,6 +532,14 @@ template <typename T> static inline int copy_info(T* info, const T& last) {
 void idf_post(tfidf_ctx* ctx, double* lut, uint64_t Nt, const uint32_t* vals, uint64_t n, uint32_t mode = TFIDF_IDF_REF);
 int idf_pin_quiesce(tfidf_ctx* ctx);
 void idf_join(tfidf_ctx* ctx);
+/* idf_pin of at least n doubles (contents not kept); the caller has quiesced its uploads */
+static inline int idf_pin_reserve(tfidf_ctx* ctx, size_t n) {
+    if (ctx->idf_pin_n >= n) return TFIDF_OK;
+    ctx->idf_pin_n = 0;
+    if (ctx->idf_pin.alloc(n * 8) != hipSuccess) return TFIDF_E_NOMEM;
+    ctx->idf_pin_n = n;
+    return TFIDF_OK;
+}
 struct IdfJoin {
     tfidf_ctx* c;
     ~IdfJoin() { idf_join(c); }
@@ -547,6 +606,14 @@ static inline uint64_t tr_bound(uint64_t nbytes, uint64_t nd) {
 int token_scratch(tfidf_ctx* ctx, TrSlice& sl, DevBuf& scratch, size_t head, size_t* a_end);
 int token_bounds(tfidf_ctx* ctx, const TrSlice& sl, const char* who, uint64_t* T);
 int token_write(tfidf_ctx* ctx, TrSlice& sl, uint64_t* tok_start, uint64_t* tok_end, uint64_t T, size_t arena_want);
+
+/* ---- engine_terms.cpp: the two preambles the calls over the result share ---- */
+/* t_key / t_len of this result (launch_term_meta), once per result: tmeta_valid */
+int ensure_term_meta(tfidf_ctx* ctx);
+/* n document ids from the host into `ids` and their output positions (k_terms_lookup; UINT32_MAX:
+ * not held) to d_pos, or when d_pos is null behind the ids in the same buffer.  Enqueued only:
+ * event records and read-backs are the caller's. */
+int lookup_ids(tfidf_ctx* ctx, DevBuf& ids, const uint32_t* host_ids, uint32_t n, uint32_t* d_pos);
 
 /* ---- engine_prune.cpp ---- */
 int ensure_spare(DevBuf& spare, const DevBuf& orig, size_t need);

@@ -79,13 +79,8 @@ int dd_signatures(tfidf_ctx* ctx, const DdPlan& pl, tfidf_dedup_info& di) {
     HIPCHK(hipEventRecord(ctx->ev_dd[0], s));
     const bool hashed = !ctx->h0_valid;
     if (hashed) {
-        if (V && !ctx->tmeta_valid) {
-            ENSURE(ctx->t_key, (size_t)V * 16 + 16);
-            ENSURE(ctx->t_len, (size_t)V * 4 + 4);
-            LAUNCH(launch_term_meta(ctx->vkeys.as<uint4>(), ctx->vrep.as<uint64_t>(), ctx->slot_of_rank.as<uint32_t>(), V,
-                                    ctx->t_key.as<uint4>(), ctx->t_len.as<uint32_t>(), s));
-            ctx->tmeta_valid = true;
-        }
+        if (V)
+            if (const int rc = ensure_term_meta(ctx)) return rc;
         LAUNCH(launch_dd_h0(ctx->t_key.as<uint4>(), ctx->t_len.as<uint32_t>(), V, ctx->dev_bytes, ctx->corpus.nbytes,
                             ctx->dd_h0.as<uint64_t>(), s));
         ctx->h0_valid = true;

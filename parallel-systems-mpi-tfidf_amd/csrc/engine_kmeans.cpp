@@ -175,14 +175,8 @@ extern "C" int tfidf_kmeans(tfidf_ctx* ctx, const tfidf_kmeans_params* params, t
 
     /* ---- the clusters' best terms and their words ---- */
     if (T) {
-        if (V && !ctx->tmeta_valid) {
-            ENSURE(ctx->t_key, (size_t)V * 16 + 16);
-            ENSURE(ctx->t_len, (size_t)V * 4 + 4);
-            if (launch_term_meta(ctx->vkeys.as<uint4>(), ctx->vrep.as<uint64_t>(), ctx->slot_of_rank.as<uint32_t>(), V,
-                                 ctx->t_key.as<uint4>(), ctx->t_len.as<uint32_t>(), s))
-                return TFIDF_E_HIP;
-            ctx->tmeta_valid = true;
-        }
+        if (V)
+            if (const int rc = ensure_term_meta(ctx)) return rc;
         ENSURE(ctx->km_top, (size_t)K * KM_TOP_SLICES * 16 + (size_t)K * 16 + KT * 8 + (KT + 1) * 8 + KT * 4 + (size_t)K * 4 + 64);
         KmTopArgs ta{};
         ta.C = a.C;

@@ -41,14 +41,7 @@ extern "C" int tfidf_model_export(tfidf_ctx* ctx, tfidf_model* out) {
         if (V) HIPCHK(hipMemcpyAsync(out->term_off, ctx->m_off.p, ((size_t)V + 1) * 8, hipMemcpyDeviceToHost, s));
         d_words = ctx->m_blob.as<uint8_t>();
     } else if (V) {
-        if (!ctx->tmeta_valid) {
-            ENSURE(ctx->t_key, (size_t)V * 16 + 16);
-            ENSURE(ctx->t_len, (size_t)V * 4 + 4);
-            if (launch_term_meta(ctx->vkeys.as<uint4>(), ctx->vrep.as<uint64_t>(), ctx->slot_of_rank.as<uint32_t>(), V,
-                                 ctx->t_key.as<uint4>(), ctx->t_len.as<uint32_t>(), s))
-                return TFIDF_E_HIP;
-            ctx->tmeta_valid = true;
-        }
+        if (const int rc = ensure_term_meta(ctx)) return rc;
         ENSURE(ctx->tm_term, (size_t)V * 4 + 4);
         ENSURE(ctx->tm_woff, ((size_t)V + 1) * 8 + 16);
         uint64_t* d_woff = ctx->tm_woff.as<uint64_t>();
@@ -100,15 +93,7 @@ extern "C" int tfidf_model_import(tfidf_ctx* ctx, const tfidf_model* m) {
         cap *= 2;
     if (cap > K1_VS_MAX_CAP) return TFIDF_E_CAPACITY;
     /* from here on the previous result or model is gone */
-    ctx->have_result = false;
-    ctx->have_model = false;
-    ctx->model_only = false;
-    ctx->text_valid = false;
-    ctx->tmeta_valid = false;
-    ctx->norm_valid = false;
-    ctx->h0_valid = false;
-    ctx->nb_valid = false;
-    ctx->bm25_L_valid = false;
+    result_changed(ctx, RC_SCORES | RC_TERMS | RC_NEW);
     if (const int q = idf_pin_quiesce(ctx)) return q;
     ctx->vcap = cap;
     DevBuf& dfb = ctx->xp ? ctx->df_global : ctx->df_local;   /* df_of_run */
@@ -137,14 +122,7 @@ extern "C" int tfidf_model_import(tfidf_ctx* ctx, const tfidf_model* m) {
     const bool full_lut = Nt <= IDF_FULL_MAX;
     IdfJoin idf_guard{ctx};
     if (V && full_lut) {
-        const size_t n = (size_t)Nt + 1;
-        if (ctx->idf_pin_n < n) {
-            if (ctx->idf_pin) (void)hipHostFree(ctx->idf_pin);
-            ctx->idf_pin = nullptr;
-            ctx->idf_pin_n = 0;
-            if (hipHostMalloc((void**)&ctx->idf_pin, n * 8, hipHostMallocDefault) != hipSuccess) return TFIDF_E_NOMEM;
-            ctx->idf_pin_n = n;
-        }
+        if (idf_pin_reserve(ctx, (size_t)Nt + 1)) return TFIDF_E_NOMEM;
         ctx->idf_full_n = 0;
         ctx->idf_pin[0] = 0.0;
         idf_post(ctx, ctx->idf_pin, Nt, nullptr, Nt);
@@ -198,14 +176,7 @@ extern "C" int tfidf_model_import(tfidf_ctx* ctx, const tfidf_model* m) {
         HIPCHK(hipMemcpyAsync(vals.data(), vals_dev, (size_t)K * 4, hipMemcpyDeviceToHost, s));
         HIPCHK(hipStreamSynchronize(s));
         ENSURE(ctx->idf_vals, (size_t)K * 8 + 8);
-        if (ctx->idf_pin_n < (size_t)K + 1) {
-            if (ctx->idf_pin) (void)hipHostFree(ctx->idf_pin);
-            ctx->idf_pin = nullptr;
-            ctx->idf_pin_n = 0;
-            if (hipHostMalloc((void**)&ctx->idf_pin, ((size_t)K + 1) * 8, hipHostMallocDefault) != hipSuccess)
-                return TFIDF_E_NOMEM;
-            ctx->idf_pin_n = (size_t)K + 1;
-        }
+        if (idf_pin_reserve(ctx, (size_t)K + 1)) return TFIDF_E_NOMEM;
         if (K < 2 * 16384) {
             for (uint32_t k = 0; k < K; ++k) ctx->idf_pin[k] = log(1.0 * (double)Nt / (double)vals[k]);
         } else {

@@ -124,13 +124,9 @@ extern "C" int tfidf_nb_fit(tfidf_ctx* ctx, const tfidf_nb_params* params) {
     ni.matrix_bytes = matrix;
 
     /* ---- labelled ids -> output positions -> a class word per position ---- */
-    ENSURE(ctx->nb_ids, (size_t)n * 8 + 8);
-    uint32_t* d_ids = ctx->nb_ids.as<uint32_t>();
     std::vector<uint32_t> h_pos((size_t)n + 1), h_lab((size_t)N + 1, NB_NO_CLASS);
-    HIPCHK(hipMemcpyAsync(d_ids, params->doc, (size_t)n * 4, hipMemcpyHostToDevice, s));
-    TLookupArgs la{d_ids, (uint32_t)n, ctx->order, ctx->dev_ids, N, d_ids + n};
-    LAUNCH(launch_terms_lookup(la, s));
-    HIPCHK(hipMemcpyAsync(h_pos.data(), d_ids + n, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+    if (const int rc = lookup_ids(ctx, ctx->nb_ids, params->doc, (uint32_t)n, nullptr)) return rc;
+    HIPCHK(hipMemcpyAsync(h_pos.data(), ctx->nb_ids.as<uint32_t>() + n, (size_t)n * 4, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
     ctx->nb_class_docs.assign(K, 0);
     for (uint64_t i = 0; i < n; ++i) {
@@ -280,9 +276,7 @@ extern "C" int tfidf_nb_predict(tfidf_ctx* ctx, const uint32_t* doc_ids, uint32_
     ENSURE(ctx->nb_ids, (size_t)R * 8 + 8);
     uint32_t* d_ids = ctx->nb_ids.as<uint32_t>();
     if (doc_ids && R) {
-        HIPCHK(hipMemcpyAsync(d_ids, doc_ids, (size_t)R * 4, hipMemcpyHostToDevice, s));
-        TLookupArgs la{d_ids, R, ctx->order, ctx->dev_ids, N, d_ids + R};
-        LAUNCH(launch_terms_lookup(la, s));
+        if (const int rc = lookup_ids(ctx, ctx->nb_ids, doc_ids, R, nullptr)) return rc;   /* the same size: d_ids stays */
         HIPCHK(hipMemcpyAsync(out->pos, d_ids + R, (size_t)R * 4, hipMemcpyDeviceToHost, s));
         HIPCHK(hipStreamSynchronize(s));
         memcpy(out->doc, doc_ids, (size_t)R * 4);

@@ -17,14 +17,7 @@
 int ensure_spare(DevBuf& spare, const DevBuf& orig, size_t need) {
     const size_t want = orig.cap > need ? orig.cap : need;
     if (spare.p && spare.cap >= want) return 0;
-    spare.release();
-    if (tfidf_dev_malloc(&spare.p, want) != hipSuccess) {
-        (void)hipGetLastError();
-        spare.p = nullptr;
-        return -1;
-    }
-    spare.cap = want;
-    return 0;
+    return spare.exact(want);
 }
 
 extern "C" int tfidf_prune(tfidf_ctx* ctx, const tfidf_prune_params* params) {
@@ -144,11 +137,7 @@ extern "C" int tfidf_prune(tfidf_ctx* ctx, const tfidf_prune_params* params) {
     std::swap(ctx->out_off, ctx->pr_off);
     ctx->V = V2;
     ctx->npairs = P2;
-    ctx->text_valid = false;
-    ctx->tmeta_valid = false;
-    ctx->h0_valid = false;
-    ctx->nb_valid = false;     /* the classifier's matrices are indexed by the old ranks */
-    ctx->norm_valid = false;   /* bm25_L stays: docSize is unchanged */
+    result_changed(ctx, RC_SCORES | RC_TERMS);   /* the classifier's matrices are indexed by the old ranks */
     pi.nterms_after = V2;
     pi.npairs_after = P2;
     pi.docs_emptied = emptied;

@@ -87,17 +87,6 @@ int sim_norms(tfidf_ctx* ctx, tfidf_similar_info& si) {
     return TFIDF_OK;
 }
 
-/* requested ids -> output positions at `d_pos` (k_terms_lookup) */
-static int sim_lookup_ids(tfidf_ctx* ctx, const uint32_t* ids, uint32_t R, uint32_t* d_pos) {
-    hipStream_t s = ctx->stream;
-    ENSURE(ctx->sm_ids, (size_t)R * 4 + 8);
-    uint32_t* d_ids = ctx->sm_ids.as<uint32_t>();
-    HIPCHK(hipMemcpyAsync(d_ids, ids, (size_t)R * 4, hipMemcpyHostToDevice, s));
-    TLookupArgs la{d_ids, R, ctx->order, ctx->dev_ids, ctx->ndocs, d_pos};
-    LAUNCH(launch_terms_lookup(la, s));
-    return TFIDF_OK;
-}
-
 /* the rows of a call from the resident result: positions (ids looked up, or every position),
  * vector ranges, norms, ids; copied to the host arrays (R entries each) */
 static int sim_resident_rows(tfidf_ctx* ctx, const uint32_t* doc_ids, uint32_t R, SimCall& c, uint64_t* h_rb,
@@ -107,7 +96,7 @@ static int sim_resident_rows(tfidf_ctx* ctx, const uint32_t* doc_ids, uint32_t R
     if (rc) return rc;
     if (!R) return TFIDF_OK;
     if (doc_ids) {
-        rc = sim_lookup_ids(ctx, doc_ids, R, c.rpos);
+        rc = lookup_ids(ctx, ctx->sm_ids, doc_ids, R, c.rpos);
         if (rc) return rc;
     }
     SimRowArgs ra{};
@@ -303,14 +292,7 @@ int tfidf_ctx_similar_export(tfidf_ctx* ctx, const uint32_t* doc_ids, uint32_t n
     tfidf_similar_info si{};
     rc = sim_norms(ctx, si);
     if (rc) return rc;
-    if (V && !ctx->tmeta_valid) {
-        ENSURE(ctx->t_key, (size_t)V * 16 + 16);
-        ENSURE(ctx->t_len, (size_t)V * 4 + 4);
-        if (launch_term_meta(ctx->vkeys.as<uint4>(), ctx->vrep.as<uint64_t>(), ctx->slot_of_rank.as<uint32_t>(), V,
-                             ctx->t_key.as<uint4>(), ctx->t_len.as<uint32_t>(), s))
-            return TFIDF_E_HIP;
-        ctx->tmeta_valid = true;
-    }
+    if (V && (rc = ensure_term_meta(ctx)) != 0) return rc;
     SimCall c;
     std::vector<uint64_t> h_rb((size_t)R + 1), h_re((size_t)R + 1);
     e->id.assign((size_t)R + 1, 0);
@@ -392,7 +374,7 @@ int tfidf_ctx_similar_ext(tfidf_ctx* ctx, const SimExport* rows, uint32_t k, tfi
     for (uint32_t i = 0; i < R; ++i) out->doc[i] = rows->id[i];
     if (R && P && ctx->ndocs && ctx->V) {
         /* the rows' own documents by id (another shard's: no position here) */
-        rc = sim_lookup_ids(ctx, rows->id.data(), R, c.rpos);
+        rc = lookup_ids(ctx, ctx->sm_ids, rows->id.data(), R, c.rpos);
         if (rc) return rc;
         HIPCHK(hipMemcpyAsync(c.rb, rows->voff.data(), (size_t)R * 8, hipMemcpyHostToDevice, s));
         HIPCHK(hipMemcpyAsync(c.re, rows->voff.data() + 1, (size_t)R * 8, hipMemcpyHostToDevice, s));

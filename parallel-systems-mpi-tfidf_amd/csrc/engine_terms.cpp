@@ -11,6 +11,28 @@
  * selected words' lengths and a gather of their bytes, copied straight into the caller's
  * arrays.  Nothing of the run's result is written. */
 
+/* ---- the preambles the calls over the result share (engine_ctx.h): emit.hip's term metadata
+ * and terms.hip's id lookup ---- */
+int ensure_term_meta(tfidf_ctx* ctx) {
+    if (ctx->tmeta_valid) return TFIDF_OK;
+    const uint32_t V = ctx->V;
+    ENSURE(ctx->t_key, (size_t)V * 16 + 16);
+    ENSURE(ctx->t_len, (size_t)V * 4 + 4);
+    LAUNCH(launch_term_meta(ctx->vkeys.as<uint4>(), ctx->vrep.as<uint64_t>(), ctx->slot_of_rank.as<uint32_t>(), V,
+                            ctx->t_key.as<uint4>(), ctx->t_len.as<uint32_t>(), ctx->stream));
+    ctx->tmeta_valid = true;
+    return TFIDF_OK;
+}
+
+int lookup_ids(tfidf_ctx* ctx, DevBuf& ids, const uint32_t* host_ids, uint32_t n, uint32_t* d_pos) {
+    ENSURE(ids, (size_t)n * (d_pos ? 4 : 8) + 8);
+    uint32_t* d_ids = ids.as<uint32_t>();
+    HIPCHK(hipMemcpyAsync(d_ids, host_ids, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
+    TLookupArgs la{d_ids, n, ctx->order, ctx->dev_ids, ctx->ndocs, d_pos ? d_pos : d_ids + n};
+    LAUNCH(launch_terms_lookup(la, ctx->stream));
+    return TFIDF_OK;
+}
+
 extern "C" void tfidf_doc_terms_free(tfidf_doc_terms* t) {
     if (!t) return;
     free(t->doc); free(t->pos); free(t->npairs); free(t->nterms); free(t->term); free(t->count);
@@ -53,29 +75,19 @@ extern "C" int tfidf_top_terms(tfidf_ctx* ctx, const uint32_t* doc_ids, uint32_t
     ti.k = k;
 
     /* ---- the selected words' lengths and byte sources: the formatter's term metadata ---- */
-    if (V && !ctx->tmeta_valid) {
-        ENSURE(ctx->t_key, (size_t)V * 16 + 16);
-        ENSURE(ctx->t_len, (size_t)V * 4 + 4);
-        if (launch_term_meta(ctx->vkeys.as<uint4>(), ctx->vrep.as<uint64_t>(), ctx->slot_of_rank.as<uint32_t>(), V,
-                             ctx->t_key.as<uint4>(), ctx->t_len.as<uint32_t>(), s))
-            return TFIDF_E_HIP;
-        ctx->tmeta_valid = true;
-    }
+    if (V)
+        if (const int rc = ensure_term_meta(ctx)) return rc;
 
     /* ---- lookup: one lane per requested id ---- */
     const uint32_t* d_pos = nullptr;
     if (doc_ids && R) {
-        ENSURE(ctx->tm_ids, (size_t)R * 8 + 8);
-        uint32_t* d_ids = ctx->tm_ids.as<uint32_t>();
-        HIPCHK(hipMemcpyAsync(d_ids, doc_ids, (size_t)R * 4, hipMemcpyHostToDevice, s));
-        TLookupArgs la{d_ids, R, ctx->order, ctx->dev_ids, N, d_ids + R};
         HIPCHK(hipEventRecord(ctx->ev_t[0], s));
-        LAUNCH(launch_terms_lookup(la, s));
+        if (const int rc = lookup_ids(ctx, ctx->tm_ids, doc_ids, R, nullptr)) return rc;
         HIPCHK(hipEventRecord(ctx->ev_t[1], s));
-        HIPCHK(hipMemcpyAsync(out->pos, d_ids + R, (size_t)R * 4, hipMemcpyDeviceToHost, s));
+        d_pos = ctx->tm_ids.as<uint32_t>() + R;
+        HIPCHK(hipMemcpyAsync(out->pos, d_pos, (size_t)R * 4, hipMemcpyDeviceToHost, s));
         HIPCHK(hipStreamSynchronize(s));
         ti.ms_lookup = ev_ms(ctx->ev_t[0], ctx->ev_t[1]);
-        d_pos = d_ids + R;
         ti.out_bytes += (uint64_t)R * 4;
     } else {
         for (uint32_t r = 0; r < R; ++r) out->pos[r] = r;

@@ -41,13 +41,7 @@ static int rw_idf_table(tfidf_ctx* ctx, uint32_t mode, uint64_t* nlogs) {
         n = K;
     }
     ENSURE(ctx->rw_idf, (size_t)n * 8 + 8);
-    if (ctx->idf_pin_n < (size_t)n + 1) {
-        if (ctx->idf_pin) (void)hipHostFree(ctx->idf_pin);
-        ctx->idf_pin = nullptr;
-        ctx->idf_pin_n = 0;
-        if (hipHostMalloc((void**)&ctx->idf_pin, ((size_t)n + 1) * 8, hipHostMallocDefault) != hipSuccess) return TFIDF_E_NOMEM;
-        ctx->idf_pin_n = (size_t)n + 1;
-    }
+    if (idf_pin_reserve(ctx, (size_t)n + 1)) return TFIDF_E_NOMEM;
     if (vals.empty()) {
         ctx->idf_pin[0] = 0.0;   /* df >= 1 for every term that occurs */
         idf_post(ctx, ctx->idf_pin, Nt, nullptr, Nt, mode);
@@ -197,8 +191,7 @@ extern "C" int tfidf_reweight(tfidf_ctx* ctx, const tfidf_weighting* w) {
         HIPCHK(hipMemcpyAsync(mw, ctx->rw_misc.as<uint32_t>() + RWM_BIG, 8, hipMemcpyDeviceToHost, s));
         HIPCHK(hipStreamSynchronize(s));   /* the spare is written: from here on the call cannot fail */
         std::swap(ctx->out_score, ctx->pr_score);
-        ctx->text_valid = false;
-        ctx->norm_valid = false;   /* bm25_L stays: docSize is unchanged */
+        result_changed(ctx, RC_SCORES);
         ri.big_docs = mw[0] < N ? mw[0] : N;
         ri.zero_norm_docs = mw[1];
         ri.ms_tables = ev_ms(ctx->ev_rw[0], ctx->ev_rw[1]);

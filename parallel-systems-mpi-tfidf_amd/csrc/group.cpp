@@ -33,6 +33,7 @@
 #include "../../include/tfidf.h"
 #include "kernels.h"
 #include "xport.h"
+#include "devbuf.h"
 #include "comm_rank.h"
 #include "comm_init.h"
 
@@ -125,13 +126,12 @@ struct RcclXport final : Xport {
     CommRank<RcclB> cr;                    /* this rank's communicator and the clique's flag */
     std::shared_ptr<Clique> clique;        /* a tfidf_group clique owns the communicator; else this */
     int device = 0;
-    uint64_t* dwords = nullptr;   /* 2 (send) + 2 * nranks (recv) */
+    DevBuf dwords_buf;   /* 2 (send) + 2 * nranks (recv) */
     ~RcclXport() override {
         if (!clique && !cr.dead && cr.comm) {
             std::vector<ncclComm_t> one{cr.comm};
             comms_close(one, cr.timeout_ms);
         }
-        if (dwords) (void)hipFree(dwords);
     }
     void note_dead() {
         if (clique && cr.dead) clique->dead[rank] = 1;
@@ -156,7 +156,8 @@ struct RcclXport final : Xport {
         return rc;
     }
     int words(const uint64_t mine[2], uint64_t* all, hipStream_t s) override {
-        if (!dwords && tfidf_dev_malloc((void**)&dwords, 16 * (size_t)(nranks + 1)) != hipSuccess) return TFIDF_E_NOMEM;
+        if (!dwords_buf.p && dwords_buf.exact(16 * (size_t)(nranks + 1))) return TFIDF_E_NOMEM;
+        uint64_t* dwords = dwords_buf.as<uint64_t>();
         if (hipMemcpyAsync(dwords, mine, 16, hipMemcpyHostToDevice, s) != hipSuccess) return TFIDF_E_HIP;
         int rc = enqueue([&](ncclComm_t c) { return ncclAllGather(dwords, dwords + 2, 2, ncclUint64, c, s); });
         if (rc) return rc;
@@ -329,21 +330,17 @@ struct LocalXport final : Xport {
     /* every rank copies all ranks' vectors into its staging area (after a barrier: all are
      * complete), then (after a second barrier: nobody overwrites a vector still being read)
      * sums them into its own */
-    uint32_t* stage = nullptr;
+    DevBuf stage_buf;
     size_t stage_n = 0;
-    ~LocalXport() override {
-        if (stage) (void)hipFree(stage);
-    }
     int allreduce_u32(uint32_t* buf, size_t n, hipStream_t s) override {
         if (!n) return hub->barrier() && hub->barrier() && hub->barrier() ? TFIDF_OK : TFIDF_E_PEER;
         if (one_device()) return allreduce_slices(buf, n, s);
         if (stage_n < n * (size_t)nranks) {
-            if (stage) (void)hipFree(stage);
-            stage = nullptr;
             stage_n = 0;
-            if (tfidf_dev_malloc((void**)&stage, n * (size_t)nranks * 4) != hipSuccess) { abort(); return TFIDF_E_NOMEM; }
+            if (stage_buf.exact(n * (size_t)nranks * 4)) { abort(); return TFIDF_E_NOMEM; }
             stage_n = n * (size_t)nranks;
         }
+        uint32_t* stage = stage_buf.as<uint32_t>();
         if (hipStreamSynchronize(s) != hipSuccess) { abort(); return TFIDF_E_HIP; }
         hub->ptr[rank] = buf;
         if (!hub->barrier()) return TFIDF_E_PEER;
@@ -368,12 +365,11 @@ struct LocalXport final : Xport {
     int allreduce_slices(uint32_t* buf, size_t n, hipStream_t s) {
         const size_t chunk = (n + nranks - 1) / nranks;
         if (stage_n < chunk) {
-            if (stage) (void)hipFree(stage);
-            stage = nullptr;
             stage_n = 0;
-            if (tfidf_dev_malloc((void**)&stage, chunk * 4) != hipSuccess) { abort(); return TFIDF_E_NOMEM; }
+            if (stage_buf.exact(chunk * 4)) { abort(); return TFIDF_E_NOMEM; }
             stage_n = chunk;
         }
+        uint32_t* stage = stage_buf.as<uint32_t>();
         auto slice = [&](int r, size_t* lo) {
             *lo = chunk * r < n ? chunk * r : n;
             return (chunk * (r + 1) < n ? chunk * (r + 1) : n) - *lo;

@@ -105,9 +105,6 @@ struct tfidf_corpus;
 struct tfidf_rows;
 int tfidf_ctx_transform(tfidf_ctx* ctx, const tfidf_corpus* batch, tfidf_rows* out, bool norm);
 
-/* engine.cpp: hipMalloc counted in tfidf_run_info.device_allocs / device_alloc_bytes */
-hipError_t tfidf_dev_malloc(void** p, size_t bytes);
-
 /* group.cpp */
 /* a process-per-GPU rank: non-blocking ncclCommInitRankConfig with the job's unique id */
 int rccl_init_rank(const void* unique_id, int rank, int nranks, int device, Xport** out);

@@ -31,7 +31,7 @@ ABI_VERSION = 2  # TFIDF_ABI_VERSION of include/tfidf.h this binding is written 
 EXPORTS = [
     "tfidf_open", "tfidf_close", "tfidf_strerror", "tfidf_abi_version", "tfidf_comm_unique_id",
     "tfidf_comm_init", "tfidf_run", "tfidf_fetch", "tfidf_result_free", "tfidf_last_run_info", "tfidf_alloc_stats",
-    "tfidf_grid_cus",
+    "tfidf_alloc_live", "tfidf_grid_cus",
     "tfidf_stage_name", "tfidf_set_timing", "tfidf_write_output", "tfidf_print_jobs",
     "tfidf_ingest_dir", "tfidf_free", "tfidf_synth_host", "tfidf_synth_device",
     "tfidf_format", "tfidf_copy_text", "tfidf_write_output_gpu", "tfidf_format_f64",
@@ -431,6 +431,7 @@ def lib() -> C.CDLL:
         L.tfidf_last_run_info.argtypes = [C.c_void_p, C.POINTER(RunInfo)]
         L.tfidf_run_totals_get.argtypes = [C.c_void_p, C.POINTER(RunTotals), C.c_int]
         L.tfidf_alloc_stats.argtypes = [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        L.tfidf_alloc_live.argtypes = [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
         L.tfidf_grid_cus.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
         L.tfidf_stage_name.restype = C.c_char_p
         L.tfidf_set_timing.argtypes = [C.c_void_p, C.c_int]
@@ -1809,6 +1810,14 @@ def format_lines(res: dict) -> bytes:
 def device_count() -> int:
     """Visible HIP devices (tfidf_device_count; 0 without a GPU)."""
     return int(lib().tfidf_device_count())
+
+
+def alloc_live():
+    """(device allocations, bytes) the library holds in this process right now: allocations minus
+    frees (tfidf_alloc_live).  The same before an Engine or Group is opened and after it is closed."""
+    a, b = C.c_uint64(), C.c_uint64()
+    _chk(lib().tfidf_alloc_live(C.byref(a), C.byref(b)), "tfidf_alloc_live")
+    return int(a.value), int(b.value)
 
 
 def comm_unique_id() -> bytes:
