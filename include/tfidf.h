@@ -449,6 +449,93 @@ typedef struct tfidf_bm25_info {
 } tfidf_bm25_info;
 int tfidf_last_bm25_info(const tfidf_ctx* ctx, tfidf_bm25_info* info);
 
+/* ---------------------------------------------------------------- clauses --- */
+
+/* tfidf_query / tfidf_query_bm25 with must, should and must-not clauses.  Query q has three
+ * texts, `must`, `should` and `must_not`, each tokenised exactly as a tfidf_query text (tokens
+ * are maximal runs of bytes outside {0x20,0x09..0x0D}, a term is the token up to its first NUL,
+ * terms of >= 16 bytes are matched by their bytes).
+ *   M(q), S(q), X(q)  the sets of distinct terms of the three texts
+ *   w(q,t)            the tokens of t in the must text plus those in the should text (a u32
+ *                     that saturates, as tfidf_query's)
+ *   scoring terms     M(q) u S(q)
+ *   m(q)              min_should[q], or 0 without the array
+ * Document d is a hit of q exactly when
+ *   (a) every term of M(q) occurs in d,
+ *   (b) no term of X(q) occurs in d,
+ *   (c) at least m(q) terms of S(q) occur in d (a term that is also in M counts here too),
+ *   (d) d holds at least one scoring term.
+ *   score(q,d)        tfidf_query's sum (TFIDF_RANK_TFIDF) or tfidf_query_bm25's (TFIDF_RANK_BM25,
+ *                     W = fl(w * idf)) over the scoring terms that occur in d, in pair order,
+ *                     every product rounded before its add: the same fixed sequence of IEEE
+ *                     operations.  A term that is only in X contributes no product.
+ *   order and cut     score descending, then global document id ascending; the first k
+ *   nmatch[q]         the documents that satisfy (a)-(d), counted before the cut
+ *   nterms_found[q]   the distinct scoring terms present in the vocabulary
+ * Consequences:
+ *   1. with empty must and must_not texts and m = 0 every field equals tfidf_query /
+ *      tfidf_query_bm25 of the should text, bit for bit;
+ *   2. in general the hits are the OR ranking of the text must + " " + should restricted to the
+ *      documents that pass (a)-(c); no score bit differs;
+ *   3. a must term outside the vocabulary gives no hits;
+ *   4. a term in both M and X gives no hits;
+ *   5. m(q) > |S(q)| gives no hits;
+ *   6. a query with only a must_not text has no hits;
+ *   7. an X term outside the vocabulary is ignored;
+ *   8. the result does not depend on grid, group size, budget or number of shards (every
+ *      condition is decided per document).
+ * Limits, checked on the host (TFIDF_E_INVAL): at most TFIDF_CLAUSE_MAX_TERMS distinct terms in one
+ * query's must text and the same in its should text, at most TFIDF_CLAUSE_MAX_NOT in its must_not
+ * text, min_should[q] <= TFIDF_CLAUSE_MAX_TERMS: the 12 + 12 + 8 bits of one count word per
+ * (query, document). */
+#define TFIDF_RANK_TFIDF 0u
+#define TFIDF_RANK_BM25  1u
+#define TFIDF_CLAUSE_MAX_TERMS 4095u
+#define TFIDF_CLAUSE_MAX_NOT   255u
+typedef struct tfidf_clauses {
+    uint64_t size;                       /* sizeof(tfidf_clauses), set by the caller */
+    uint32_t nqueries, ranking;          /* TFIDF_RANK_TFIDF / TFIDF_RANK_BM25 */
+    const tfidf_queries *must, *should, *must_not;   /* NULL: that text is empty in every query;
+                                                        otherwise ->nqueries == nqueries */
+    const uint32_t* min_should;          /* nqueries entries, or NULL */
+    const tfidf_bm25_params* bm25;       /* BM25: NULL = the defaults; must be NULL for TFIDF_RANK_TFIDF */
+} tfidf_clauses;
+/* Every rule above on the host, without a GPU: TFIDF_E_INVAL for NULL, a short `size`, an
+ * unknown ranking, nqueries > TFIDF_QUERY_MAX_QUERIES, a batch with another nqueries or a bad
+ * q_off, bm25 set under TFIDF_RANK_TFIDF or bad BM25 parameters, and the limits. */
+int tfidf_clauses_check(const tfidf_clauses* clauses);
+/* Errors, state rules and buffers are tfidf_query's: TFIDF_E_STATE before a successful tfidf_run
+ * and on a model-only context, *out zeroed on error, the run's result is not disturbed, the call
+ * is local with a communicator attached, the buffers belong to the context (a repeated call
+ * allocates nothing), and the call follows tfidf_prune / tfidf_reweight as tfidf_query does.
+ * tfidf_last_query_info and tfidf_last_bm25_info keep what the last tfidf_query /
+ * tfidf_query_bm25 left.  The rows are freed with tfidf_hits_free. */
+int tfidf_query_clauses(tfidf_ctx* ctx, const tfidf_clauses* clauses, uint32_t k, tfidf_hits* out);
+/* The same over every shard of a group, merged like tfidf_group_query (BM25 with avgdl = 0: the
+ * average over every shard, as tfidf_group_query_bm25).  The conditions are per document and the
+ * shards partition the documents, so the result is the single-shard one. */
+int tfidf_group_query_clauses(tfidf_group* g, const tfidf_clauses* clauses, uint32_t k, tfidf_hits* out);
+/* Counters of the last tfidf_query_clauses: tfidf_bm25_info's fields (avgdl 0 under
+ * TFIDF_RANK_TFIDF) and two more (the caller sets `size` = sizeof). */
+typedef struct tfidf_clause_info {
+    uint64_t size;
+    uint32_t nqueries, k;
+    uint32_t nterms;          /* distinct terms of the batch, the three texts together */
+    uint32_t nterms_found;
+    uint32_t ngroups;
+    uint32_t group_queries;
+    uint64_t acc_bytes;
+    double   ms_lookup;
+    double   ms_score;
+    double   ms_topk;
+    double   ms_total;
+    double   avgdl;
+    uint32_t nq_unsatisfiable; /* queries dropped on the host: a must term outside this shard's
+                                  vocabulary, a term in both M and X, or m > |S| */
+    uint32_t ngroups_tab_lds;  /* groups whose table the scoring kernels staged in LDS */
+} tfidf_clause_info;
+int tfidf_last_clause_info(const tfidf_ctx* ctx, tfidf_clause_info* info);
+
 /* ---------------------------------------------------------------- keywords -- */
 
 /* Per-document top-k keyword extraction over the resident result of the last run: the k

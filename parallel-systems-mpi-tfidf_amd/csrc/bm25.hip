@@ -60,6 +60,12 @@ struct Bm25Score {
     }
 };
 
+/* the same with clauses: a match adds its posting's increment to the document's count word */
+struct Bm25ClauseScore : Bm25Score {
+    using Args = BClauseArgs;
+    static constexpr bool POST_INC = true;
+};
+
 }  // namespace
 
 int launch_bm25_df(const uint32_t* rank, uint32_t n, const uint32_t* df, uint32_t V, uint32_t* out, hipStream_t s) {
@@ -69,3 +75,8 @@ int launch_bm25_df(const uint32_t* rank, uint32_t n, const uint32_t* df, uint32_
 }
 
 int launch_bm25_score(const BScoreArgs& a, uint32_t ncu, hipStream_t s) { return docscan::launch_score<Bm25Score>(a, ncu, s); }
+
+int launch_bm25_score_clauses(const BClauseArgs& a, uint32_t ncu, hipStream_t s) {
+    if (!a.post_inc) return -1;
+    return docscan::launch_score<Bm25ClauseScore>(a, ncu, s);
+}

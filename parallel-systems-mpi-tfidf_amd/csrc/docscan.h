@@ -18,6 +18,7 @@
  *   P::doc_ready     completes the state: at the document's first match in the wave kernel
  *                    (wave-uniform), once per document in the workgroup kernel
  *   P::value         a matching pair's value, by the lane or thread that holds the match
+ *   P::POST_INC      optional, true: a match adds its posting's increment to the count word
  *
  * No product may be fused into an add and every operation rounds on its own: hipcc contracts
  * a * b + c by default, through __dmul_rn / __dadd_rn as well (they compiled to v_fmac_f64
@@ -39,7 +40,14 @@ namespace docscan {
 constexpr int NT = 256;
 constexpr uint32_t QF_BITS = 1u << 18;          /* LDS filter: 32 KiB */
 constexpr uint32_t QF_WORDS = QF_BITS / 32u;
-constexpr uint32_t QTAB_WORDS = 4096u;          /* a group's table staged in LDS when it fits (16 KiB) */
+
+/* P::POST_INC (a static constexpr bool, absent = false): a match adds its posting's post_inc word
+ * to the count instead of 1 (the clause policies: one field of the word per clause kind); P::Args
+ * then has the member post_inc, an array inside the table's block */
+template <class P, class = void>
+struct post_inc_of { static constexpr bool value = false; };
+template <class P>
+struct post_inc_of<P, decltype((void)P::POST_INC)> { static constexpr bool value = P::POST_INC; };
 
 /* index of term t in the group's sorted list, or QUERY_NO_TERM */
 __device__ __forceinline__ uint32_t gterm_find(const uint32_t* gterm, uint32_t n, uint32_t t) {
@@ -69,25 +77,29 @@ struct GTab {
     const uint32_t* post_off;
     const uint32_t* post_q;
     const W* post_w;
+    const uint32_t* post_inc;
 };
 /* no barrier of its own: filter_build's barriers follow.  lds is 8-byte aligned and the host
  * put binary64 weights at an even word of the block. */
-template <class W>
-__device__ __forceinline__ GTab<W> tab_stage(const DocScanArgs& a, uint32_t* lds) {
-    GTab<W> t{a.gterm, a.post_off, a.post_q, (const W*)a.post_w};
+template <class P>
+__device__ __forceinline__ GTab<typename P::W> tab_stage(const typename P::Args& a, uint32_t* lds) {
+    using W = typename P::W;
+    GTab<W> t{a.gterm, a.post_off, a.post_q, (const W*)a.post_w, nullptr};
+    if constexpr (post_inc_of<P>::value) t.post_inc = a.post_inc;
     if (a.tab_words != 0u && a.tab_words <= QTAB_WORDS) {
         for (uint32_t i = threadIdx.x; i < a.tab_words; i += NT) lds[i] = a.gterm[i];
         t.gterm = lds;
         t.post_off = lds + (a.post_off - a.gterm);
         t.post_q = lds + (a.post_q - a.gterm);
         t.post_w = (const W*)(lds + (a.post_w - a.gterm));
+        if constexpr (post_inc_of<P>::value) t.post_inc = lds + (a.post_inc - a.gterm);
     }
     return t;
 }
 
 /* one match added by its owner wave: lane x takes posting x of the term (a term's postings
  * name distinct queries, so the lanes of one pass never share an accumulator) */
-template <class W>
+template <bool INC, class W>
 __device__ __forceinline__ void add_match(const DocScanArgs& a, const GTab<W>& g, uint32_t ti, double v, double* wacc,
                                           uint32_t* wcnt, uint32_t lane) {
     const uint32_t p0 = g.post_off[ti], p1 = g.post_off[ti + 1];
@@ -96,7 +108,7 @@ __device__ __forceinline__ void add_match(const DocScanArgs& a, const GTab<W>& g
         if (q < a.nq) {
             const double prod = (double)g.post_w[x] * v;
             wacc[q] = wacc[q] + prod;
-            wcnt[q] += 1u;
+            wcnt[q] += INC ? g.post_inc[x] : 1u;
         }
     }
     wave_lds_order();
@@ -132,7 +144,7 @@ __global__ __launch_bounds__(NT) void k_doc_score(const typename P::Args a) {
     __shared__ double acc_s[NT / 64][QG_MAX];
     __shared__ uint32_t cnt_s[NT / 64][QG_MAX];
     __shared__ uint32_t tab_s[QTAB_WORDS] __attribute__((aligned(8)));
-    const GTab<typename P::W> g = tab_stage<typename P::W>(a, tab_s);
+    const GTab<typename P::W> g = tab_stage<P>(a, tab_s);
     filter_build(a, filt);
     const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
     double* wacc = acc_s[wv];
@@ -169,7 +181,7 @@ __global__ __launch_bounds__(NT) void k_doc_score(const typename P::Args a) {
                 while (m) {   /* the round's matches in pair order */
                     const int l = __builtin_ctzll(m);
                     m &= m - 1ull;
-                    add_match(a, g, (uint32_t)__shfl((int)ti, l, 64), __shfl(v, l, 64), wacc, wcnt, lane);
+                    add_match<post_inc_of<P>::value>(a, g, (uint32_t)__shfl((int)ti, l, 64), __shfl(v, l, 64), wacc, wcnt, lane);
                 }
             }
         }
@@ -187,7 +199,7 @@ __global__ __launch_bounds__(NT) void k_doc_score_big(const typename P::Args a) 
     __shared__ double m_v[NT];
     __shared__ uint32_t wsum[NT / 64];
     __shared__ uint32_t tab_s[QTAB_WORDS] __attribute__((aligned(8)));
-    const GTab<typename P::W> g = tab_stage<typename P::W>(a, tab_s);
+    const GTab<typename P::W> g = tab_stage<P>(a, tab_s);
     filter_build(a, filt);
     const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
     uint32_t nbig = *a.big_count;
@@ -215,7 +227,7 @@ __global__ __launch_bounds__(NT) void k_doc_score_big(const typename P::Args a) 
             if (hit) { m_ti[at] = ti; m_v[at] = P::value(a, d, pp); }
             __syncthreads();
             if (wv == 0)
-                for (uint32_t x = 0; x < total; ++x) add_match(a, g, m_ti[x], m_v[x], acc_s, cnt_s, lane);
+                for (uint32_t x = 0; x < total; ++x) add_match<post_inc_of<P>::value>(a, g, m_ti[x], m_v[x], acc_s, cnt_s, lane);
             __syncthreads();
         }
         if (wv == 0) write_doc(a, j, acc_s, cnt_s, lane);

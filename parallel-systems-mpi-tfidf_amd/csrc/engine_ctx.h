@@ -6,7 +6,7 @@
  * File map (each add-on file drives the .hip file of the same name):
  *   engine.cpp            context open/close, comm, the DF exchange, run_*, the idf pool, fetch,
  *                         synth, format and output writing: the measured pipeline of tfidf_run
- *   engine_query.cpp      tfidf_query, tfidf_query_bm25 (query.hip, bm25.hip); the topk_* driver
+ *   engine_query.cpp      tfidf_query, tfidf_query_bm25, tfidf_query_clauses (query.hip, bm25.hip); the topk_* driver
  *   engine_transform.cpp  tfidf_transform
  *   engine_text.cpp       tfidf_analyze, tfidf_ngrams (analyze.hip, ngram.hip); corpus intake and
  *                         token bounds, shared with tfidf_transform
@@ -241,6 +241,7 @@ struct tfidf_ctx {
     uint64_t bm25_L = 0;
     bool bm25_L_valid = false;
     tfidf_bm25_info binfo{};
+    tfidf_clause_info cinfo{};                  /* tfidf_query_clauses: tfidf_query's buffers too */
     /* per-document top-k terms (tfidf_top_terms, terms.hip): the requested ids and their output
      * positions, a batch's per-row words (npairs, nterms, id), its k entries per row (score
      * bits, pair, term, count, word length -> offset), the gathered words, the list of long
@@ -562,7 +563,7 @@ struct TopkCand {
 TopkPlan topk_plan(uint32_t N, uint32_t k, uint32_t rows, uint64_t acc_bytes);
 int topk_ensure(tfidf_ctx* ctx, const TopkPlan& p, uint32_t N);
 int topk_rounds(tfidf_ctx* ctx, const TopkPlan& p, const double* acc, const uint32_t* cnt, uint32_t N, uint32_t k,
-                uint32_t gn, unsigned long long* d_nm, TopkCand* res);
+                uint32_t gn, unsigned long long* d_nm, TopkCand* res, const uint32_t* need = nullptr);
 int topk_read_back(tfidf_ctx* ctx, const TopkCand& res, const unsigned long long* d_nm, uint32_t gn, uint32_t k,
                    uint64_t* h_s, uint32_t* h_id, uint32_t* h_n, uint64_t* h_nm);
 

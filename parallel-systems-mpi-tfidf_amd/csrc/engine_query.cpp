@@ -1,6 +1,6 @@
 /*
- * engine_query.cpp — tfidf_query, tfidf_query_bm25 and the top-k driver they share with
- * tfidf_similar (query.hip, bm25.hip).
+ * engine_query.cpp — tfidf_query, tfidf_query_bm25, tfidf_query_clauses and the top-k driver they
+ * share with tfidf_similar (query.hip, bm25.hip).
  * The context and the helpers every engine file shares: engine_ctx.h.
  */
 #include <float.h>
@@ -96,13 +96,14 @@ static TopkCand topk_cand(tfidf_ctx* ctx, const TopkPlan& p, int c) {
 /* the top-k rounds of a group of gn queries (rows): the accumulators' slices, then the slices'
  * lists until one is left per query: row q = entries [q * k, q * k + n[q]) of *res */
 int topk_rounds(tfidf_ctx* ctx, const TopkPlan& p, const double* acc, const uint32_t* cnt, uint32_t N, uint32_t k,
-                uint32_t gn, unsigned long long* d_nm, TopkCand* res) {
+                uint32_t gn, unsigned long long* d_nm, TopkCand* res, const uint32_t* need) {
     hipStream_t s = ctx->stream;
     int cur = 0;
     TopkCand o = topk_cand(ctx, p, cur);
     QTopkArgs ta{};
     ta.acc = acc;
     ta.cnt = cnt;
+    ta.need = need;
     ta.order = ctx->order;
     ta.doc_ids = ctx->dev_ids;
     ta.n_in = N;
@@ -148,15 +149,45 @@ int topk_read_back(tfidf_ctx* ctx, const TopkCand& res, const unsigned long long
     return TFIDF_OK;
 }
 
-int tfidf_ctx_query(tfidf_ctx* ctx, const tfidf_queries* qs, uint32_t k, tfidf_hits* out, std::vector<uint8_t>* found_out,
-                    std::vector<uint64_t>* found_off_out, const Bm25Call* bm) {
-    if (!ctx || !qs || !out) return TFIDF_E_INVAL;
-    if (k == 0 || k > TFIDF_QUERY_MAX_K || qs->nqueries > TFIDF_QUERY_MAX_QUERIES) return TFIDF_E_INVAL;
+/* a batch as tfidf_query takes it */
+static int queries_check(const tfidf_queries* qs) {
+    if (!qs || qs->nqueries > TFIDF_QUERY_MAX_QUERIES) return TFIDF_E_INVAL;
     const uint32_t nq = qs->nqueries;
     if (nq && !qs->q_off) return TFIDF_E_INVAL;
     for (uint32_t q = 0; q < nq; ++q)
         if (qs->q_off[q] > qs->q_off[q + 1]) return TFIDF_E_INVAL;
     if (nq && (qs->q_off[nq] > qs->nbytes || (qs->q_off[nq] > qs->q_off[0] && !qs->bytes))) return TFIDF_E_INVAL;
+    return TFIDF_OK;
+}
+
+/* f(term bytes, length) for every token of query q of the batch, in order: tokens are maximal
+ * runs of non-whitespace, a term is the token up to its first NUL (strcmp semantics) */
+template <class F>
+static void for_each_term(const tfidf_queries* qs, uint32_t q, F f) {
+    const uint8_t* b = qs->bytes;
+    const uint64_t e = qs->q_off[q + 1];
+    for (uint64_t i = qs->q_off[q]; i < e;) {
+        while (i < e && query_is_ws(b[i])) ++i;
+        if (i >= e) break;
+        const uint64_t t0 = i;
+        while (i < e && !query_is_ws(b[i])) ++i;
+        uint64_t tl = 0;
+        while (t0 + tl < i && b[t0 + tl] != 0) ++tl;
+        f((const char*)b + t0, (size_t)tl);
+    }
+}
+
+/* with a clause plan (cl) qs is unused: the batch is the plan's three texts, a posting carries
+ * the increment of its clause kinds and the first top-k round tests the count word against
+ * need[q]; everything else is the one path */
+int tfidf_ctx_query(tfidf_ctx* ctx, const tfidf_queries* qs, uint32_t k, tfidf_hits* out, std::vector<uint8_t>* found_out,
+                    std::vector<uint64_t>* found_off_out, const Bm25Call* bm, const ClausePlan* cl) {
+    if (!ctx || (!qs && !cl) || !out) return TFIDF_E_INVAL;
+    if (k == 0 || k > TFIDF_QUERY_MAX_K) return TFIDF_E_INVAL;
+    if (!cl) {
+        if (const int rc = queries_check(qs)) return rc;
+    }
+    const uint32_t nq = cl ? cl->nqueries : qs->nqueries;
     if (!ctx->have_result) return TFIDF_E_STATE;
     const auto wall0 = std::chrono::steady_clock::now();
     if (const int rc = call_begin(ctx, ctx->ev_q)) return rc;
@@ -189,28 +220,37 @@ int tfidf_ctx_query(tfidf_ctx* ctx, const tfidf_queries* qs, uint32_t k, tfidf_h
     std::unordered_map<std::string, uint32_t> term_id;
     std::vector<const std::string*> terms;
     std::vector<uint64_t> qt_off((size_t)nq + 1, 0);
-    std::vector<uint32_t> qt_term, qt_w;
+    std::vector<uint32_t> qt_term, qt_w, qt_inc;   /* qt_inc: clauses only, the CL_INC_* of the term's texts, summed */
     for (uint32_t q = 0; q < nq; ++q) {
-        const uint8_t* b = qs->bytes;
-        const uint64_t e = qs->q_off[q + 1];
         std::unordered_map<uint32_t, size_t> seen;
-        for (uint64_t i = qs->q_off[q]; i < e;) {
-            while (i < e && query_is_ws(b[i])) ++i;
-            if (i >= e) break;
-            const uint64_t t0 = i;
-            while (i < e && !query_is_ws(b[i])) ++i;
-            uint64_t tl = 0;
-            while (t0 + tl < i && b[t0 + tl] != 0) ++tl;   /* strcmp semantics: up to the first NUL */
-            auto ins = term_id.emplace(std::string((const char*)b + t0, (size_t)tl), (uint32_t)terms.size());
+        /* a token of a text that scores (w += 1) or of the must_not text; inc: the text's CL_INC_* */
+        auto token = [&](const char* p, size_t n, uint32_t inc) {
+            auto ins = term_id.emplace(std::string(p, n), (uint32_t)terms.size());
             if (ins.second) terms.push_back(&ins.first->first);
             auto at = seen.emplace(ins.first->second, qt_term.size());
-            if (at.second) { qt_term.push_back(ins.first->second); qt_w.push_back(1u); }
-            else if (qt_w[at.first->second] != 0xFFFFFFFFu) ++qt_w[at.first->second];
+            const bool scores = inc != CL_INC_NOT;
+            if (at.second) {
+                qt_term.push_back(ins.first->second);
+                qt_w.push_back(scores ? 1u : 0u);
+                if (cl) qt_inc.push_back(inc);
+                return;
+            }
+            const size_t x = at.first->second;
+            if (scores && qt_w[x] != 0xFFFFFFFFu) ++qt_w[x];
+            const uint32_t field = inc == CL_INC_NOT ? 0xFF000000u : inc * CL_FIELD;
+            if (cl && !(qt_inc[x] & field)) qt_inc[x] += inc;   /* once per text */
+        };
+        if (!cl) {
+            for_each_term(qs, q, [&](const char* p, size_t n) { token(p, n, CL_INC_SHOULD); });
+        } else {   /* the numbering every rank shares: must text, should text, then what is only in must_not */
+            if (cl->must) for_each_term(cl->must, q, [&](const char* p, size_t n) { token(p, n, CL_INC_MUST); });
+            if (cl->should) for_each_term(cl->should, q, [&](const char* p, size_t n) { token(p, n, CL_INC_SHOULD); });
+            if (cl->must_not) for_each_term(cl->must_not, q, [&](const char* p, size_t n) { token(p, n, CL_INC_NOT); });
         }
         qt_off[q + 1] = qt_term.size();
     }
     const uint32_t nT = (uint32_t)terms.size();
-    tfidf_query_info qi{};
+    tfidf_clause_info qi{};   /* the widest of the three infos: the call's own is cut from it below */
     qi.nqueries = nq;
     qi.k = k;
     qi.nterms = nT;
@@ -255,10 +295,30 @@ int tfidf_ctx_query(tfidf_ctx* ctx, const tfidf_queries* qs, uint32_t k, tfidf_h
     if (found_off_out) *found_off_out = qt_off;
     for (uint32_t q = 0; q < nq; ++q)
         for (uint64_t x = qt_off[q]; x < qt_off[q + 1]; ++x)
-            if (rank[qt_term[x]] != QUERY_NO_TERM) {
+            if (rank[qt_term[x]] != QUERY_NO_TERM && qt_w[x] != 0u) {   /* w = 0: only in the must_not text */
                 ++out->nterms_found[q];
                 if (found_out) (*found_out)[x] = 1;
             }
+
+    /* ---- clauses: need[q] = |M| << 12 | m, and the queries no document of this shard can satisfy ---- */
+    std::vector<uint32_t> need(cl ? nq : 0, 0u);
+    std::vector<uint8_t> dropped(cl ? nq : 0, 0);
+    for (uint32_t q = 0; cl && q < nq; ++q) {
+        uint32_t nM = 0, nS = 0;
+        bool bad = false;
+        for (uint64_t x = qt_off[q]; x < qt_off[q + 1]; ++x) {
+            const uint32_t inc = qt_inc[x];
+            const bool must = (inc >> 12) & CL_FIELD;
+            nM += must;
+            nS += (inc & CL_FIELD) != 0u;
+            bad = bad || (must && (rank[qt_term[x]] == QUERY_NO_TERM || (inc >> 24)));
+        }
+        const uint32_t m = cl->min_should ? cl->min_should[q] : 0u;
+        if (nM > TFIDF_CLAUSE_MAX_TERMS || nS > TFIDF_CLAUSE_MAX_TERMS || m > TFIDF_CLAUSE_MAX_TERMS) return TFIDF_E_INVAL;
+        need[q] = nM << 12 | m;
+        dropped[q] = bad || m > nS;
+        qi.nq_unsatisfiable += dropped[q];
+    }
 
     /* ---- BM25: idf per distinct found term, the host's libm log (one operation per line) ---- */
     std::vector<double> idf(bm ? nT : 0, 0.0);
@@ -286,15 +346,18 @@ int tfidf_ctx_query(tfidf_ctx* ctx, const tfidf_queries* qs, uint32_t k, tfidf_h
     }
     std::vector<uint64_t> h_s((size_t)G * k), h_nm(G);
     std::vector<uint32_t> h_id((size_t)G * k), h_n(G);
-    struct Post { uint32_t rank, q, w, term; };
+    struct Post { uint32_t rank, q, w, term, inc; };
     std::vector<Post> posts;
     std::vector<uint32_t> tab;
     for (uint32_t g0 = 0; N && g0 < nq; g0 += (uint32_t)G) {
         const uint32_t gn = nq - g0 < G ? nq - g0 : (uint32_t)G;
         posts.clear();
-        for (uint32_t q = 0; q < gn; ++q)
+        for (uint32_t q = 0; q < gn; ++q) {
+            if (cl && dropped[g0 + q]) continue;
             for (uint64_t x = qt_off[g0 + q]; x < qt_off[g0 + q + 1]; ++x)
-                if (rank[qt_term[x]] != QUERY_NO_TERM) posts.push_back(Post{rank[qt_term[x]], q, qt_w[x], qt_term[x]});
+                if (rank[qt_term[x]] != QUERY_NO_TERM)
+                    posts.push_back(Post{rank[qt_term[x]], q, qt_w[x], qt_term[x], cl ? qt_inc[x] : 1u});
+        }
         if (posts.empty()) continue;   /* no term of the group is in the vocabulary: no hits */
         if (posts.size() > 0x7FFFFFFFull) return TFIDF_E_CAPACITY;
         ++qi.ngroups;
@@ -303,18 +366,24 @@ int tfidf_ctx_query(tfidf_ctx* ctx, const tfidf_queries* qs, uint32_t k, tfidf_h
         uint32_t nG = 0;
         for (size_t i = 0; i < posts.size(); ++i) nG += i == 0 || posts[i].rank != posts[i - 1].rank;
         const uint32_t nP = (uint32_t)posts.size();
-        /* BM25: the weights are binary64 W(q,t) = fl(w * idf), at the next even word */
-        const size_t w_at = (size_t)2 * nG + 1 + nP + (bm ? (nP + 1) & 1u : 0u);
-        tab.assign(w_at + (bm ? 2 : 1) * (size_t)nP, 0);
+        /* clauses: the postings' increments behind their queries, and behind the table the group's
+         * need words.  BM25: the weights are binary64 W(q,t) = fl(w * idf), at the next even word */
+        const size_t inc_at = (size_t)2 * nG + 1 + nP, w_base = inc_at + (cl ? nP : 0u);
+        const size_t w_at = w_base + (bm ? w_base & 1u : 0u);
+        const size_t tab_words = w_at + (bm ? 2 : 1) * (size_t)nP;
+        tab.assign(tab_words + (cl ? gn : 0u), 0);
         uint32_t* gterm = tab.data();
         uint32_t* poff = gterm + nG;
         uint32_t* pq = poff + nG + 1;
         uint32_t* pw = gterm + w_at;
+        for (uint32_t q = 0; cl && q < gn; ++q) tab[tab_words + q] = need[g0 + q];
         for (uint32_t i = 0, t = 0; i < nP; ++i) {
             if (i == 0 || posts[i].rank != posts[i - 1].rank) { gterm[t] = posts[i].rank; poff[t] = i; ++t; }
             pq[i] = posts[i].q;
+            if (cl) gterm[inc_at + i] = posts[i].inc;
             if (bm) {
-                const double W = (double)posts[i].w * idf[posts[i].term];
+                /* a must_not-only posting: W = +0.0 whatever the idf, its product is +0.0 */
+                const double W = posts[i].w ? (double)posts[i].w * idf[posts[i].term] : 0.0;
                 memcpy(pw + 2 * (size_t)i, &W, 8);
             } else {
                 pw[i] = posts[i].w;
@@ -335,7 +404,8 @@ int tfidf_ctx_query(tfidf_ctx* ctx, const tfidf_queries* qs, uint32_t k, tfidf_h
         sa.post_off = sa.gterm + nG;
         sa.post_q = sa.post_off + nG + 1;
         sa.post_w = sa.gterm + w_at;
-        sa.tab_words = tab.size() <= 0xFFFFFFFFull ? (uint32_t)tab.size() : 0u;
+        sa.tab_words = tab_words <= 0xFFFFFFFFull ? (uint32_t)tab_words : 0u;
+        qi.ngroups_tab_lds += sa.tab_words != 0u && sa.tab_words <= QTAB_WORDS;
         sa.nq = gn;
         sa.acc = ctx->q_acc.as<double>();
         sa.cnt = ctx->q_cnt.as<uint32_t>();
@@ -353,16 +423,16 @@ int tfidf_ctx_query(tfidf_ctx* ctx, const tfidf_queries* qs, uint32_t k, tfidf_h
             ba.avgdl = avgdl;
             ba.k1_plus_1 = bm->k1 + 1.0;
             ba.one_minus_b = 1.0 - bm->b;
-            lrc = launch_bm25_score(ba, ctx->ncu, s);
+            lrc = cl ? launch_bm25_score_clauses(BClauseArgs{ba, sa.gterm + inc_at}, ctx->ncu, s) : launch_bm25_score(ba, ctx->ncu, s);
         } else {
             QScoreArgs ta{sa};
             ta.out_score = ctx->out_score.as<double>();
-            lrc = launch_query_score(ta, ctx->ncu, s);
+            lrc = cl ? launch_query_score_clauses(QClauseArgs{ta, sa.gterm + inc_at}, ctx->ncu, s) : launch_query_score(ta, ctx->ncu, s);
         }
         LAUNCH(lrc);
         HIPCHK(hipEventRecord(ctx->ev_q[1], s));
         TopkCand res{};
-        int rc = topk_rounds(ctx, plan, sa.acc, sa.cnt, N, k, gn, d_nm, &res);
+        int rc = topk_rounds(ctx, plan, sa.acc, sa.cnt, N, k, gn, d_nm, &res, cl ? sa.gterm + tab_words : nullptr);
         if (rc) return rc;
         HIPCHK(hipEventRecord(ctx->ev_q[2], s));
         rc = topk_read_back(ctx, res, d_nm, gn, k, h_s.data(), h_id.data(), h_n.data(), h_nm.data());
@@ -380,19 +450,19 @@ int tfidf_ctx_query(tfidf_ctx* ctx, const tfidf_queries* qs, uint32_t k, tfidf_h
         }
     }
     qi.ms_total = wall_ms(wall0);
-    if (bm) {
-        tfidf_bm25_info bi{};
-        bi.nqueries = qi.nqueries; bi.k = qi.k; bi.nterms = qi.nterms; bi.nterms_found = qi.nterms_found;
-        bi.ngroups = qi.ngroups; bi.group_queries = qi.group_queries; bi.acc_bytes = qi.acc_bytes;
-        bi.ms_lookup = qi.ms_lookup; bi.ms_score = qi.ms_score; bi.ms_topk = qi.ms_topk; bi.ms_total = qi.ms_total;
-        bi.avgdl = avgdl;
-        ctx->binfo = bi;
-    } else {
-        ctx->qinfo = qi;
-    }
+    qi.avgdl = avgdl;
+    /* the three infos share their leading fields (static_asserts below) */
+    if (cl) ctx->cinfo = qi;
+    else if (bm) memcpy(&ctx->binfo, &qi, sizeof(ctx->binfo));
+    else memcpy(&ctx->qinfo, &qi, sizeof(ctx->qinfo));
     guard.h = nullptr;
     return TFIDF_OK;
 }
+
+static_assert(offsetof(tfidf_clause_info, avgdl) == offsetof(tfidf_bm25_info, avgdl) &&
+                  offsetof(tfidf_bm25_info, avgdl) == sizeof(tfidf_query_info) &&
+                  offsetof(tfidf_clause_info, nq_unsatisfiable) == sizeof(tfidf_bm25_info),
+              "tfidf_clause_info extends tfidf_bm25_info, which extends tfidf_query_info");
 
 extern "C" int tfidf_query(tfidf_ctx* ctx, const tfidf_queries* queries, uint32_t k, tfidf_hits* out) {
     return tfidf_ctx_query(ctx, queries, k, out, nullptr, nullptr);
@@ -413,4 +483,53 @@ extern "C" int tfidf_last_bm25_info(const tfidf_ctx* ctx, tfidf_bm25_info* info)
 
 extern "C" int tfidf_last_query_info(const tfidf_ctx* ctx, tfidf_query_info* info) {
     return ctx ? copy_info(info, ctx->qinfo) : TFIDF_E_INVAL;
+}
+
+/* ------------------------------------------------------------------ clauses ---- */
+
+int tfidf_clause_plan(const tfidf_clauses* c, ClausePlan* plan, Bm25Call* bm, bool* has_bm) {
+    if (!c || c->size < sizeof(tfidf_clauses)) return TFIDF_E_INVAL;
+    if (c->ranking != TFIDF_RANK_TFIDF && c->ranking != TFIDF_RANK_BM25) return TFIDF_E_INVAL;
+    if (c->nqueries > TFIDF_QUERY_MAX_QUERIES) return TFIDF_E_INVAL;
+    if (c->ranking == TFIDF_RANK_TFIDF && c->bm25) return TFIDF_E_INVAL;
+    *has_bm = c->ranking == TFIDF_RANK_BM25;
+    if (*has_bm) {
+        if (const int rc = tfidf_bm25_params_check(c->bm25, bm)) return rc;
+    }
+    const tfidf_queries* text[3] = {c->must, c->should, c->must_not};
+    const size_t limit[3] = {TFIDF_CLAUSE_MAX_TERMS, TFIDF_CLAUSE_MAX_TERMS, TFIDF_CLAUSE_MAX_NOT};
+    for (int i = 0; i < 3; ++i) {
+        if (!text[i]) continue;
+        if (text[i]->nqueries != c->nqueries || queries_check(text[i])) return TFIDF_E_INVAL;
+        for (uint32_t q = 0; q < c->nqueries; ++q) {
+            std::unordered_map<std::string, int> distinct;
+            for_each_term(text[i], q, [&](const char* p, size_t n) { distinct.emplace(std::string(p, n), 0); });
+            if (distinct.size() > limit[i]) return TFIDF_E_INVAL;
+        }
+    }
+    for (uint32_t q = 0; c->min_should && q < c->nqueries; ++q)
+        if (c->min_should[q] > TFIDF_CLAUSE_MAX_TERMS) return TFIDF_E_INVAL;
+    *plan = ClausePlan{c->nqueries, c->must, c->should, c->must_not, c->min_should};
+    return TFIDF_OK;
+}
+
+extern "C" int tfidf_clauses_check(const tfidf_clauses* clauses) {
+    ClausePlan plan{};
+    Bm25Call bm{};
+    bool has_bm = false;
+    return tfidf_clause_plan(clauses, &plan, &bm, &has_bm);
+}
+
+extern "C" int tfidf_query_clauses(tfidf_ctx* ctx, const tfidf_clauses* clauses, uint32_t k, tfidf_hits* out) {
+    if (out) memset(out, 0, sizeof(*out));
+    if (!ctx || !clauses || !out) return TFIDF_E_INVAL;
+    ClausePlan plan{};
+    Bm25Call bm{};
+    bool has_bm = false;
+    if (const int rc = tfidf_clause_plan(clauses, &plan, &bm, &has_bm)) return rc;
+    return tfidf_ctx_query(ctx, nullptr, k, out, nullptr, nullptr, has_bm ? &bm : nullptr, &plan);
+}
+
+extern "C" int tfidf_last_clause_info(const tfidf_ctx* ctx, tfidf_clause_info* info) {
+    return ctx ? copy_info(info, ctx->cinfo) : TFIDF_E_INVAL;
 }

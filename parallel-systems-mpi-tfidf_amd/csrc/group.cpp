@@ -608,8 +608,9 @@ int tfidf_group_write_output(tfidf_group* g, const char* path) {
  * rank as in tfidf_group_run; the rows are merged here by (score descending, document id
  * ascending).  The shards partition the documents, so a document of the global top-k is in
  * its shard's top-k and the merge is exact. */
-static int group_query(tfidf_group* g, const tfidf_queries* queries, uint32_t k, tfidf_hits* out, const Bm25Call* bm) {
-    if (!g || !queries || !out) return TFIDF_E_INVAL;
+static int group_query(tfidf_group* g, const tfidf_queries* queries, uint32_t k, tfidf_hits* out, const Bm25Call* bm,
+                       const ClausePlan* cl = nullptr) {
+    if (!g || (!queries && !cl) || !out) return TFIDF_E_INVAL;
     const int R = g->n;
     std::vector<int> rc((size_t)R, TFIDF_OK);
     std::vector<tfidf_hits> part((size_t)R);
@@ -619,13 +620,13 @@ static int group_query(tfidf_group* g, const tfidf_queries* queries, uint32_t k,
     {
         std::vector<std::thread> th;
         for (int r = 1; r < R; ++r)
-            th.emplace_back([&, r] { rc[r] = tfidf_ctx_query(g->ctx[r], queries, k, &part[r], &found[r], &foff[r], bm); });
-        rc[0] = tfidf_ctx_query(g->ctx[0], queries, k, &part[0], &found[0], &foff[0], bm);
+            th.emplace_back([&, r] { rc[r] = tfidf_ctx_query(g->ctx[r], queries, k, &part[r], &found[r], &foff[r], bm, cl); });
+        rc[0] = tfidf_ctx_query(g->ctx[0], queries, k, &part[0], &found[0], &foff[0], bm, cl);
         for (auto& t : th) t.join();
     }
     int err = TFIDF_OK;
     for (int r = 0; r < R && !err; ++r) err = rc[r];
-    const uint32_t nq = queries->nqueries;
+    const uint32_t nq = cl ? cl->nqueries : queries->nqueries;
     tfidf_hits m;
     memset(&m, 0, sizeof(m));
     if (!err) {
@@ -683,24 +684,47 @@ int tfidf_group_query(tfidf_group* g, const tfidf_queries* queries, uint32_t k, 
 /* BM25 over every shard: with avgdl = 0 the ranks' L and n are summed here (exact integers,
  * one division) and every rank scores with the same avgdl; df and N are the run's global
  * ones, so a document's score is the single-shard run's and the merge is exact. */
+static int group_avgdl(tfidf_group* g, Bm25Call* bm) {
+    if (bm->avgdl > 0.0) return TFIDF_OK;
+    uint64_t L = 0, n = 0;
+    for (int r = 0; r < g->n; ++r) {
+        uint64_t l = 0, m = 0;
+        const int rc = tfidf_ctx_bm25_lengths(g->ctx[r], &l, &m);
+        if (rc) return rc;
+        L += l;
+        n += m;
+    }
+    if (L) bm->avgdl = (double)L / (double)n;   /* L = 0: no rank has a pair, every row is empty */
+    return TFIDF_OK;
+}
+
 int tfidf_group_query_bm25(tfidf_group* g, const tfidf_queries* queries, uint32_t k, const tfidf_bm25_params* params,
                            tfidf_hits* out) {
     if (!g || !queries || !out) return TFIDF_E_INVAL;
     Bm25Call bm{};
     int rc = tfidf_bm25_params_check(params, &bm);
     if (rc) return rc;
-    if (!(bm.avgdl > 0.0)) {
-        uint64_t L = 0, n = 0;
-        for (int r = 0; r < g->n; ++r) {
-            uint64_t l = 0, m = 0;
-            rc = tfidf_ctx_bm25_lengths(g->ctx[r], &l, &m);
-            if (rc) return rc;
-            L += l;
-            n += m;
-        }
-        if (L) bm.avgdl = (double)L / (double)n;   /* L = 0: no rank has a pair, every row is empty */
-    }
+    rc = group_avgdl(g, &bm);
+    if (rc) return rc;
     return group_query(g, queries, k, out, &bm);
+}
+
+/* Clauses over every shard: the conditions are decided per document and the shards partition
+ * the documents, so the merge of tfidf_group_query is exact here too.  A must term that one
+ * shard's vocabulary lacks drops the query on that shard alone: none of its documents holds it. */
+int tfidf_group_query_clauses(tfidf_group* g, const tfidf_clauses* clauses, uint32_t k, tfidf_hits* out) {
+    if (out) memset(out, 0, sizeof(*out));
+    if (!g || !clauses || !out) return TFIDF_E_INVAL;
+    ClausePlan plan{};
+    Bm25Call bm{};
+    bool has_bm = false;
+    int rc = tfidf_clause_plan(clauses, &plan, &bm, &has_bm);
+    if (rc) return rc;
+    if (has_bm) {
+        rc = group_avgdl(g, &bm);
+        if (rc) return rc;
+    }
+    return group_query(g, nullptr, k, out, has_bm ? &bm : nullptr, &plan);
 }
 
 /* Every rank selects on its own host thread (tfidf_top_terms is local to a context).  NULL

@@ -392,6 +392,7 @@ int launch_format_f64(const double* v, uint64_t n, uint8_t* out, uint32_t* statu
 #define QG_MAX        64u      /* queries per scoring pass: one accumulator per lane of the owner wave */
 #define QS_BIG        4096u    /* documents over this many pairs: a workgroup each (K5_MAX_PAIRS's cut) */
 #define QT_SLICE      4096u    /* candidates a top-k workgroup sorts in LDS (> TFIDF_QUERY_MAX_K) */
+#define QTAB_WORDS    4096u    /* a group's table is staged in LDS when it has at most this many u32 words (16 KiB) */
 #define QUERY_NO_TERM 0xFFFFFFFFu
 /* distinct query terms -> term ranks (QUERY_NO_TERM: not in this shard's vocabulary) */
 struct QLookupArgs {
@@ -413,8 +414,8 @@ int launch_query_lookup(const QLookupArgs& a, hipStream_t s);
  * ranking function shares: gterm = the group's sorted distinct term ranks, term i's postings
  * (query in the group, weight) at [post_off[i], post_off[i + 1]); acc / cnt are written for
  * every (query, output position): [nq][ndocs].  The table is one block from gterm on: gterm,
- * post_off, post_q as u32 words, then the weights in the ranking function's type (u32, or
- * binary64 at an even word). */
+ * post_off, post_q as u32 words, with clauses post_inc (one u32 per posting), then the weights
+ * in the ranking function's type (u32, or binary64 at an even word). */
 struct DocScanArgs {
     const uint64_t* out_off;
     const uint32_t* out_term;
@@ -437,13 +438,27 @@ struct QScoreArgs : DocScanArgs {
     const double* out_score;
 };
 int launch_query_score(const QScoreArgs& a, uint32_t ncu, hipStream_t s);
+/* Clauses (tfidf_query_clauses): a posting's increment of the count word, one field per clause
+ * kind, and the word a document's count is tested against: 12 + 12 + 8 bits. */
+#define CL_INC_SHOULD 1u
+#define CL_INC_MUST   (1u << 12)
+#define CL_INC_NOT    (1u << 24)
+#define CL_FIELD      0xFFFu
+/* the same pass where a match adds its posting's post_inc to cnt instead of 1: one u32 per
+ * posting (the CL_INC_* of the term's clause kinds, summed), inside the table's block */
+struct QClauseArgs : QScoreArgs {
+    const uint32_t* post_inc;
+};
+int launch_query_score_clauses(const QClauseArgs& a, uint32_t ncu, hipStream_t s);
 /* one top-k round: per (query, slice of QT_SLICE inputs) the best kk in order.  First round
- * (acc != null): the inputs are the output positions, hits where cnt != 0, ids through
+ * (acc != null): the inputs are the output positions, hits where cnt != 0 (need == null) or
+ * where cnt passes the clause test against need[q] = |M| << 12 | min_should, ids through
  * order / doc_ids (null: index + 1), nmatch[q] += the slice's hits.  Later rounds: in_slices
  * lists of kk (score bits, id) with in_n valid entries each.  out_*: [nq][out_slices][kk] */
 struct QTopkArgs {
     const double* acc;
     const uint32_t* cnt;
+    const uint32_t* need;        /* first round: per query of the group, or null */
     const uint32_t* order;
     const uint32_t* doc_ids;
     const uint64_t* in_s;
@@ -474,6 +489,10 @@ struct BScoreArgs : DocScanArgs {
     double one_minus_b;          /* fl(1.0 - b) */
 };
 int launch_bm25_score(const BScoreArgs& a, uint32_t ncu, hipStream_t s);
+struct BClauseArgs : BScoreArgs {
+    const uint32_t* post_inc;    /* as QClauseArgs */
+};
+int launch_bm25_score_clauses(const BClauseArgs& a, uint32_t ncu, hipStream_t s);
 
 /* ---- per-document top-k terms over the resident result (terms.hip, tfidf_top_terms) ---- */
 #define TERMS_NO_POS 0xFFFFFFFFu

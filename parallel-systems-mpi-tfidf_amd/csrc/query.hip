@@ -59,7 +59,24 @@ struct TfidfScore {
     static __device__ __forceinline__ double value(const Args& a, const Doc&, uint64_t pp) { return gload(a.out_score + pp); }
 };
 
+/* the same with clauses: a match adds its posting's increment to the document's count word */
+struct TfidfClauseScore : TfidfScore {
+    using Args = QClauseArgs;
+    static constexpr bool POST_INC = true;
+};
+
 /* ------------------------------------------------------------------- top-k -- */
+
+/* the first round's test of a document's count word.  Without clauses: any match.  With them
+ * (CLAUSES, n = need[q] = |M| << 12 | min_should): no must_not term, every must term, enough
+ * should terms, and at least one scoring term.  A template parameter of the kernel, so that the
+ * rounds of tfidf_query, tfidf_query_bm25 and tfidf_similar are the code they were. */
+template <bool CLAUSES>
+__device__ __forceinline__ bool hit_valid(uint32_t cnt, uint32_t n) {
+    if (!CLAUSES) return cnt != 0u;
+    return (cnt >> 24) == 0u && ((cnt >> 12) & CL_FIELD) == (n >> 12) && (cnt & CL_FIELD) >= (n & CL_FIELD) &&
+           (cnt & 0xFFFFFFu) != 0u;
+}
 
 /* a before b: score descending, then document id ascending.  Keys are the scores' bit
  * patterns + 1 (scores are >= +0.0 and finite: the patterns order like the values and the
@@ -68,6 +85,7 @@ __device__ __forceinline__ bool hit_before(uint64_t sa, uint32_t ia, uint64_t sb
     return sa > sb || (sa == sb && ia < ib);
 }
 
+template <bool CLAUSES>
 __global__ __launch_bounds__(NT) void k_query_topk(const QTopkArgs a) {
     __shared__ uint64_t ls[QT_SLICE];
     __shared__ uint32_t lid[QT_SLICE];
@@ -75,6 +93,7 @@ __global__ __launch_bounds__(NT) void k_query_topk(const QTopkArgs a) {
     const uint32_t slice = blockIdx.x, q = blockIdx.y;
     if (threadIdx.x == 0) lcount = 0u;
     __syncthreads();
+    const uint32_t need = CLAUSES ? a.need[q] : 0u;
     const uint64_t e0 = (uint64_t)slice * QT_SLICE;
     const uint64_t e1 = e0 + QT_SLICE < a.n_in ? e0 + QT_SLICE : a.n_in;
     for (uint64_t e = e0 + threadIdx.x; e < e1; e += NT) {
@@ -83,7 +102,7 @@ __global__ __launch_bounds__(NT) void k_query_topk(const QTopkArgs a) {
         uint32_t id = 0;
         const uint64_t at = (uint64_t)q * a.n_in + e;
         if (a.acc) {   /* first round: the dense accumulators, e = output position */
-            valid = a.cnt[at] != 0u;
+            valid = hit_valid<CLAUSES>(a.cnt[at], need);
             if (valid) {
                 s = (uint64_t)__double_as_longlong(a.acc[at]);
                 id = doc_id_at(a.order, a.doc_ids, (uint32_t)e);
@@ -145,8 +164,14 @@ int launch_query_lookup(const QLookupArgs& a, hipStream_t s) {
 
 int launch_query_score(const QScoreArgs& a, uint32_t ncu, hipStream_t s) { return docscan::launch_score<TfidfScore>(a, ncu, s); }
 
+int launch_query_score_clauses(const QClauseArgs& a, uint32_t ncu, hipStream_t s) {
+    if (!a.post_inc) return -1;
+    return docscan::launch_score<TfidfClauseScore>(a, ncu, s);
+}
+
 int launch_query_topk(const QTopkArgs& a, uint32_t nq, hipStream_t s) {
     if (!nq || !a.out_slices) return 0;
-    k_query_topk<<<dim3(a.out_slices, nq), NT, 0, s>>>(a);
+    if (a.acc && a.need) k_query_topk<true><<<dim3(a.out_slices, nq), NT, 0, s>>>(a);
+    else k_query_topk<false><<<dim3(a.out_slices, nq), NT, 0, s>>>(a);
     return ok();
 }

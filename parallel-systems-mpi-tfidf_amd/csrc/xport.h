@@ -63,8 +63,22 @@ hipStream_t tfidf_ctx_stream(const tfidf_ctx* ctx);
  * found[found_off[q] + i] for the i-th distinct term of query q in first-occurrence order
  * (the same numbering on every rank: tfidf_group_query counts a term found by any rank once) */
 struct Bm25Call;
+struct ClausePlan;
 int tfidf_ctx_query(tfidf_ctx* ctx, const tfidf_queries* queries, uint32_t k, tfidf_hits* out,
-                    std::vector<uint8_t>* found, std::vector<uint64_t>* found_off, const Bm25Call* bm = nullptr);
+                    std::vector<uint8_t>* found, std::vector<uint64_t>* found_off, const Bm25Call* bm = nullptr,
+                    const ClausePlan* clauses = nullptr);
+/* engine_query.cpp: tfidf_query_clauses is tfidf_ctx_query with a clause plan (`queries` is then
+ * unused): the three texts of a checked tfidf_clauses.  The numbering behind found / found_off is
+ * per query the must text's terms, then the should text's, then the terms that are only in the
+ * must_not text (never found: they are no scoring terms).  The counters go to
+ * tfidf_last_clause_info. */
+struct ClausePlan {
+    uint32_t nqueries;
+    const tfidf_queries *must, *should, *must_not;   /* null: empty in every query */
+    const uint32_t* min_should;                      /* or null */
+};
+/* the plan and the BM25 call (*has_bm) of checked clauses; TFIDF_E_INVAL as tfidf_clauses_check */
+int tfidf_clause_plan(const tfidf_clauses* c, ClausePlan* plan, Bm25Call* bm, bool* has_bm);
 /* engine_query.cpp: tfidf_query_bm25 is tfidf_ctx_query with validated parameters (bm non-null: the
  * scoring pass is bm25.hip's, the counters go to tfidf_last_bm25_info).  avgdl 0: this
  * context's own average */

@@ -32,7 +32,18 @@
  *   --bm25-b Y    its length normalisation (default 0.75, 0 <= Y <= 1); the average document
  *                 length is the corpus's own.  Either parameter implies --bm25; any of the
  *                 three without --query is a usage error (exit 2).
- * With several shards the ranks' hits are merged (tfidf_group_query / tfidf_group_query_bm25).
+ *   --query-ops   clauses (tfidf_query_clauses; host/query_ops.h): a token "+word" of a line must
+ *                 occur in a hit, a token "-word" must not, every other token scores as before.
+ *                 The operators are read before the analyzer and the n-grams, which then see
+ *                 the three texts: --strip-punct never sees them ("+Fox," under --lower
+ *                 --strip-punct requires "fox"), and under --ngrams 2 "+new +york" requires the
+ *                 phrase new_york (and both words);
+ *   --query-all   every token must occur; with --query-ops, every token without an operator;
+ *   --min-match M at least M (0..4095) of a line's plain tokens' distinct terms must occur.
+ *                 Each of the three implies the clause call, works with --bm25 and keeps the
+ *                 hits file's format; without --query each is a usage error (exit 2).
+ * With several shards the ranks' hits are merged (tfidf_group_query / tfidf_group_query_bm25 /
+ * tfidf_group_query_clauses).
  *
  * Keywords (the k best-scoring words of every document, tfidf_top_terms):
  *   --keywords K          after output.txt (and after the hits file of --query), one line
@@ -195,6 +206,7 @@
 
 #include "../../include/tfidf.h"
 #include "labels_file.h"
+#include "query_ops.h"
 
 static double wall_ms(void) {
     struct timespec ts;
@@ -341,7 +353,9 @@ static struct {
     uint32_t top;
     int bm25;           /* 0: the summed TF-IDF scores, bytes as without the option */
     double k1, b;
-} g_query = {NULL, "hits.txt", 10, 0, TFIDF_BM25_DEFAULT_K1, TFIDF_BM25_DEFAULT_B};
+    int ops, all;       /* --query-ops, --query-all */
+    long min_match;     /* --min-match, -1: not given.  None of the three: the calls and bytes as without them */
+} g_query = {NULL, "hits.txt", 10, 0, TFIDF_BM25_DEFAULT_K1, TFIDF_BM25_DEFAULT_B, 0, 0, -1};
 
 /* the query file's lines as one batch (tfidf_queries): q_off at the line starts */
 static int load_queries(uint8_t** bytes, uint64_t* nbytes, uint64_t** off, uint32_t* nq) {
@@ -375,9 +389,77 @@ static int load_queries(uint8_t** bytes, uint64_t* nbytes, uint64_t** off, uint3
     return TFIDF_OK;
 }
 
+static void write_hits(const tfidf_hits* h, int* rc) {
+    FILE* f = fopen(g_query.hits, "w");
+    if (!f) printf("Error Opening File: %s\n", g_query.hits);
+    for (uint32_t q = 0; f && q < h->nqueries; ++q)
+        for (uint32_t i = 0; i < h->nhits[q]; ++i)
+            fprintf(f, "q%u\tdoc%u\t%.16f\n", q + 1, h->doc[(size_t)q * h->k + i], h->score[(size_t)q * h->k + i]);
+    if (f && fclose(f) != 0) *rc = TFIDF_E_OUTPUT;
+}
+
+/* --query with --query-ops, --query-all or --min-match: the lines' tokens sorted into the three
+ * texts (query_ops.h), each text through the analyzer and the n-grams like the lines themselves */
+static int run_clause_queries(tfidf_ctx* ctx, tfidf_group* g) {
+    uint64_t* off = NULL;
+    uint8_t* bytes = NULL;
+    uint64_t nbytes = 0;
+    uint32_t nq = 0;
+    int rc = load_queries(&bytes, &nbytes, &off, &nq);
+    if (rc == TFIDF_E_NOINPUT) { printf("Error Opening File: %s\n", g_query.file); return TFIDF_OK; }
+    if (rc) return rc;
+    uint8_t* tb[3] = {NULL, NULL, NULL};
+    uint64_t tn[3] = {0, 0, 0}, *to[3] = {NULL, NULL, NULL};
+    if (qops_split_batch(bytes, off, nq, g_query.ops, g_query.all, tb, tn, to)) rc = TFIDF_E_NOMEM;
+    free(bytes);
+    free(off);
+    tfidf_queries text[3];
+    memset(text, 0, sizeof(text));
+    for (int c = 0; c < 3 && !rc; ++c) {
+        rc = analyze_host_batch(tb[c], tn[c], to[c], nq);
+        if (!rc) rc = ngram_host_batch(&tb[c], &tn[c], &to[c], nq);
+        text[c].bytes = tb[c];
+        text[c].nbytes = tn[c];
+        text[c].q_off = to[c];
+        text[c].nqueries = nq;
+    }
+    uint32_t* mm = NULL;
+    if (!rc && g_query.min_match > 0) {
+        mm = (uint32_t*)malloc(((size_t)nq + 1) * sizeof(uint32_t));
+        if (!mm) rc = TFIDF_E_NOMEM;
+        for (uint32_t q = 0; mm && q < nq; ++q) mm[q] = (uint32_t)g_query.min_match;
+    }
+    tfidf_hits h;
+    memset(&h, 0, sizeof(h));
+    if (!rc) {
+        tfidf_bm25_params bp;
+        memset(&bp, 0, sizeof(bp));
+        bp.size = sizeof(bp);
+        bp.k1 = g_query.k1;
+        bp.b = g_query.b;
+        tfidf_clauses cl;
+        memset(&cl, 0, sizeof(cl));
+        cl.size = sizeof(cl);
+        cl.nqueries = nq;
+        cl.ranking = g_query.bm25 ? TFIDF_RANK_BM25 : TFIDF_RANK_TFIDF;
+        cl.must = &text[QOPS_MUST];
+        cl.should = &text[QOPS_SHOULD];
+        cl.must_not = &text[QOPS_MUST_NOT];
+        cl.min_should = mm;
+        cl.bm25 = g_query.bm25 ? &bp : NULL;
+        rc = g ? tfidf_group_query_clauses(g, &cl, g_query.top, &h) : tfidf_query_clauses(ctx, &cl, g_query.top, &h);
+    }
+    if (!rc) write_hits(&h, &rc);
+    tfidf_hits_free(&h);
+    free(mm);
+    for (int c = 0; c < 3; ++c) { free(tb[c]); free(to[c]); }
+    return rc;
+}
+
 /* --query: ranks the resident result of ctx (one shard) or of every rank of g */
 static int run_queries(tfidf_ctx* ctx, tfidf_group* g) {
     if (!g_query.file) return TFIDF_OK;
+    if (g_query.ops || g_query.all || g_query.min_match >= 0) return run_clause_queries(ctx, g);
     tfidf_queries qs;
     uint64_t* off = NULL;
     uint8_t* bytes = NULL;
@@ -401,14 +483,7 @@ static int run_queries(tfidf_ctx* ctx, tfidf_group* g) {
     } else {
         rc = g ? tfidf_group_query(g, &qs, g_query.top, &h) : tfidf_query(ctx, &qs, g_query.top, &h);
     }
-    if (!rc) {
-        FILE* f = fopen(g_query.hits, "w");
-        if (!f) printf("Error Opening File: %s\n", g_query.hits);
-        for (uint32_t q = 0; f && q < h.nqueries; ++q)
-            for (uint32_t i = 0; i < h.nhits[q]; ++i)
-                fprintf(f, "q%u\tdoc%u\t%.16f\n", q + 1, h.doc[(size_t)q * h.k + i], h.score[(size_t)q * h.k + i]);
-        if (f && fclose(f) != 0) rc = TFIDF_E_OUTPUT;
-    }
+    if (!rc) write_hits(&h, &rc);
     tfidf_hits_free(&h);
     free(bytes);
     free(off);
@@ -1053,7 +1128,7 @@ static int run_sharded(int ngpus, int nshards, const char* indir, const char* ou
 
 static int usage(void) {
     fprintf(stderr, "usage: tfidf [--debug-jobs] [--stats] [--gpus N] [--shards K] [--device D] "
-                    "[--input DIR] [--output FILE] [--query FILE [--top K] [--hits FILE] [--bm25 [--bm25-k1 X] [--bm25-b Y]]] "
+                    "[--input DIR] [--output FILE] [--query FILE [--top K] [--hits FILE] [--bm25 [--bm25-k1 X] [--bm25-b Y]] [--query-ops] [--query-all] [--min-match M]] "
                     "[--keywords K [--keywords-file FILE]] "
                     "[--similar K [--similar-docs FILE] [--similar-file FILE]] "
                     "[--clusters K [--clusters-iter I] [--clusters-seeds FILE] [--clusters-terms T] [--clusters-file FILE]] "
@@ -1112,6 +1187,18 @@ int main(int argc, char** argv) {
             g_query.top = (uint32_t)k;
         }
         else if (!strcmp(argv[i], "--bm25")) g_query.bm25 = 1;
+        else if (!strcmp(argv[i], "--query-ops")) g_query.ops = 1;
+        else if (!strcmp(argv[i], "--query-all")) g_query.all = 1;
+        else if (!strcmp(argv[i], "--min-match") && i + 1 < argc) {
+            char* end = NULL;
+            const char* a = argv[++i];
+            const long m = strtol(a, &end, 10);
+            if (a[0] < '0' || a[0] > '9' || *end || m > (long)TFIDF_CLAUSE_MAX_TERMS) {
+                fprintf(stderr, "tfidf: --min-match takes 0..%u\n", TFIDF_CLAUSE_MAX_TERMS);
+                return 2;
+            }
+            g_query.min_match = m;
+        }
         else if ((!strcmp(argv[i], "--bm25-k1") || !strcmp(argv[i], "--bm25-b")) && i + 1 < argc) {
             const int is_b = !strcmp(argv[i], "--bm25-b");
             char* end = NULL;
@@ -1300,6 +1387,10 @@ int main(int argc, char** argv) {
     }
     if (g_query.bm25 && !g_query.file) {   /* nothing to rank: say so instead of ignoring the switch */
         fprintf(stderr, "tfidf: --bm25, --bm25-k1 and --bm25-b need --query FILE\n");
+        return 2;
+    }
+    if ((g_query.ops || g_query.all || g_query.min_match >= 0) && !g_query.file) {
+        fprintf(stderr, "tfidf: --query-ops, --query-all and --min-match need --query FILE\n");
         return 2;
     }
     /* TFIDF.c:100-103 before anything touches the GPU */

@@ -44,6 +44,7 @@ EXPORTS = [
     "tfidf_similar", "tfidf_neighbors_free", "tfidf_group_similar", "tfidf_last_similar_info",
     "tfidf_kmeans", "tfidf_clusters_free", "tfidf_last_kmeans_info",
     "tfidf_query_bm25", "tfidf_group_query_bm25", "tfidf_last_bm25_info",
+    "tfidf_clauses_check", "tfidf_query_clauses", "tfidf_group_query_clauses", "tfidf_last_clause_info",
     "tfidf_transform", "tfidf_rows_free", "tfidf_group_transform", "tfidf_last_transform_info",
     "tfidf_model_check", "tfidf_model_export", "tfidf_group_model_export", "tfidf_model_import",
     "tfidf_model_save", "tfidf_model_load", "tfidf_model_free", "tfidf_last_model_info",
@@ -59,6 +60,10 @@ EXPORTS = [
     "tfidf_nb_predict_rows", "tfidf_nb_export", "tfidf_last_nb_info", "tfidf_result_nb_fit", "tfidf_nb_model_predict",
 ]
 QUERY_MAX_K = 1024  # TFIDF_QUERY_MAX_K
+RANK_TFIDF = 0  # TFIDF_RANK_TFIDF
+RANK_BM25 = 1  # TFIDF_RANK_BM25
+CLAUSE_MAX_TERMS = 4095  # TFIDF_CLAUSE_MAX_TERMS
+CLAUSE_MAX_NOT = 255  # TFIDF_CLAUSE_MAX_NOT
 TERMS_MAX_K = 1024  # TFIDF_TERMS_MAX_K
 SIMILAR_MAX_K = 1024  # TFIDF_SIMILAR_MAX_K
 KMEANS_MAX_K = 256  # TFIDF_KMEANS_MAX_K
@@ -167,6 +172,18 @@ class Bm25Params(C.Structure):
 
 class Bm25Info(C.Structure):
     _fields_ = QueryInfo._fields_ + [("avgdl", C.c_double)]
+
+
+class Clauses(C.Structure):
+    _fields_ = [
+        ("size", C.c_uint64), ("nqueries", C.c_uint32), ("ranking", C.c_uint32),
+        ("must", C.POINTER(Queries)), ("should", C.POINTER(Queries)), ("must_not", C.POINTER(Queries)),
+        ("min_should", C.c_void_p), ("bm25", C.POINTER(Bm25Params)),
+    ]
+
+
+class ClauseInfo(C.Structure):
+    _fields_ = Bm25Info._fields_ + [("nq_unsatisfiable", C.c_uint32), ("ngroups_tab_lds", C.c_uint32)]
 
 
 class DocTerms(C.Structure):
@@ -474,6 +491,10 @@ def lib() -> C.CDLL:
         L.tfidf_group_query_bm25.argtypes = [C.c_void_p, C.POINTER(Queries), C.c_uint32, C.POINTER(Bm25Params),
                                              C.POINTER(Hits)]
         L.tfidf_last_bm25_info.argtypes = [C.c_void_p, C.POINTER(Bm25Info)]
+        L.tfidf_clauses_check.argtypes = [C.POINTER(Clauses)]
+        L.tfidf_query_clauses.argtypes = [C.c_void_p, C.POINTER(Clauses), C.c_uint32, C.POINTER(Hits)]
+        L.tfidf_group_query_clauses.argtypes = [C.c_void_p, C.POINTER(Clauses), C.c_uint32, C.POINTER(Hits)]
+        L.tfidf_last_clause_info.argtypes = [C.c_void_p, C.POINTER(ClauseInfo)]
         L.tfidf_top_terms.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(DocTerms)]
         L.tfidf_group_top_terms.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(DocTerms)]
         L.tfidf_doc_terms_free.argtypes = [C.POINTER(DocTerms)]
@@ -570,9 +591,8 @@ def _ptr(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
-def _query(fn, handle, queries, k: int, what: str, params=None) -> dict:
-    """One batch through tfidf_query / tfidf_group_query (or, with params, their BM25 forms):
-    queries are bytes objects."""
+def _queries(queries):
+    """a tfidf_queries over bytes objects, and the arrays it points into"""
     data = np.frombuffer(b"".join(queries), dtype=np.uint8)
     off = np.zeros(len(queries) + 1, dtype=np.uint64)
     if len(queries):
@@ -582,6 +602,16 @@ def _query(fn, handle, queries, k: int, what: str, params=None) -> dict:
     qs.nbytes = len(data)
     qs.q_off = off.ctypes.data
     qs.nqueries = len(queries)
+    return qs, (data, off)
+
+
+def _query(fn, handle, queries, k: int, what: str, params=None) -> dict:
+    """One batch through tfidf_query / tfidf_group_query (or, with params, their BM25 forms):
+    queries are bytes objects.  A Clauses struct as `queries` goes through as it is."""
+    if isinstance(queries, Clauses):
+        qs = queries
+    else:
+        qs, _keep = _queries(queries)
     h = Hits()
     if params is None:
         _chk(fn(handle, C.byref(qs), k, C.byref(h)), what)
@@ -608,6 +638,43 @@ def _bm25_params(k1: float, b: float, avgdl: float) -> Bm25Params:
     p.size = C.sizeof(Bm25Params)
     p.k1, p.b, p.avgdl = k1, b, avgdl
     return p
+
+
+def make_clauses(must=None, should=None, must_not=None, min_should=None, bm25=None, nqueries=None):
+    """A tfidf_clauses and the objects it points into (keep both alive for the call).  must /
+    should / must_not: lists of bytes objects of one length, or None (empty in every query);
+    min_should: one integer per query, or None; bm25: None ranks by the summed TF-IDF scores,
+    True by BM25 with the defaults, a dict(k1=, b=, avgdl=) by BM25 with these; nqueries: the
+    count, when it is not the texts' own."""
+    texts = [t for t in (must, should, must_not) if t is not None]
+    c = Clauses()
+    c.size = C.sizeof(Clauses)
+    c.nqueries = nqueries if nqueries is not None else (len(texts[0]) if texts else
+                                                        (len(min_should) if min_should is not None else 0))
+    keep = []
+    for name, text in (("must", must), ("should", should), ("must_not", must_not)):
+        if text is not None:
+            qs, arrays = _queries(text)
+            keep += [qs, arrays]
+            setattr(c, name, C.pointer(qs))
+    if min_should is not None:
+        ms = np.ascontiguousarray(min_should, dtype=np.uint32)
+        if len(ms) == 0:
+            ms = np.zeros(1, dtype=np.uint32)
+        keep.append(ms)
+        c.min_should = ms.ctypes.data
+    c.ranking = RANK_TFIDF if bm25 is None else RANK_BM25
+    if isinstance(bm25, dict):
+        p = _bm25_params(bm25.get("k1", 1.2), bm25.get("b", 0.75), bm25.get("avgdl", 0.0))
+        keep.append(p)
+        c.bm25 = C.pointer(p)
+    return c, keep
+
+
+def clauses_check(must=None, should=None, must_not=None, min_should=None, bm25=None) -> int:
+    """tfidf_clauses_check's return code for these clauses (host only)"""
+    c, _keep = make_clauses(must, should, must_not, min_should, bm25)
+    return lib().tfidf_clauses_check(C.byref(c))
 
 
 def _top_terms(fn, handle, k: int, docs, what: str, words: bool = True) -> dict:
@@ -1300,6 +1367,21 @@ class Engine:
         res["avgdl"] = self.bm25_info()["avgdl"]
         return res
 
+    def query_clauses(self, must=None, should=None, must_not=None, k: int = 10, min_should=None, bm25=None) -> dict:
+        """Engine.query with must / should / must-not clauses (tfidf_query_clauses): three lists
+        of bytes objects of one length (None: empty in every query), min_should one integer per
+        query; bm25: None, True or dict(k1=, b=, avgdl=) (make_clauses).  Returns what
+        Engine.query returns."""
+        c, _keep = make_clauses(must, should, must_not, min_should, bm25)
+        return _query(lib().tfidf_query_clauses, self.h, c, k, "tfidf_query_clauses")
+
+    def clause_info(self) -> dict:
+        """Counters and device times of the last query_clauses (tfidf_last_clause_info)."""
+        q = ClauseInfo()
+        q.size = C.sizeof(ClauseInfo)
+        _chk(lib().tfidf_last_clause_info(self.h, C.byref(q)), "tfidf_last_clause_info")
+        return {k: getattr(q, k) for k, _ in ClauseInfo._fields_ if k != "size"}
+
     def bm25_info(self) -> dict:
         """Counters and device times of the last query_bm25 (tfidf_last_bm25_info)."""
         q = Bm25Info()
@@ -1719,6 +1801,11 @@ class Group:
                      _bm25_params(k1, b, avgdl))
         res["avgdl"] = self.ranks[0].bm25_info()["avgdl"]   # every rank scored with the same value
         return res
+
+    def query_clauses(self, must=None, should=None, must_not=None, k: int = 10, min_should=None, bm25=None) -> dict:
+        """Clauses over all shards (tfidf_group_query_clauses); see Engine.query_clauses."""
+        c, _keep = make_clauses(must, should, must_not, min_should, bm25)
+        return _query(lib().tfidf_group_query_clauses, self.h, c, k, "tfidf_group_query_clauses")
 
     def top_terms(self, k: int = 10, docs=None, words: bool = True) -> dict:
         """The k best-scoring words of each document over all shards (tfidf_group_top_terms);

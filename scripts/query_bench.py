@@ -10,6 +10,15 @@ one by one (64 passes) next to the batch's single pass; and tfidf_fetch of the s
 the only other way to get at the scores.
 
     python3 scripts/query_bench.py [--scale S] [--commit ID] [--out profiles/query_c2.json]
+
+With --clauses it measures tfidf_query_clauses instead, on the same run and the same queries:
+tfidf_query and tfidf_query_bm25 as they are, the clause call with each query's text as its
+should text (the same hits, by definition), and the clause call with the first half of each
+query's tokens as must, the rest as should and one more Zipf-drawn word as must_not; the last two
+under both rankings.  Per call: median and min-max over --reps of the scoring time, the top-k time
+and the host wall time.
+
+    python3 scripts/query_bench.py --clauses [--scale S] [--commit ID] [--out profiles/query_clauses_c2.json]
 """
 import argparse
 import json
@@ -33,6 +42,7 @@ ap.add_argument("--k", type=int, default=10)
 ap.add_argument("--reps", type=int, default=10)
 ap.add_argument("--commit", default="")
 ap.add_argument("--out", default="")
+ap.add_argument("--clauses", action="store_true")
 args = ap.parse_args()
 
 p = tfidf_configs.plan(args.config, scale=args.scale)
@@ -54,6 +64,57 @@ with tfidf_abi.Engine(0) as e:
         for _ in range(args.queries):
             ws = by_df[np.searchsorted(cdf, rng.random(args.words))]
             queries.append(b" ".join(bytes(tb[int(toff[t]):int(toff[t + 1])]) for t in ws.tolist()))
+        extra = by_df[np.searchsorted(cdf, rng.random(args.queries))]      # --clauses: one must_not word per query
+        excluded = [bytes(tb[int(toff[t]):int(toff[t + 1])]) for t in extra.tolist()]
+
+    def clause_modes():
+        """name -> (call, its info): the plain calls, then the clause call in the shapes above"""
+        half = [q.split() for q in queries]
+        must = [b" ".join(w[:len(w) // 2]) for w in half]
+        rest = [b" ".join(w[len(w) // 2:]) for w in half]
+        modes = {
+            "query": (lambda: e.query(queries, args.k), e.query_info),
+            "query_bm25": (lambda: e.query_bm25(queries, args.k), e.bm25_info),
+        }
+        for name, bm in (("", None), ("_bm25", True)):
+            modes["clauses_should_only" + name] = (
+                lambda bm=bm: e.query_clauses(should=queries, k=args.k, bm25=bm), e.clause_info)
+            modes["clauses_half_must_one_not" + name] = (
+                lambda bm=bm: e.query_clauses(must, rest, excluded, args.k, None, bm), e.clause_info)
+        return modes
+
+    def measure(call, info, reps):
+        rows = []
+        for _ in range(reps):
+            t1 = time.perf_counter()
+            res = call()
+            wall = (time.perf_counter() - t1) * 1e3
+            row = info()
+            row["wall_ms"] = wall
+            rows.append(row)
+        return res, rows
+
+    if args.clauses:
+        out = {"commit": args.commit, "config": args.config, "scale": args.scale, "docs": N, "pairs": P, "terms": V,
+               "queries": args.queries, "words_per_query": args.words, "k": args.k, "reps": args.reps, "modes": {}}
+        for name, (call, info) in clause_modes().items():
+            measure(call, info, 2)                 # warm-up: code objects, the context's buffers
+            res, rows = measure(call, info, args.reps)
+            m = {"groups": rows[-1]["ngroups"], "mean_nmatch": float(np.mean(res["nmatch"])),
+                 "mean_nhits": float(np.mean(res["nhits"])),
+                 "nq_unsatisfiable": rows[-1].get("nq_unsatisfiable"), "groups_tab_lds": rows[-1].get("ngroups_tab_lds")}
+            for k in ("ms_score", "ms_topk", "wall_ms"):
+                v = [x[k] for x in rows]
+                m[k] = {"median": round(statistics.median(v), 4), "min": round(min(v), 4), "max": round(max(v), 4)}
+            out["modes"][name] = m
+        out["note"] = ("device times are HIP events inside the calls; wall_ms includes host tokenising, uploads and "
+                       "the D2H of the rows")
+        line = json.dumps(out)
+        print(line, flush=True)
+        if args.out:
+            with open(args.out, "w") as f:
+                f.write(line + "\n")
+        sys.exit(0)
     probe = e.hbm_probe(1 << 30, 5)
 
     def timed(qs, reps):
