@@ -2543,8 +2543,11 @@ __device__ __forceinline__ uint4 xb_key_at(const uint32_t* __restrict__ rrec, ui
  * are also staged in LDS, so the find-or-claim probes compare keys without waiting on
  * memory: LDS slot -> the bucket-local index of the key's first copy + the summed df, and
  * each record is answered from the slot it found (reply[i + sender]).  A bucket of more
- * than XB_MAXREC records (not expected: the mean is <= XB_MEAN) takes the same steps with
- * the keys compared in memory. */
+ * than XB_MAXREC records takes the same steps with the keys compared in memory.  The mean is
+ * <= XB_MEAN, but a bucket holds every copy of its keys, so a term that all R ranks hold puts R
+ * records into one: the large path is expected whenever R exceeds XB_MAXREC / (distinct keys
+ * per bucket), and at R = 1024 it is the rule for every common term.  Its table stays at XB_T
+ * slots: what bounds a bucket is its distinct keys (<= XB_T), not its records. */
 constexpr uint32_t XB_NT = 256;
 constexpr uint32_t XB_MAXREC = 1024;
 constexpr uint32_t XB_PER = XB_MAXREC / XB_NT;
@@ -2680,8 +2683,9 @@ size_t owner_bucket_scratch(uint64_t n) {
 int launch_owner_aggregate_buckets(const uint32_t* rrec, uint64_t n, const uint32_t* roff, uint32_t R, void* scratch,
                                    size_t scratch_bytes, uint32_t* reply, unsigned long long* used, uint32_t* status,
                                    uint32_t stage_max, hipStream_t s) {
-    /* stage_max: buckets of up to this many records (<= XB_MAXREC) are staged in LDS; the
-     * tests set 0 so that every bucket takes the path that compares keys in memory */
+    /* stage_max: buckets of up to this many records (<= XB_MAXREC) are staged in LDS, larger
+     * ones (the bucket of a term that more than stage_max ranks hold) compare keys in memory;
+     * the tests also set 0 so that every bucket takes that path */
     if (stage_max > XB_MAXREC) stage_max = XB_MAXREC;
     const uint32_t nb = owner_buckets(n);
     uint32_t lg = 0;
