@@ -1697,6 +1697,123 @@ int tfidf_result_nb_fit(const tfidf_result* r, const tfidf_nb_params* params, tf
 int tfidf_nb_model_predict(const tfidf_nb_model* m, uint32_t nrows, const uint64_t* row_off, const uint32_t* term,
                            const uint32_t* count, uint32_t flags, tfidf_nb_labels* out);
 
+/* ------------------------------------------------------------ term matching -- */
+
+/* Fuzzy and prefix matching of patterns against the resident term dictionary: the term
+ * expansion a retrieval engine answers `recieve` and `connect*` with.  A pattern is matched
+ * against every term of the context's table; its best few matches, by edit distance and then by
+ * document frequency, are returned with their words and can stand in for it in an ordinary
+ * query.  The reference has no such pass.  Everything is integer arithmetic on BYTES: there are
+ * no code points here, a two-byte UTF-8 letter is two bytes of distance.
+ *
+ *   pattern      p = bytes[p_off[p], p_off[p + 1]) (host pointers), 1..TFIDF_MATCH_MAX_PATTERN
+ *                bytes of any value; kind[p] is TFIDF_MATCH_FUZZY or TFIDF_MATCH_PREFIX;
+ *                max_edits[p] <= TFIDF_MATCH_MAX_EDITS is the budget of a fuzzy pattern and is
+ *                ignored for a prefix pattern
+ *   prefix       term t matches when len(t) >= len(p) and t's first len(p) bytes equal p;
+ *                dist = 0
+ *   fuzzy        term t matches when the first min(fixed_prefix, len(p)) bytes of p equal t's
+ *                (so t has at least that many) and dist(p, t) <= max_edits[p]
+ *   dist         the Levenshtein distance (insert, delete, substitute one byte); with
+ *                TFIDF_MATCH_TRANSPOSE in flags the optimal-string-alignment distance: an
+ *                adjacent transposition is one edit too, and no substring is edited twice.
+ *                "ab" -> "ba" is 1 with the flag and 2 without; "ca" -> "abc" is 3 with it
+ *                (not the 2 of the unrestricted Damerau distance)
+ *   empty term   a term like any other: it matches a fuzzy pattern of length <= max_edits[p]
+ *   order        dist ascending, then df descending (the global df), then term-table order
+ *                ascending (= rank ascending = strcmp of "word\t").  Ranks are unique: the order
+ *                is total and the result unique
+ *   cut          the first max_expansions matches are returned
+ * Nothing depends on grid, pattern grouping, batch cut or list capacity. */
+#define TFIDF_MATCH_MAX_PATTERN    64u      /* bytes */
+#define TFIDF_MATCH_MAX_EDITS      2u
+#define TFIDF_MATCH_MAX_EXPANSIONS 1024u
+#define TFIDF_MATCH_MAX_PATTERNS   65536u
+#define TFIDF_MATCH_FUZZY  0u
+#define TFIDF_MATCH_PREFIX 1u
+#define TFIDF_MATCH_TRANSPOSE 1u            /* flags: an adjacent transposition is one edit */
+typedef struct tfidf_patterns {
+    const uint8_t*  bytes;
+    uint64_t        nbytes;
+    const uint64_t* p_off;       /* npatterns + 1 entries, non-decreasing, p_off[npatterns] <= nbytes */
+    uint32_t        npatterns;
+    const uint8_t*  kind;        /* npatterns: TFIDF_MATCH_FUZZY / TFIDF_MATCH_PREFIX */
+    const uint8_t*  max_edits;   /* npatterns: 0..TFIDF_MATCH_MAX_EDITS (fuzzy patterns) */
+} tfidf_patterns;
+typedef struct tfidf_match_params {
+    uint64_t size;               /* sizeof(tfidf_match_params), set by the caller */
+    uint32_t max_expansions;     /* E: 1..TFIDF_MATCH_MAX_EXPANSIONS */
+    uint32_t flags;              /* TFIDF_MATCH_TRANSPOSE or 0 */
+    uint32_t fixed_prefix;       /* 0..TFIDF_MATCH_MAX_PATTERN: leading bytes a fuzzy match must share */
+    uint32_t reserved;
+    uint64_t list_records;       /* capacity of the device match list in records; 0: the default
+                                    (262144), else >= 1024.  A field, not an environment knob */
+} tfidf_match_params;
+/* Rows laid out like tfidf_doc_terms.  Arrays are owned by the library and released by
+ * tfidf_term_matches_free(). */
+typedef struct tfidf_term_matches {
+    uint32_t  npatterns, k;  /* rows, row stride (= max_expansions) */
+    uint64_t* nmatch;        /* per pattern: matching terms (all, before the cut) */
+    uint32_t* nterms;        /* per pattern: min(k, nmatch) */
+    uint32_t* term;          /* npatterns * k, row p at p * k: term rank (UINT32_MAX from a group) */
+    uint8_t*  dist;          /* same layout */
+    uint32_t* df;            /* same layout: global df */
+    uint64_t* word_off;      /* npatterns * k + 1: entry p * k + j is bytes [word_off[..], word_off[.. + 1]); unused entries empty */
+    uint8_t*  word_bytes;    /* the matched words' bytes, gathered on the device */
+} tfidf_term_matches;
+/* Host only, no GPU.  TFIDF_E_INVAL for: a NULL argument; params->size < sizeof(tfidf_match_params);
+ * max_expansions == 0 or > TFIDF_MATCH_MAX_EXPANSIONS; unknown flag bits; fixed_prefix >
+ * TFIDF_MATCH_MAX_PATTERN; list_records in 1..1023; npatterns > TFIDF_MATCH_MAX_PATTERNS;
+ * with npatterns > 0 a NULL p_off, kind or max_edits, a non-monotone p_off or
+ * p_off[npatterns] > nbytes; a pattern of 0 or more than TFIDF_MATCH_MAX_PATTERN bytes; an
+ * unknown kind; a fuzzy pattern's max_edits > TFIDF_MATCH_MAX_EDITS. */
+int tfidf_match_check(const tfidf_patterns* patterns, const tfidf_match_params* params);
+/* Matches every pattern against the context's term table in HBM: the table of the last run (after
+ * a tfidf_prune: the kept terms and their df) or of an imported model (the call needs the
+ * dictionary alone, so it works on a model-only context).  TFIDF_E_INVAL for NULL arguments or
+ * what tfidf_match_check refuses; TFIDF_E_STATE when the context holds neither a result nor a
+ * model; on an error *out is zeroed.  npatterns == 0 is valid.  The result is not disturbed;
+ * the run's corpus must still be valid, as for tfidf_format (long terms' bytes are read from
+ * it).  With a communicator attached the call is local: this shard's table with the global df.
+ * The patterns are scanned in groups of 64, one pass over the table per group; matches go to a
+ * device list of list_records records (40 bytes each).  A group whose matches exceed it is
+ * scanned again in batches of patterns whose exact counts fit, and for one pattern with more
+ * matches than the capacity the list grows once to that count, which is at most V.  The
+ * buffers belong to the context: a repeated identical call allocates nothing
+ * (tfidf_alloc_stats). */
+int tfidf_match_terms(tfidf_ctx* ctx, const tfidf_patterns* patterns, const tfidf_match_params* params,
+                      tfidf_term_matches* out);
+void tfidf_term_matches_free(tfidf_term_matches* m);
+/* The same over every shard of a group (tfidf_group_run): every rank matches its own table on its
+ * own host thread, the host merges the ranks' rows by (dist, df descending, "word\t" ascending)
+ * and keeps a word several ranks hold once.  A term has the same dist and the same global df in
+ * every shard that holds it, so the merged first E of the ranks' first E are the first E of the
+ * corpus-wide dictionary.  term is UINT32_MAX (there is no common table); nmatch[p] is the
+ * largest of the ranks' counts, a lower bound of the corpus-wide count that is exact with one
+ * shard (with several, the merged row may hold more words than one rank counted: nterms[p] is the
+ * row's length, at most E). */
+int tfidf_group_match_terms(tfidf_group* g, const tfidf_patterns* patterns, const tfidf_match_params* params,
+                            tfidf_term_matches* out);
+/* Host only, plain C (match_host.c): the same definition over a model struct, the second opinion
+ * on the device; term is the index into the model's table.  TFIDF_E_INVAL for NULL arguments,
+ * what tfidf_match_check refuses or a model that fails tfidf_model_check; *out is zeroed then. */
+int tfidf_model_match_terms(const tfidf_model* m, const tfidf_patterns* patterns, const tfidf_match_params* params,
+                            tfidf_term_matches* out);
+/* Counters of the last tfidf_match_terms (the caller sets `size` = sizeof, as tfidf_query_info). */
+typedef struct tfidf_match_info {
+    uint64_t size;
+    uint32_t npatterns, k;
+    uint32_t ngroups;         /* scans of the table (a group that overflowed is scanned again per batch) */
+    uint32_t nbatches;        /* selections: a sort of the list, the cut and the word gather */
+    uint64_t nrecords;        /* matches written to the list by the scans that were selected from */
+    uint64_t list_records;    /* the capacity the call ended with */
+    double   ms_scan;         /* device times (HIP events), summed */
+    double   ms_select;
+    double   ms_words;
+    double   ms_total;        /* host wall time of the whole call */
+} tfidf_match_info;
+int tfidf_last_match_info(const tfidf_ctx* ctx, tfidf_match_info* info);
+
 /* ---------------------------------------------------------------- ingest ---- */
 
 /* Reference input contract (TFIDF.c:98-110,130-147): N = number of entries of `dir`

@@ -19,6 +19,7 @@
  *   engine_dedup.cpp      tfidf_minhash, tfidf_near_dups (dedup.hip; the groups: dedup_host.c)
  *   engine_nb.cpp         tfidf_nb_fit, tfidf_nb_predict, tfidf_nb_predict_rows, tfidf_nb_export
  *                         (nb.hip; the check and the host twin: nb_host.c)
+ *   engine_match.cpp      tfidf_match_terms (match.hip; the check and the host twin: match_host.c)
  * The add-on calls run between runs on the context's stream and use the run's arena as scratch
  * only; none of them is on the path tfidf_run times.  The add-on launches and the run's own
  * persistent kernels alike take their CU count from ctx_ncu below.
@@ -354,6 +355,14 @@ struct tfidf_ctx {
     const uint64_t* nb_T_dev = nullptr;
     std::vector<uint64_t> nb_class_docs;        /* n_c, kept for tfidf_nb_export */
     tfidf_nb_info nbinfo{};
+    /* term matching (tfidf_match_terms, match.hip): the call's pattern block (MT_PAT bytes per
+     * pattern, then lengths, kinds, budgets); the per-pattern match counts with the list's cursor
+     * behind them; the match list and its sort's second half (keys, values); a batch's segment
+     * offsets, its k entries per pattern (term, dist, df, word length -> offset) and the gathered
+     * words.  Nothing is kept per result. */
+    DevBuf mt_pat, mt_cnt, mt_k0, mt_k1, mt_v0, mt_v1, mt_seg, mt_term, mt_dist, mt_df, mt_woff, mt_words;
+    Event ev_mt[6];                             /* scan / select / words bounds (created by the first call) */
+    tfidf_match_info mtinfo{};
 #define WR_NBUF 8
 #define WR_BUF (16ull << 20)
 #define WR_GROUPS 8

@@ -1160,6 +1160,103 @@ int tfidf_group_model_export(tfidf_group* g, tfidf_model* out) {
     return TFIDF_OK;
 }
 
+/* Every rank matches the patterns against its own term table (tfidf_match_terms is local to a
+ * context), one host thread per rank.  A row is ordered by (dist, df descending, "word\t"), and a
+ * word has the same dist and the same global df in every shard that holds it, so the ranks' rows
+ * merge by that key and a word several ranks return is kept once: the first E of the merge are
+ * the first E of the corpus-wide dictionary.  nmatch is the largest rank's count. */
+int tfidf_group_match_terms(tfidf_group* g, const tfidf_patterns* patterns, const tfidf_match_params* params,
+                            tfidf_term_matches* out) {
+    if (!out) return TFIDF_E_INVAL;
+    memset(out, 0, sizeof(*out));
+    if (!g || tfidf_match_check(patterns, params) != TFIDF_OK) return TFIDF_E_INVAL;
+    const int R = g->n;
+    std::vector<int> rc((size_t)R, TFIDF_OK);
+    std::vector<tfidf_term_matches> part((size_t)R);
+    for (tfidf_term_matches& p : part) memset(&p, 0, sizeof(p));
+    {
+        std::vector<std::thread> th;
+        for (int r = 1; r < R; ++r)
+            th.emplace_back([&, r] { rc[r] = tfidf_match_terms(g->ctx[r], patterns, params, &part[r]); });
+        rc[0] = tfidf_match_terms(g->ctx[0], patterns, params, &part[0]);
+        for (auto& t : th) t.join();
+    }
+    int err = TFIDF_OK;
+    for (int r = 0; r < R && !err; ++r) err = rc[r];
+    const uint32_t P = patterns->npatterns, E = params->max_expansions;
+    const size_t PE = (size_t)P * E;
+    tfidf_term_matches m;
+    memset(&m, 0, sizeof(m));
+    uint64_t bsum = 0;
+    for (int r = 0; r < R && !err; ++r) bsum += part[r].word_off[PE];
+    if (!err) {
+        m.npatterns = P;
+        m.k = E;
+        m.nmatch = (uint64_t*)calloc((size_t)P + 1, 8);
+        m.nterms = (uint32_t*)calloc((size_t)P + 1, 4);
+        m.term = (uint32_t*)calloc(PE + 1, 4);
+        m.dist = (uint8_t*)calloc(PE + 1, 1);
+        m.df = (uint32_t*)calloc(PE + 1, 4);
+        m.word_off = (uint64_t*)calloc(PE + 1, 8);
+        m.word_bytes = (uint8_t*)malloc((size_t)bsum + 1);
+        if (!m.nmatch || !m.nterms || !m.term || !m.dist || !m.df || !m.word_off || !m.word_bytes) err = TFIDF_E_NOMEM;
+    }
+    uint64_t B = 0;
+    std::vector<uint32_t> at((size_t)R);
+    for (uint32_t p = 0; p < P && !err; ++p) {
+        for (int r = 0; r < R; ++r) {
+            at[r] = 0;
+            if (part[r].nmatch[p] > m.nmatch[p]) m.nmatch[p] = part[r].nmatch[p];
+        }
+        uint32_t n = 0;
+        for (; n < E; ++n) {
+            int best = -1;
+            size_t be = 0;
+            for (int r = 0; r < R; ++r) {
+                if (at[r] >= part[r].nterms[p]) continue;
+                const tfidf_term_matches& q = part[r];
+                const size_t e = (size_t)p * E + at[r];
+                bool first = best < 0;
+                if (!first) {
+                    const tfidf_term_matches& b = part[best];
+                    if (q.dist[e] != b.dist[be]) first = q.dist[e] < b.dist[be];
+                    else if (q.df[e] != b.df[be]) first = q.df[e] > b.df[be];
+                    else first = word_tab_cmp(q.word_bytes + q.word_off[e], (uint32_t)(q.word_off[e + 1] - q.word_off[e]),
+                                              b.word_bytes + b.word_off[be], (uint32_t)(b.word_off[be + 1] - b.word_off[be])) < 0;
+                }
+                if (first) { best = r; be = e; }
+            }
+            if (best < 0) break;
+            const tfidf_term_matches& b = part[best];
+            const uint64_t wl = b.word_off[be + 1] - b.word_off[be];
+            const size_t o = (size_t)p * E + n;
+            m.term[o] = 0xFFFFFFFFu;
+            m.dist[o] = b.dist[be];
+            m.df[o] = b.df[be];
+            m.word_off[o] = B;
+            memcpy(m.word_bytes + B, b.word_bytes + b.word_off[be], (size_t)wl);
+            for (int r = 0; r < R; ++r) {   /* the same word on the other ranks (and this one) */
+                if (at[r] >= part[r].nterms[p]) continue;
+                const tfidf_term_matches& q = part[r];
+                const size_t e = (size_t)p * E + at[r];
+                const uint64_t ql = q.word_off[e + 1] - q.word_off[e];
+                if (ql == wl && (!wl || memcmp(q.word_bytes + q.word_off[e], m.word_bytes + B, (size_t)wl) == 0)) ++at[r];
+            }
+            B += wl;
+        }
+        m.nterms[p] = n;
+        for (uint32_t j = n; j < E; ++j) m.word_off[(size_t)p * E + j] = B;
+    }
+    if (!err) m.word_off[PE] = B;
+    for (tfidf_term_matches& p : part) tfidf_term_matches_free(&p);
+    if (err) {
+        tfidf_term_matches_free(&m);
+        return err;
+    }
+    *out = m;
+    return TFIDF_OK;
+}
+
 void tfidf_group_close(tfidf_group* g) {
     if (!g) return;
     for (tfidf_ctx* c : g->ctx)

@@ -385,6 +385,7 @@ int launch_format_f64(const double* v, uint64_t n, uint8_t* out, uint32_t* statu
 #define PR_WG_PER_CU       4u  /* k_pr_pairs (count and write) */
 #define NB_WG_PER_CU       8u  /* k_nb_count, k_nb_sums, k_nb_predict: a wave per document or row, as k_km_assign */
 #define NB_EL_WG_PER_CU    8u  /* k_nb_argmax, k_nb_list, k_nb_weights: a thread per matrix entry */
+#define MT_WG_PER_CU       7u  /* k_mt_scan: ~21.5 KiB of LDS each (the lanes' term bytes and the group's patterns) */
 #define BIG_WG_MAX         256u /* k_doc_score_big, k_sim_score_big, k_rw_docs_big: at most this many ... */
 #define BIG_WG_PER_CU      4u  /* ... and this many per CU */
 
@@ -1110,5 +1111,65 @@ struct NbPredictArgs {
     double* all;                 /* [nrows][K] or null */
 };
 int launch_nb_predict(const NbPredictArgs& a, uint32_t ncu, hipStream_t s);
+
+/* ---- fuzzy and prefix term matching over the resident term table (match.hip, tfidf_match_terms) ---- */
+#define MT_NT       256u         /* threads per scan workgroup = terms per tile: one lane per term */
+#define MT_GROUP    64u          /* patterns per scan: their bytes, lengths, kinds and budgets staged in LDS */
+#define MT_PAT      64u          /* a pattern's slot in the pattern block (TFIDF_MATCH_MAX_PATTERN) */
+#define MT_TERM_MAX 66u          /* bytes of a term a lane holds: no longer term matches a fuzzy pattern, and a
+                                    prefix pattern reads at most MT_PAT of them */
+#define MT_NO_MATCH 3u           /* a distance over every budget */
+/* Where the scan reads term t's bytes.  From a run: t_key / t_len of launch_term_meta (a term under
+ * 16 bytes is its key, a longer one lies in the corpus at the key's offset).  From an imported
+ * model: m_off / m_blob, with tkey null. */
+struct MtSrc {
+    const uint4* tkey;           /* null: the model form */
+    const uint32_t* tlen;
+    const uint8_t* corpus;
+    uint64_t corpus_bytes;       /* bound of corpus / blob */
+    const uint64_t* moff;        /* nterms + 1 */
+    const uint8_t* blob;
+};
+/* One scan of the table for the patterns [p0, p0 + np), np <= MT_GROUP, of the call's pattern
+ * block: pat = MT_PAT bytes per pattern, plen / pkind / pbudget one byte each.  Every match adds 1
+ * to nmatch[p] (u64 atomics: exact in any order) and takes the next record of the list from
+ * *nrec; records beyond list_cap are counted and not written.  A record's key orders the list:
+ * w = p - p0, z = dist, y = ~df, x = rank. */
+struct MtScanArgs {
+    MtSrc src;
+    const uint32_t* df;          /* global df by rank */
+    uint32_t V;
+    const uint8_t* pat;
+    const uint8_t* plen;
+    const uint8_t* pkind;
+    const uint8_t* pbudget;
+    uint32_t p0, np;
+    uint32_t fixed_prefix;
+    uint32_t transpose;
+    unsigned long long* nmatch;  /* by pattern of the call */
+    unsigned long long* nrec;
+    uint4* key;
+    uint32_t* val;               /* the rank again: the sorts carry a value */
+    uint64_t list_cap;
+};
+int launch_match_scan(const MtScanArgs& a, uint32_t ncu, hipStream_t s);
+/* The cut over the sorted list: pattern i < np of the batch owns the records [seg[i], seg[i + 1]);
+ * entry i * k + j takes record seg[i] + j for j < min(k, its records): term, dist, df and wlen =
+ * the term's byte length; the rest of the row is term 0, wlen 0.  wlen[np * k] = 0. */
+struct MtCutArgs {
+    const uint4* key;
+    const uint32_t* seg;         /* np + 1 */
+    uint32_t np, k;
+    MtSrc src;
+    uint32_t V;
+    uint32_t* term;
+    uint8_t* dist;
+    uint32_t* df;
+    uint64_t* wlen;
+};
+int launch_match_cut(const MtCutArgs& a, hipStream_t s);
+/* launch_terms_words for the model form: entry i is bytes [woff[i], woff[i + 1]) of `bytes` */
+int launch_match_words_model(const uint32_t* term, const uint64_t* woff, uint64_t n, const MtSrc& src, uint32_t V,
+                             uint8_t* bytes, hipStream_t s);
 
 #endif

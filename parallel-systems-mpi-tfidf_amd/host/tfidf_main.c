@@ -44,6 +44,22 @@
  *                 hits file's format; without --query each is a usage error (exit 2).
  * With several shards the ranks' hits are merged (tfidf_group_query / tfidf_group_query_bm25 /
  * tfidf_group_query_clauses).
+ *   --fuzzy D|auto  term expansion (tfidf_match_terms; host/query_expand.h): every token of a
+ *                 line, as the lookup would see it (behind the analyzer and the n-grams), of at most
+ *                 64 bytes is matched against the dictionary within D = 0..2 byte edits (auto: 0 up
+ *                 to 2 bytes, 1 up to 5, else 2) and the line is rewritten as the words its tokens
+ *                 matched, which then goes to the same call as before; --fuzzy-no-transpose counts
+ *                 an adjacent transposition as two edits, --fuzzy-prefix P (default 0) requires the
+ *                 first P bytes to match, --max-expansions E (default 50, at most 1024) words stand
+ *                 in for a token, the best by distance, then df;
+ *   --prefix-ops  a token of >= 2 bytes that ends in '*' (read before the analyzer) is a prefix:
+ *                 every word that starts with it, the best E by df.  Works with --bm25 and
+ *                 --shards; the hits file keeps its format.  Not with --query-ops, --query-all or
+ *                 --min-match (exit 2).
+ *   --suggest FILE  instead of ranking, the matches of every distinct token of every line of FILE
+ *                 go to suggest.txt (--suggest-file FILE) as q<i>\t<token>\t<word>\t<dist>\t<df>;
+ *                 needs --fuzzy or --prefix-ops (exit 2); also as `tfidf --model FILE --suggest
+ *                 FILE`, without input/ or output.txt.
  *
  * Keywords (the k best-scoring words of every document, tfidf_top_terms):
  *   --keywords K          after output.txt (and after the hits file of --query), one line
@@ -207,6 +223,7 @@
 #include "../../include/tfidf.h"
 #include "labels_file.h"
 #include "query_ops.h"
+#include "query_expand.h"
 
 static double wall_ms(void) {
     struct timespec ts;
@@ -358,8 +375,8 @@ static struct {
 } g_query = {NULL, "hits.txt", 10, 0, TFIDF_BM25_DEFAULT_K1, TFIDF_BM25_DEFAULT_B, 0, 0, -1};
 
 /* the query file's lines as one batch (tfidf_queries): q_off at the line starts */
-static int load_queries(uint8_t** bytes, uint64_t* nbytes, uint64_t** off, uint32_t* nq) {
-    FILE* f = fopen(g_query.file, "rb");
+static int load_queries(const char* path, uint8_t** bytes, uint64_t* nbytes, uint64_t** off, uint32_t* nq) {
+    FILE* f = fopen(path, "rb");
     if (!f) return TFIDF_E_NOINPUT;
     size_t cap = 1 << 16, n = 0;
     uint8_t* b = (uint8_t*)malloc(cap);
@@ -389,6 +406,90 @@ static int load_queries(uint8_t** bytes, uint64_t* nbytes, uint64_t** off, uint3
     return TFIDF_OK;
 }
 
+/* ---- term expansion (--fuzzy, --prefix-ops, --suggest; query_expand.h) ---- */
+static struct {
+    int fuzzy;              /* QEXP_OFF: no --fuzzy; 0..2 or QEXP_AUTO */
+    int prefix_ops;
+    int no_transpose;
+    int opts;               /* --fuzzy-no-transpose, --fuzzy-prefix or --max-expansions given */
+    uint32_t fixed_prefix, max_expansions;
+    const char* suggest;    /* NULL: no suggestions.  None of these: the calls and bytes as without them */
+    const char* suggest_file;
+} g_expand = {QEXP_OFF, 0, 0, 0, 0, 50, NULL, "suggest.txt"};
+
+/* a file's lines as the call sees them: the plain and the prefix text behind the analyzer and the
+ * n-grams, their tokens and patterns, and the patterns' matches in ctx's or the group's dictionary */
+typedef struct {
+    uint8_t* tb[2];
+    uint64_t tn[2], *to[2];
+    uint32_t nq;
+    qexp_plan plan;
+    tfidf_term_matches m;
+} expansion;
+
+static void expansion_free(expansion* x) {
+    for (int c = 0; c < 2; ++c) { free(x->tb[c]); free(x->to[c]); }
+    qexp_plan_free(&x->plan);
+    tfidf_term_matches_free(&x->m);
+    memset(x, 0, sizeof(*x));
+}
+
+static int expansion_load(tfidf_ctx* ctx, tfidf_group* g, const char* path, expansion* x) {
+    memset(x, 0, sizeof(*x));
+    int rc = load_queries(path, &x->tb[0], &x->tn[0], &x->to[0], &x->nq);
+    if (rc) return rc;
+    if (g_expand.prefix_ops) {
+        uint8_t* sb[2];
+        uint64_t sn[2], *so[2];
+        if (qexp_split_batch(x->tb[0], x->to[0], x->nq, sb, sn, so)) rc = TFIDF_E_NOMEM;
+        if (!rc) {
+            free(x->tb[0]);
+            free(x->to[0]);
+            for (int c = 0; c < 2; ++c) { x->tb[c] = sb[c]; x->tn[c] = sn[c]; x->to[c] = so[c]; }
+        }
+    }
+    for (int c = 0; c < 2 && !rc; ++c) {
+        if (!x->tb[c]) continue;
+        rc = analyze_host_batch(x->tb[c], x->tn[c], x->to[c], x->nq);
+        if (!rc) rc = ngram_host_batch(&x->tb[c], &x->tn[c], &x->to[c], x->nq);
+    }
+    if (!rc) {
+        const uint8_t* const text[2] = {x->tb[0], x->tb[1]};
+        const uint64_t* const off[2] = {x->to[0], x->to[1]};
+        const int q = qexp_plan_build(text, off, x->nq, g_expand.fuzzy, &x->plan);
+        if (q == QEXP_E_PATTERNS) fprintf(stderr, "tfidf: %s holds more than %u distinct patterns\n", path, TFIDF_MATCH_MAX_PATTERNS);
+        rc = q == QEXP_E_NOMEM ? TFIDF_E_NOMEM : q ? TFIDF_E_INVAL : TFIDF_OK;
+    }
+    if (!rc) {
+        tfidf_match_params mp;
+        memset(&mp, 0, sizeof(mp));
+        mp.size = sizeof(mp);
+        mp.max_expansions = g_expand.max_expansions;
+        mp.flags = g_expand.no_transpose ? 0u : TFIDF_MATCH_TRANSPOSE;
+        mp.fixed_prefix = g_expand.fixed_prefix;
+        rc = g ? tfidf_group_match_terms(g, &x->plan.patterns, &mp, &x->m) : tfidf_match_terms(ctx, &x->plan.patterns, &mp, &x->m);
+    }
+    if (rc) expansion_free(x);
+    return rc;
+}
+
+/* --suggest: the matches of every token of FILE's lines, from ctx's dictionary or every rank's of g */
+static int run_suggest(tfidf_ctx* ctx, tfidf_group* g) {
+    if (!g_expand.suggest) return TFIDF_OK;
+    expansion x;
+    int rc = expansion_load(ctx, g, g_expand.suggest, &x);
+    if (rc == TFIDF_E_NOINPUT) { printf("Error Opening File: %s\n", g_expand.suggest); return TFIDF_OK; }
+    if (rc) return rc;
+    FILE* f = fopen(g_expand.suggest_file, "w");
+    if (!f) printf("Error Opening File: %s\n", g_expand.suggest_file);
+    if (f) {
+        qexp_suggest(&x.plan, x.nq, &x.m, f);
+        if (fclose(f) != 0) rc = TFIDF_E_OUTPUT;
+    }
+    expansion_free(&x);
+    return rc;
+}
+
 static void write_hits(const tfidf_hits* h, int* rc) {
     FILE* f = fopen(g_query.hits, "w");
     if (!f) printf("Error Opening File: %s\n", g_query.hits);
@@ -405,7 +506,7 @@ static int run_clause_queries(tfidf_ctx* ctx, tfidf_group* g) {
     uint8_t* bytes = NULL;
     uint64_t nbytes = 0;
     uint32_t nq = 0;
-    int rc = load_queries(&bytes, &nbytes, &off, &nq);
+    int rc = load_queries(g_query.file, &bytes, &nbytes, &off, &nq);
     if (rc == TFIDF_E_NOINPUT) { printf("Error Opening File: %s\n", g_query.file); return TFIDF_OK; }
     if (rc) return rc;
     uint8_t* tb[3] = {NULL, NULL, NULL};
@@ -464,10 +565,23 @@ static int run_queries(tfidf_ctx* ctx, tfidf_group* g) {
     uint64_t* off = NULL;
     uint8_t* bytes = NULL;
     memset(&qs, 0, sizeof(qs));
-    int rc = load_queries(&bytes, &qs.nbytes, &off, &qs.nqueries);
-    if (rc == TFIDF_E_NOINPUT) { printf("Error Opening File: %s\n", g_query.file); return TFIDF_OK; }
-    if (!rc) rc = analyze_host_batch(bytes, qs.nbytes, off, qs.nqueries);
-    if (!rc) rc = ngram_host_batch(&bytes, &qs.nbytes, &off, qs.nqueries);
+    int rc;
+    if (g_expand.fuzzy != QEXP_OFF || g_expand.prefix_ops) {   /* the lines' tokens stand for the words they match */
+        expansion x;
+        rc = expansion_load(ctx, g, g_query.file, &x);
+        if (rc == TFIDF_E_NOINPUT) { printf("Error Opening File: %s\n", g_query.file); return TFIDF_OK; }
+        if (!rc) {
+            const uint8_t* const text[2] = {x.tb[0], x.tb[1]};
+            qs.nqueries = x.nq;
+            if (qexp_rewrite(&x.plan, text, x.nq, &x.m, &bytes, &qs.nbytes, &off)) rc = TFIDF_E_NOMEM;
+            expansion_free(&x);
+        }
+    } else {
+        rc = load_queries(g_query.file, &bytes, &qs.nbytes, &off, &qs.nqueries);
+        if (rc == TFIDF_E_NOINPUT) { printf("Error Opening File: %s\n", g_query.file); return TFIDF_OK; }
+        if (!rc) rc = analyze_host_batch(bytes, qs.nbytes, off, qs.nqueries);
+        if (!rc) rc = ngram_host_batch(&bytes, &qs.nbytes, &off, qs.nqueries);
+    }
     if (rc) { free(bytes); free(off); return rc; }
     qs.bytes = bytes;
     qs.q_off = off;
@@ -943,6 +1057,7 @@ static int run_model(int device) {
     tfidf_model_free(&m);   /* the context owns what it needs */
     if (!rc && g_weight.on) rc = tfidf_reweight(ctx, &g_weight.w);   /* the file records no scheme */
     if (!rc) rc = run_transform(ctx, NULL);
+    if (!rc) rc = run_suggest(ctx, NULL);   /* the dictionary is all it needs */
     tfidf_close(ctx);
     return rc ? fail(rc) : 0;
 }
@@ -997,6 +1112,7 @@ static int run_single(int device, const char* indir, const char* outpath, int de
                 out_ms, (unsigned long long)oi.text_bytes, oi.ms_prepare, oi.ms_d2h_busy, oi.ms_write, oi.writers);
     }
     rc = run_queries(ctx, NULL);
+    if (!rc) rc = run_suggest(ctx, NULL);
     if (!rc) rc = run_keywords(ctx, NULL);
     if (!rc) rc = run_similar(ctx, NULL);
     if (!rc) rc = run_clusters(ctx);
@@ -1112,6 +1228,7 @@ static int run_sharded(int ngpus, int nshards, const char* indir, const char* ou
                 (unsigned long long)pairs, wall_ms() - t_run);
     }
     rc = run_queries(NULL, g);
+    if (!rc) rc = run_suggest(NULL, g);
     if (!rc) rc = run_keywords(NULL, g);
     if (!rc) rc = run_similar(NULL, g);
     if (!rc) rc = run_transform(NULL, g);
@@ -1128,7 +1245,9 @@ static int run_sharded(int ngpus, int nshards, const char* indir, const char* ou
 
 static int usage(void) {
     fprintf(stderr, "usage: tfidf [--debug-jobs] [--stats] [--gpus N] [--shards K] [--device D] "
-                    "[--input DIR] [--output FILE] [--query FILE [--top K] [--hits FILE] [--bm25 [--bm25-k1 X] [--bm25-b Y]] [--query-ops] [--query-all] [--min-match M]] "
+                    "[--input DIR] [--output FILE] [--query FILE [--top K] [--hits FILE] [--bm25 [--bm25-k1 X] [--bm25-b Y]] [--query-ops] [--query-all] [--min-match M] "
+                    "[--fuzzy D|auto] [--prefix-ops] [--fuzzy-no-transpose] [--fuzzy-prefix P] [--max-expansions E]] "
+                    "[--suggest FILE [--suggest-file FILE]] "
                     "[--keywords K [--keywords-file FILE]] "
                     "[--similar K [--similar-docs FILE] [--similar-file FILE]] "
                     "[--clusters K [--clusters-iter I] [--clusters-seeds FILE] [--clusters-terms T] [--clusters-file FILE]] "
@@ -1139,6 +1258,7 @@ static int usage(void) {
                     "[--min-df X] [--max-df X] [--max-features M] "
                     "[--tf ratio|raw|log|binary] [--sublinear-tf] [--idf ref|smooth|plus1|none] [--norm none|l1|l2] "
                     "[--lower] [--strip-punct] [--min-token N] [--stopwords FILE] [--stem] [--utf8] [--ngrams SPEC [--ngram-joiner C]]\n"
+                    "       tfidf --model FILE --suggest FILE (--fuzzy D|auto | --prefix-ops) [--suggest-file FILE] [--device D]\n"
                     "       tfidf --model FILE --transform DIR [--transform-file FILE] [--device D] [--min-df X] [--max-df X] [--max-features M] "
                     "[--tf T] [--sublinear-tf] [--idf I] [--norm L] "
                     "[--lower] [--strip-punct] [--min-token N] [--stopwords FILE] [--stem] [--utf8] [--ngrams SPEC [--ngram-joiner C]]\n"
@@ -1162,6 +1282,11 @@ static int usage(void) {
                     "--idf plus1 is ln(N / df) + 1, --norm l1|l2 divides a document's scores by their sum or by the root of "
                     "the sum of their squares; --tf raw needs a norm; the model file does not record them; not with "
                     "--debug-jobs\n"
+                    "  --fuzzy D|auto replaces every token of a --query line by the words of the dictionary within D byte edits "
+                    "(auto: 0 up to 2 bytes, 1 up to 5, else 2; an adjacent transposition is one edit unless --fuzzy-no-transpose; "
+                    "--fuzzy-prefix P bytes must match exactly), the best --max-expansions E (default 50) by distance, then df; "
+                    "--prefix-ops reads a token ending in '*' as a prefix; --suggest FILE writes the matches of FILE's tokens "
+                    "instead of ranking with them, also from --model FILE\n"
                     "  --ngrams SPEC adds word n-grams behind the analyzer: SPEC is N (= 1-N) or A-B with 1 <= A <= B <= 8; "
                     "the words of a gram are joined by '_' or by the byte of --ngram-joiner C\n");
     return 2;
@@ -1188,6 +1313,28 @@ int main(int argc, char** argv) {
         }
         else if (!strcmp(argv[i], "--bm25")) g_query.bm25 = 1;
         else if (!strcmp(argv[i], "--query-ops")) g_query.ops = 1;
+        else if (!strcmp(argv[i], "--fuzzy") && i + 1 < argc) {
+            const char* v = argv[++i];
+            if (!strcmp(v, "auto")) g_expand.fuzzy = QEXP_AUTO;
+            else if (v[0] >= '0' && v[0] <= '2' && !v[1]) g_expand.fuzzy = v[0] - '0';
+            else { fprintf(stderr, "tfidf: --fuzzy takes 0..%u or auto\n", TFIDF_MATCH_MAX_EDITS); return 2; }
+        }
+        else if (!strcmp(argv[i], "--prefix-ops")) g_expand.prefix_ops = 1;
+        else if (!strcmp(argv[i], "--fuzzy-no-transpose")) { g_expand.no_transpose = 1; g_expand.opts = 1; }
+        else if (!strcmp(argv[i], "--fuzzy-prefix") && i + 1 < argc) {
+            const long v = atol(argv[++i]);
+            if (v < 0 || v > (long)TFIDF_MATCH_MAX_PATTERN) { fprintf(stderr, "tfidf: --fuzzy-prefix takes 0..%u\n", TFIDF_MATCH_MAX_PATTERN); return 2; }
+            g_expand.fixed_prefix = (uint32_t)v;
+            g_expand.opts = 1;
+        }
+        else if (!strcmp(argv[i], "--max-expansions") && i + 1 < argc) {
+            const long v = atol(argv[++i]);
+            if (v < 1 || v > (long)TFIDF_MATCH_MAX_EXPANSIONS) { fprintf(stderr, "tfidf: --max-expansions takes 1..%u\n", TFIDF_MATCH_MAX_EXPANSIONS); return 2; }
+            g_expand.max_expansions = (uint32_t)v;
+            g_expand.opts = 1;
+        }
+        else if (!strcmp(argv[i], "--suggest") && i + 1 < argc) g_expand.suggest = argv[++i];
+        else if (!strcmp(argv[i], "--suggest-file") && i + 1 < argc) g_expand.suggest_file = argv[++i];
         else if (!strcmp(argv[i], "--query-all")) g_query.all = 1;
         else if (!strcmp(argv[i], "--min-match") && i + 1 < argc) {
             char* end = NULL;
@@ -1372,8 +1519,28 @@ int main(int argc, char** argv) {
         const int bad = load_labels();
         if (bad) return bad;
     }
+    {   /* term expansion: what it needs and what it does not go with, before anything touches the GPU */
+        const int expanding = g_expand.fuzzy != QEXP_OFF || g_expand.prefix_ops;
+        if (g_expand.suggest && !expanding) {
+            fprintf(stderr, "tfidf: --suggest FILE needs --fuzzy D|auto or --prefix-ops\n");
+            return 2;
+        }
+        if (expanding && !g_query.file && !g_expand.suggest) {
+            fprintf(stderr, "tfidf: --fuzzy and --prefix-ops need --query FILE or --suggest FILE\n");
+            return 2;
+        }
+        if (g_expand.opts && !expanding) {
+            fprintf(stderr, "tfidf: --fuzzy-no-transpose, --fuzzy-prefix and --max-expansions need --fuzzy D|auto or --prefix-ops\n");
+            return 2;
+        }
+        if (expanding && (g_query.ops || g_query.all || g_query.min_match >= 0)) {
+            fprintf(stderr, "tfidf: --fuzzy and --prefix-ops cannot be combined with --query-ops, --query-all or --min-match: a required "
+                            "token with several expansions needs an any-of group in the clauses\n");
+            return 2;
+        }
+    }
     if (g_model.load) {   /* a model holds no pairs: nothing to rank, list or print */
-        if (!g_transform.dir) {
+        if (!g_transform.dir && !g_expand.suggest) {
             fprintf(stderr, "tfidf: --model needs --transform DIR\n");
             return 2;
         }

@@ -58,6 +58,8 @@ EXPORTS = [
     "tfidf_last_dedup_info", "tfidf_result_minhash", "tfidf_result_near_dups", "tfidf_dedup_groups",
     "tfidf_nb_check", "tfidf_nb_model_free", "tfidf_nb_labels_free", "tfidf_nb_fit", "tfidf_nb_predict",
     "tfidf_nb_predict_rows", "tfidf_nb_export", "tfidf_last_nb_info", "tfidf_result_nb_fit", "tfidf_nb_model_predict",
+    "tfidf_match_check", "tfidf_match_terms", "tfidf_term_matches_free", "tfidf_group_match_terms",
+    "tfidf_model_match_terms", "tfidf_last_match_info",
 ]
 QUERY_MAX_K = 1024  # TFIDF_QUERY_MAX_K
 RANK_TFIDF = 0  # TFIDF_RANK_TFIDF
@@ -100,6 +102,14 @@ NB_VARIANTS = {"multinomial": 0, "complement": 1}  # TFIDF_NB_MULTINOMIAL / TFID
 NB_FEATURES = {"count": 0, "binary": 1}  # TFIDF_NB_COUNT / TFIDF_NB_BINARY
 NB_ALL_SCORES = 1  # TFIDF_NB_ALL_SCORES
 NO_CLASS = 0xFFFFFFFF  # TFIDF_NO_CLASS: tfidf_nb_labels.label of a document the context does not hold
+MATCH_MAX_PATTERN = 64  # TFIDF_MATCH_MAX_PATTERN
+MATCH_MAX_EDITS = 2  # TFIDF_MATCH_MAX_EDITS
+MATCH_MAX_EXPANSIONS = 1024  # TFIDF_MATCH_MAX_EXPANSIONS
+MATCH_MAX_PATTERNS = 65536  # TFIDF_MATCH_MAX_PATTERNS
+MATCH_FUZZY = 0  # TFIDF_MATCH_FUZZY
+MATCH_PREFIX = 1  # TFIDF_MATCH_PREFIX
+MATCH_TRANSPOSE = 1  # TFIDF_MATCH_TRANSPOSE
+MATCH_DEFAULT_RECORDS = 262144  # the device match list's default capacity (tfidf_match_params.list_records == 0)
 
 
 class Corpus(C.Structure):
@@ -413,6 +423,36 @@ class NbInfo(C.Structure):
     ]
 
 
+class Patterns(C.Structure):
+    _fields_ = [
+        ("bytes", C.c_void_p), ("nbytes", C.c_uint64), ("p_off", C.c_void_p), ("npatterns", C.c_uint32),
+        ("kind", C.c_void_p), ("max_edits", C.c_void_p),
+    ]
+
+
+class MatchParams(C.Structure):
+    _fields_ = [
+        ("size", C.c_uint64), ("max_expansions", C.c_uint32), ("flags", C.c_uint32), ("fixed_prefix", C.c_uint32),
+        ("reserved", C.c_uint32), ("list_records", C.c_uint64),
+    ]
+
+
+class TermMatches(C.Structure):
+    _fields_ = [
+        ("npatterns", C.c_uint32), ("k", C.c_uint32), ("nmatch", C.POINTER(C.c_uint64)), ("nterms", C.POINTER(C.c_uint32)),
+        ("term", C.POINTER(C.c_uint32)), ("dist", C.POINTER(C.c_uint8)), ("df", C.POINTER(C.c_uint32)),
+        ("word_off", C.POINTER(C.c_uint64)), ("word_bytes", C.POINTER(C.c_uint8)),
+    ]
+
+
+class MatchInfo(C.Structure):
+    _fields_ = [
+        ("size", C.c_uint64), ("npatterns", C.c_uint32), ("k", C.c_uint32), ("ngroups", C.c_uint32),
+        ("nbatches", C.c_uint32), ("nrecords", C.c_uint64), ("list_records", C.c_uint64), ("ms_scan", C.c_double),
+        ("ms_select", C.c_double), ("ms_words", C.c_double), ("ms_total", C.c_double),
+    ]
+
+
 class DirPlan(C.Structure):
     _fields_ = [
         ("ndocs", C.c_uint32), ("nshards", C.c_uint32), ("doc_ids", C.POINTER(C.c_uint32)),
@@ -569,6 +609,15 @@ def lib() -> C.CDLL:
         L.tfidf_result_nb_fit.argtypes = [C.POINTER(Result), C.POINTER(NbParams), C.POINTER(NbModel)]
         L.tfidf_nb_model_predict.argtypes = [C.POINTER(NbModel), C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
                                              C.c_uint32, C.POINTER(NbLabels)]
+        L.tfidf_match_check.argtypes = [C.POINTER(Patterns), C.POINTER(MatchParams)]
+        L.tfidf_match_terms.argtypes = [C.c_void_p, C.POINTER(Patterns), C.POINTER(MatchParams), C.POINTER(TermMatches)]
+        L.tfidf_group_match_terms.argtypes = [C.c_void_p, C.POINTER(Patterns), C.POINTER(MatchParams),
+                                              C.POINTER(TermMatches)]
+        L.tfidf_model_match_terms.argtypes = [C.POINTER(Model), C.POINTER(Patterns), C.POINTER(MatchParams),
+                                              C.POINTER(TermMatches)]
+        L.tfidf_term_matches_free.argtypes = [C.POINTER(TermMatches)]
+        L.tfidf_term_matches_free.restype = None
+        L.tfidf_last_match_info.argtypes = [C.c_void_p, C.POINTER(MatchInfo)]
         if L.tfidf_abi_version() != ABI_VERSION:
             raise RuntimeError(f"{LIB_PATH}: ABI version {L.tfidf_abi_version()}, binding expects {ABI_VERSION} "
                                f"(stale build: rebuild with __graft_entry__.build())")
@@ -1182,6 +1231,88 @@ def nb_model_predict(model: dict, row_off, term, count, all_scores: bool = True)
         lib().tfidf_nb_labels_free(C.byref(t))
 
 
+def make_patterns(patterns, kinds=None, max_edits=None):
+    """A tfidf_patterns over bytes objects and the arrays it points into (keep both alive for the
+    call).  kinds / max_edits: one value for every pattern or one per pattern; the defaults are
+    MATCH_FUZZY and 2."""
+    n = len(patterns)
+
+    def per(v, default):
+        if v is None:
+            v = default
+        a = np.full(n, v, dtype=np.uint8) if np.isscalar(v) else np.ascontiguousarray(v, dtype=np.uint8)
+        return a if len(a) else np.zeros(1, dtype=np.uint8)
+
+    data = np.frombuffer(b"".join(patterns), dtype=np.uint8)
+    if len(data) == 0:
+        data = np.zeros(1, dtype=np.uint8)
+    off = np.zeros(n + 1, dtype=np.uint64)
+    if n:
+        off[1:] = np.cumsum([len(p) for p in patterns], dtype=np.uint64)
+    kind, edits = per(kinds, MATCH_FUZZY), per(max_edits, MATCH_MAX_EDITS)
+    ps = Patterns()
+    ps.bytes = data.ctypes.data
+    ps.nbytes = int(off[-1])
+    ps.p_off = off.ctypes.data
+    ps.npatterns = n
+    ps.kind = kind.ctypes.data
+    ps.max_edits = edits.ctypes.data
+    return ps, (data, off, kind, edits)
+
+
+def match_params(max_expansions: int = 50, transpose: bool = True, fixed_prefix: int = 0, list_records: int = 0,
+                 flags=None, size=None) -> MatchParams:
+    """A tfidf_match_params; flags and size override what transpose and sizeof give."""
+    p = MatchParams()
+    p.size = C.sizeof(MatchParams) if size is None else size
+    p.max_expansions = max_expansions
+    p.flags = (MATCH_TRANSPOSE if transpose else 0) if flags is None else flags
+    p.fixed_prefix = fixed_prefix
+    p.list_records = list_records
+    return p
+
+
+def match_check(patterns, kinds=None, max_edits=None, params: MatchParams = None, **kw) -> int:
+    """tfidf_match_check's return code (host only).  patterns: bytes objects, or a Patterns struct."""
+    ps, _keep = (patterns, None) if isinstance(patterns, Patterns) else make_patterns(patterns, kinds, max_edits)
+    p = params if params is not None else match_params(**kw)
+    return int(lib().tfidf_match_check(C.byref(ps), C.byref(p)))
+
+
+def _match_terms(fn, handle, patterns, kinds, max_edits, params, what: str, **kw) -> dict:
+    """tfidf_match_terms / tfidf_group_match_terms / tfidf_model_match_terms: per pattern nmatch,
+    nterms and the rows term, dist, df [npatterns][k], and words: a list of bytes per pattern."""
+    ps, _keep = (patterns, None) if isinstance(patterns, Patterns) else make_patterns(patterns, kinds, max_edits)
+    p = params if params is not None else match_params(**kw)
+    t = TermMatches()
+    _chk(fn(handle, C.byref(ps), C.byref(p), C.byref(t)), what)
+    try:
+        P, k = int(t.npatterns), int(t.k)
+
+        def arr(q, n, dt):
+            return np.ctypeslib.as_array(q, shape=(n,)).astype(dt, copy=True) if n else np.zeros(0, dtype=dt)
+
+        woff = arr(t.word_off, P * k + 1, np.uint64).tolist()
+        wb = bytes(arr(t.word_bytes, woff[-1], np.uint8))
+        nt = arr(t.nterms, P, np.uint32)
+        return {
+            "k": k, "nmatch": arr(t.nmatch, P, np.uint64), "nterms": nt,
+            "term": arr(t.term, P * k, np.uint32).reshape(P, k), "dist": arr(t.dist, P * k, np.uint8).reshape(P, k),
+            "df": arr(t.df, P * k, np.uint32).reshape(P, k),
+            "words": [[wb[woff[r * k + j]:woff[r * k + j + 1]] for j in range(int(nt[r]))] for r in range(P)],
+        }
+    finally:
+        lib().tfidf_term_matches_free(C.byref(t))
+
+
+def model_match_terms(model: dict, patterns, kinds=None, max_edits=None, params: MatchParams = None, **kw) -> dict:
+    """tfidf_model_match_terms (host only, plain C): the patterns against a model dict's term table;
+    term is the index into it.  Keywords as match_params."""
+    m, _keep = _model_struct(model)
+    return _match_terms(lib().tfidf_model_match_terms, C.byref(m), patterns, kinds, max_edits, params,
+                        "tfidf_model_match_terms", **kw)
+
+
 def synth_host(seed: int, V: int, mode: int, cdf, doc_ids, ntok):
     """Host generation (csrc/synth.h).  Returns (bytes uint8, doc_off uint64)."""
     ntok = np.ascontiguousarray(ntok, dtype=np.uint64)
@@ -1397,6 +1528,19 @@ class Engine:
         valid up to nterms) and words: per row the list of the words' bytes (words=False
         leaves it out)."""
         return _top_terms(lib().tfidf_top_terms, self.h, k, docs, "tfidf_top_terms", words)
+
+    def match_terms(self, patterns, kinds=None, max_edits=None, params: MatchParams = None, **kw) -> dict:
+        """Fuzzy and prefix patterns against this context's term table (tfidf_match_terms).
+        patterns: bytes objects; kinds / max_edits: one value or one per pattern (MATCH_FUZZY, 2);
+        keywords as match_params (max_expansions, transpose, fixed_prefix, list_records)."""
+        return _match_terms(lib().tfidf_match_terms, self.h, patterns, kinds, max_edits, params, "tfidf_match_terms", **kw)
+
+    def match_info(self) -> dict:
+        """Counters and device times of the last match_terms (tfidf_last_match_info)."""
+        t = MatchInfo()
+        t.size = C.sizeof(MatchInfo)
+        _chk(lib().tfidf_last_match_info(self.h, C.byref(t)), "tfidf_last_match_info")
+        return {k: getattr(t, k) for k, _ in MatchInfo._fields_ if k != "size"}
 
     def terms_info(self) -> dict:
         """Counters and device times of the last top_terms (tfidf_last_terms_info)."""
@@ -1811,6 +1955,13 @@ class Group:
         """The k best-scoring words of each document over all shards (tfidf_group_top_terms);
         see Engine.top_terms.  term is the rank in the holding shard's term table."""
         return _top_terms(lib().tfidf_group_top_terms, self.h, k, docs, "tfidf_group_top_terms", words)
+
+    def match_terms(self, patterns, kinds=None, max_edits=None, params: MatchParams = None, **kw) -> dict:
+        """Fuzzy and prefix patterns against every shard's term table, merged
+        (tfidf_group_match_terms); see Engine.match_terms.  term is UINT32_MAX, nmatch the largest
+        rank's count."""
+        return _match_terms(lib().tfidf_group_match_terms, self.h, patterns, kinds, max_edits, params,
+                            "tfidf_group_match_terms", **kw)
 
     def similar(self, k: int = 10, docs=None) -> dict:
         """The k nearest neighbours of each document over all shards (tfidf_group_similar): the
