@@ -1814,6 +1814,139 @@ typedef struct tfidf_match_info {
 } tfidf_match_info;
 int tfidf_last_match_info(const tfidf_ctx* ctx, tfidf_match_info* info);
 
+/* ---------------------------------------------------------------- snippets -- */
+
+/* Best passage and match marks for (query, document) jobs: where in a hit the query matched, and
+ * the window of W tokens a result page would show.  The run's corpus is still resident (the term
+ * table points into it), so positions are found on demand in the documents that were hit; the run
+ * stores none and there is no inverted index.  The reference has no such pass.  Everything is a
+ * comparison of bytes and integer arithmetic: the result is defined exactly.
+ *
+ *   tokens       a document's tokens t_0 .. t_{T-1} are those of tfidf_corpus: maximal runs of
+ *                bytes not in {0x20,0x09..0x0D} inside the document (a document boundary is a token
+ *                boundary); a token's term is its bytes up to its first NUL; a token beginning with
+ *                NUL has the empty term, which is a term.  T = the run's doc_size of the document
+ *   query terms  query q is tokenised as tfidf_query does.  U(q) = its distinct terms in order of
+ *                first occurrence; the first TFIDF_SNIP_MAX_TERMS are used, and when there are more
+ *                every job of q carries TFIDF_SNIP_TRUNCATED.  A term of U is found when the
+ *                resident vocabulary holds it (a term of >= 16 bytes only when the bytes are equal,
+ *                the rule of tfidf_query); only found terms match, so a word removed by tfidf_prune
+ *                no longer marks.  A term's slot is its index in U, found or not: the result does
+ *                not depend on which shard holds the document
+ *   jobs         njobs <= TFIDF_SNIP_MAX_JOBS pairs (job_query[j], job_doc[j]), the second a global
+ *                document id; any order, repeats allowed.  A document this context does not hold
+ *                gives the job TFIDF_SNIP_NO_DOC and zeros in every other field
+ *   matches      token i matches when its term equals a found u_s; then slot(i) = s
+ *   window       W = params.window.  For a start s the window is the tokens [s, min(s + W, T));
+ *                cover(s) = the distinct slots among its matches, hits(s) = its matches.  The
+ *                candidates are the match positions (any window can be moved right to its first
+ *                match without losing one).  The chosen start maximises (cover, hits), cover first;
+ *                ties go to the smallest s
+ *   centring     last = the chosen window's last match position, span = last - s + 1,
+ *                slack = W - span: s' = s - min(s, slack / 2) (integer division),
+ *                e' = min(s' + W, T).  The final window is [s', e'); cover and hits are counted
+ *                again over it (centring can bring in a match on the left).  A document without a
+ *                match gets s' = 0, e' = min(W, T), cover = hits = 0; T = 0 gives zeros
+ *   win_byte     offsets relative to the document's first byte: the first byte of token s', and the
+ *                first byte of token e' or, when e' = T, the document's length (the text may end in
+ *                whitespace; trimming is the caller's)
+ *   marks        the first min(max_marks, hits) matches of the final window in position order, each
+ *                (byte offset relative to the document, the term's length, slot)
+ *   text         with TFIDF_SNIP_TEXT the window's bytes, as the counter saw them
+ * Nothing depends on grid, batch cut or scratch budget. */
+#define TFIDF_SNIP_MAX_TERMS  256u
+#define TFIDF_SNIP_MAX_JOBS   (1u << 20)
+#define TFIDF_SNIP_MAX_WINDOW 1024u
+#define TFIDF_SNIP_MAX_MARKS  1024u
+#define TFIDF_SNIP_TEXT       1u            /* params.flags: copy the windows' bytes */
+#define TFIDF_SNIP_NO_DOC     1u            /* job flags: the context does not hold the document */
+#define TFIDF_SNIP_TRUNCATED  2u            /* job flags: the query has more than TFIDF_SNIP_MAX_TERMS distinct terms */
+#define TFIDF_SNIP_MIN_SCRATCH 65536ull
+typedef struct tfidf_snippet_params {
+    uint64_t size;               /* sizeof(tfidf_snippet_params), set by the caller */
+    uint32_t window;             /* W: 1..TFIDF_SNIP_MAX_WINDOW */
+    uint32_t max_marks;          /* M: 0..TFIDF_SNIP_MAX_MARKS */
+    uint32_t flags;              /* TFIDF_SNIP_TEXT or 0 */
+    uint32_t reserved;
+    uint64_t scratch_bytes;      /* device scratch of a batch of jobs (tile words + match records);
+                                    0: the default (256 MiB), else >= TFIDF_SNIP_MIN_SCRATCH.  A
+                                    field, not an environment knob */
+} tfidf_snippet_params;
+/* Arrays are owned by the library and released by tfidf_snippets_free(). */
+typedef struct tfidf_snippets {
+    uint32_t  njobs, nqueries;
+    /* per job */
+    uint32_t* flags;           /* TFIDF_SNIP_NO_DOC | TFIDF_SNIP_TRUNCATED */
+    uint32_t* ntokens;         /* T */
+    uint32_t* nmatch;          /* matches in the whole document */
+    uint32_t* nterms_matched;  /* distinct slots in the whole document */
+    uint32_t* win_tok;         /* 2 * njobs: (s', e') */
+    uint64_t* win_byte;        /* 2 * njobs */
+    uint32_t* cover;           /* of the final window */
+    uint32_t* hits;
+    uint64_t* mark_off;        /* njobs + 1: job j's marks are [mark_off[j], mark_off[j + 1]) */
+    uint64_t* mark_byte;
+    uint32_t* mark_len;
+    uint32_t* mark_slot;
+    uint64_t* text_off;        /* njobs + 1 (all 0 without TFIDF_SNIP_TEXT) */
+    uint8_t*  text;
+    /* per query: its used terms, U(q) cut at TFIDF_SNIP_MAX_TERMS; a term's slot is its index here */
+    uint64_t* qterm_off;       /* nqueries + 1 */
+    uint64_t* qterm_pos;       /* the term's offset inside the query's bytes */
+    uint32_t* qterm_len;
+    uint8_t*  qterm_found;
+} tfidf_snippets;
+void tfidf_snippets_free(tfidf_snippets* s);
+/* Host only, no GPU.  TFIDF_E_INVAL for: NULL; size < sizeof(tfidf_snippet_params); window == 0 or
+ * > TFIDF_SNIP_MAX_WINDOW; max_marks > TFIDF_SNIP_MAX_MARKS; unknown flag bits; scratch_bytes in
+ * 1..TFIDF_SNIP_MIN_SCRATCH-1. */
+int tfidf_snippets_check(const tfidf_snippet_params* params);
+/* Snippets of njobs jobs over the resident corpus of the last run.  TFIDF_E_STATE before a
+ * successful tfidf_run and on a model-only context (it has no corpus); TFIDF_E_INVAL for a NULL
+ * argument (job arrays may be NULL when njobs == 0), what tfidf_snippets_check refuses, bad queries
+ * as tfidf_query, njobs > TFIDF_SNIP_MAX_JOBS or a job_query[j] >= nqueries; on an error *out is
+ * zeroed.  The resident result is not disturbed and the run's corpus must still be valid, as for
+ * tfidf_query.  With a communicator attached the call is local.  The documents are scanned in
+ * tiles of 4096 bytes, so one long document spreads over the whole GPU; jobs go in batches whose
+ * tile words and match records fit scratch_bytes (one job larger than that grows the buffer once
+ * to its size).  The buffers belong to the context: a repeated identical call allocates nothing
+ * (tfidf_alloc_stats). */
+int tfidf_snippet(tfidf_ctx* ctx, const tfidf_queries* queries, const uint32_t* job_query, const uint32_t* job_doc,
+                  uint32_t njobs, const tfidf_snippet_params* params, tfidf_snippets* out);
+/* The same over every shard of a group (tfidf_group_run): every rank gets the whole job list on its
+ * own host thread and answers TFIDF_SNIP_NO_DOC for what it does not hold; the host takes each job
+ * from the rank that held it.  Slots index U(q), so the merged result equals a single shard's field
+ * for field; a query term counts as found when any rank found it. */
+int tfidf_group_snippet(tfidf_group* g, const tfidf_queries* queries, const uint32_t* job_query, const uint32_t* job_doc,
+                        uint32_t njobs, const tfidf_snippet_params* params, tfidf_snippets* out);
+/* Host only, plain C (snippet_host.c): the definition over a fetched result and the host corpus the
+ * run had (host pointers; doc_ids NULL means 1..ndocs), the second opinion on the device.  A term
+ * is found by binary search in the result's term table.  Errors as tfidf_snippet, without the
+ * state checks. */
+int tfidf_result_snippet(const tfidf_result* r, const tfidf_corpus* host_corpus, const tfidf_queries* queries,
+                         const uint32_t* job_query, const uint32_t* job_doc, uint32_t njobs,
+                         const tfidf_snippet_params* params, tfidf_snippets* out);
+/* Counters of the last tfidf_snippet (the caller sets `size` = sizeof, as tfidf_query_info). */
+typedef struct tfidf_snippet_info {
+    uint64_t size;
+    uint32_t njobs;
+    uint32_t nbatches;        /* count passes (batches of jobs by tiles) */
+    uint32_t nsubbatches;     /* write / select / emit passes (cuts by match records) */
+    uint32_t nbig;            /* jobs whose candidates took more than one select slice */
+    uint64_t ntiles;
+    uint64_t nbytes;          /* document bytes scanned by the count passes */
+    uint64_t ntokens;
+    uint64_t nmatches;
+    uint64_t scratch_bytes;   /* the budget the call ended with (grown for one job larger than it) */
+    double   ms_lookup;       /* device times (HIP events), summed */
+    double   ms_count;
+    double   ms_write;
+    double   ms_select;
+    double   ms_emit;
+    double   ms_total;        /* host wall time of the whole call */
+} tfidf_snippet_info;
+int tfidf_last_snippet_info(const tfidf_ctx* ctx, tfidf_snippet_info* info);
+
 /* ---------------------------------------------------------------- ingest ---- */
 
 /* Reference input contract (TFIDF.c:98-110,130-147): N = number of entries of `dir`

@@ -20,6 +20,7 @@
  *   engine_nb.cpp         tfidf_nb_fit, tfidf_nb_predict, tfidf_nb_predict_rows, tfidf_nb_export
  *                         (nb.hip; the check and the host twin: nb_host.c)
  *   engine_match.cpp      tfidf_match_terms (match.hip; the check and the host twin: match_host.c)
+ *   engine_snippets.cpp   tfidf_snippet (snippets.hip; the check and the host twin: snippet_host.c)
  * The add-on calls run between runs on the context's stream and use the run's arena as scratch
  * only; none of them is on the path tfidf_run times.  The add-on launches and the run's own
  * persistent kernels alike take their CU count from ctx_ncu below.
@@ -363,6 +364,15 @@ struct tfidf_ctx {
     DevBuf mt_pat, mt_cnt, mt_k0, mt_k1, mt_v0, mt_v1, mt_seg, mt_term, mt_dist, mt_df, mt_woff, mt_words;
     Event ev_mt[6];                             /* scan / select / words bounds (created by the first call) */
     tfidf_match_info mtinfo{};
+    /* snippets (tfidf_snippet, snippets.hip): the call's term offsets, bytes, keys and found flags; the
+     * queries' table words and term tables; the jobs' ids, positions, queries and documents; a batch's
+     * tile words (the jobs' first tiles, the per-tile token and match counts and their scans, the
+     * per-job totals, slices, best keys and slot masks); a sub-batch's match records, its per-job
+     * results with the marks' and texts' offsets, and the marks and window bytes.  Nothing is kept
+     * per result: positions are found anew by every call, so the invalidation table below has no row. */
+    DevBuf sn_terms, sn_tab, sn_jobs, sn_tile, sn_rec, sn_out, sn_marks;
+    Event ev_sn[10];                            /* lookup / count / write, select, emit / fill bounds (created by the first call) */
+    tfidf_snippet_info sninfo{};
 #define WR_NBUF 8
 #define WR_BUF (16ull << 20)
 #define WR_GROUPS 8

@@ -1257,6 +1257,113 @@ int tfidf_group_match_terms(tfidf_group* g, const tfidf_patterns* patterns, cons
     return TFIDF_OK;
 }
 
+/* Every rank gets the whole job list on its own host thread and answers TFIDF_SNIP_NO_DOC for what it
+ * does not hold; each job is taken from the first rank that held it.  Slots index U(q), which every
+ * rank derives from the same query bytes, so a job's fields are a single shard's; a term counts as
+ * found when any rank found it. */
+int tfidf_group_snippet(tfidf_group* g, const tfidf_queries* queries, const uint32_t* job_query, const uint32_t* job_doc,
+                        uint32_t njobs, const tfidf_snippet_params* params, tfidf_snippets* out) {
+    if (!out) return TFIDF_E_INVAL;
+    memset(out, 0, sizeof(*out));
+    if (!g) return TFIDF_E_INVAL;
+    const int R = g->n;
+    std::vector<int> rc((size_t)R, TFIDF_OK);
+    std::vector<tfidf_snippets> part((size_t)R);
+    for (tfidf_snippets& p : part) memset(&p, 0, sizeof(p));
+    {
+        std::vector<std::thread> th;
+        for (int r = 1; r < R; ++r)
+            th.emplace_back([&, r] { rc[r] = tfidf_snippet(g->ctx[r], queries, job_query, job_doc, njobs, params, &part[r]); });
+        rc[0] = tfidf_snippet(g->ctx[0], queries, job_query, job_doc, njobs, params, &part[0]);
+        for (auto& t : th) t.join();
+    }
+    int err = TFIDF_OK;
+    for (int r = 0; r < R && !err; ++r) err = rc[r];
+    tfidf_snippets m;
+    memset(&m, 0, sizeof(m));
+    std::vector<int> from((size_t)njobs, 0);
+    uint64_t nmarks = 0, ntext = 0, nT = 0;
+    if (!err) {
+        for (uint32_t j = 0; j < njobs; ++j) {
+            int r = 0;
+            while (r < R && (part[r].flags[j] & TFIDF_SNIP_NO_DOC)) ++r;
+            from[j] = r < R ? r : 0;
+            const tfidf_snippets& p = part[from[j]];
+            nmarks += p.mark_off[j + 1] - p.mark_off[j];
+            ntext += p.text_off[j + 1] - p.text_off[j];
+        }
+        const uint32_t nq = part[0].nqueries;
+        nT = part[0].qterm_off[nq];
+        m.njobs = njobs;
+        m.nqueries = nq;
+        m.flags = (uint32_t*)calloc((size_t)njobs + 1, 4);
+        m.ntokens = (uint32_t*)calloc((size_t)njobs + 1, 4);
+        m.nmatch = (uint32_t*)calloc((size_t)njobs + 1, 4);
+        m.nterms_matched = (uint32_t*)calloc((size_t)njobs + 1, 4);
+        m.win_tok = (uint32_t*)calloc(2 * (size_t)njobs + 1, 4);
+        m.win_byte = (uint64_t*)calloc(2 * (size_t)njobs + 1, 8);
+        m.cover = (uint32_t*)calloc((size_t)njobs + 1, 4);
+        m.hits = (uint32_t*)calloc((size_t)njobs + 1, 4);
+        m.mark_off = (uint64_t*)calloc((size_t)njobs + 1, 8);
+        m.text_off = (uint64_t*)calloc((size_t)njobs + 1, 8);
+        m.mark_byte = (uint64_t*)calloc((size_t)nmarks + 1, 8);
+        m.mark_len = (uint32_t*)calloc((size_t)nmarks + 1, 4);
+        m.mark_slot = (uint32_t*)calloc((size_t)nmarks + 1, 4);
+        m.text = (uint8_t*)calloc((size_t)ntext + 1, 1);
+        m.qterm_off = (uint64_t*)calloc((size_t)nq + 1, 8);
+        m.qterm_pos = (uint64_t*)calloc((size_t)nT + 1, 8);
+        m.qterm_len = (uint32_t*)calloc((size_t)nT + 1, 4);
+        m.qterm_found = (uint8_t*)calloc((size_t)nT + 1, 1);
+        if (!m.flags || !m.ntokens || !m.nmatch || !m.nterms_matched || !m.win_tok || !m.win_byte || !m.cover || !m.hits ||
+            !m.mark_off || !m.text_off || !m.mark_byte || !m.mark_len || !m.mark_slot || !m.text || !m.qterm_off ||
+            !m.qterm_pos || !m.qterm_len || !m.qterm_found)
+            err = TFIDF_E_NOMEM;
+    }
+    if (!err) {
+        uint64_t M = 0, B = 0;
+        for (uint32_t j = 0; j < njobs; ++j) {
+            const tfidf_snippets& p = part[from[j]];
+            m.flags[j] = p.flags[j];
+            m.ntokens[j] = p.ntokens[j];
+            m.nmatch[j] = p.nmatch[j];
+            m.nterms_matched[j] = p.nterms_matched[j];
+            m.win_tok[2 * (size_t)j] = p.win_tok[2 * (size_t)j];
+            m.win_tok[2 * (size_t)j + 1] = p.win_tok[2 * (size_t)j + 1];
+            m.win_byte[2 * (size_t)j] = p.win_byte[2 * (size_t)j];
+            m.win_byte[2 * (size_t)j + 1] = p.win_byte[2 * (size_t)j + 1];
+            m.cover[j] = p.cover[j];
+            m.hits[j] = p.hits[j];
+            m.mark_off[j] = M;
+            m.text_off[j] = B;
+            const uint64_t nm = p.mark_off[j + 1] - p.mark_off[j], nb = p.text_off[j + 1] - p.text_off[j];
+            if (nm) {
+                memcpy(m.mark_byte + M, p.mark_byte + p.mark_off[j], (size_t)nm * 8);
+                memcpy(m.mark_len + M, p.mark_len + p.mark_off[j], (size_t)nm * 4);
+                memcpy(m.mark_slot + M, p.mark_slot + p.mark_off[j], (size_t)nm * 4);
+            }
+            if (nb) memcpy(m.text + B, p.text + p.text_off[j], (size_t)nb);
+            M += nm;
+            B += nb;
+        }
+        m.mark_off[njobs] = M;
+        m.text_off[njobs] = B;
+        memcpy(m.qterm_off, part[0].qterm_off, ((size_t)m.nqueries + 1) * 8);
+        if (nT) {
+            memcpy(m.qterm_pos, part[0].qterm_pos, (size_t)nT * 8);
+            memcpy(m.qterm_len, part[0].qterm_len, (size_t)nT * 4);
+        }
+        for (int r = 0; r < R; ++r)
+            for (uint64_t x = 0; x < nT; ++x) m.qterm_found[x] |= part[r].qterm_found[x];
+    }
+    for (tfidf_snippets& p : part) tfidf_snippets_free(&p);
+    if (err) {
+        tfidf_snippets_free(&m);
+        return err;
+    }
+    *out = m;
+    return TFIDF_OK;
+}
+
 void tfidf_group_close(tfidf_group* g) {
     if (!g) return;
     for (tfidf_ctx* c : g->ctx)

@@ -386,6 +386,7 @@ int launch_format_f64(const double* v, uint64_t n, uint8_t* out, uint32_t* statu
 #define NB_WG_PER_CU       8u  /* k_nb_count, k_nb_sums, k_nb_predict: a wave per document or row, as k_km_assign */
 #define NB_EL_WG_PER_CU    8u  /* k_nb_argmax, k_nb_list, k_nb_weights: a thread per matrix entry */
 #define MT_WG_PER_CU       7u  /* k_mt_scan: ~21.5 KiB of LDS each (the lanes' term bytes and the group's patterns) */
+#define SN_WG_PER_CU       8u  /* k_sn_scan: ~14 KiB of LDS each (the tile, its halo, the query's keys); k_sn_select, k_sn_emit, k_sn_fill */
 #define BIG_WG_MAX         256u /* k_doc_score_big, k_sim_score_big, k_rw_docs_big: at most this many ... */
 #define BIG_WG_PER_CU      4u  /* ... and this many per CU */
 
@@ -1171,5 +1172,121 @@ int launch_match_cut(const MtCutArgs& a, hipStream_t s);
 /* launch_terms_words for the model form: entry i is bytes [woff[i], woff[i + 1]) of `bytes` */
 int launch_match_words_model(const uint32_t* term, const uint64_t* woff, uint64_t n, const MtSrc& src, uint32_t V,
                              uint8_t* bytes, hipStream_t s);
+
+/* ---- snippets over the resident corpus (snippets.hip, tfidf_snippet) ---- */
+#define SN_NT          256u      /* threads per workgroup: one lane per 16-byte group of a tile */
+#define SN_TILE        4096u     /* bytes of a job's document one workgroup trip scans */
+#define SN_HALO        64u       /* bytes behind the tile staged in LDS with it: a token that starts in the tile
+                                    reads on from LDS up to there, beyond from HBM */
+#define SN_TAB_MAX     512u      /* slots of a query's term table: 2 x TFIDF_SNIP_MAX_TERMS */
+#define SN_SLICE       1024u     /* candidate starts one select workgroup trip takes (four per lane) */
+#define SN_MAX_TILES   (1u << 20)   /* tiles of one batch: its token ordinals stay under 2^32 (2048 per tile) */
+/* an entry of a query's term table (open addressing by sn_hash, linear probing, built on the host from
+ * the keys the lookup returned; found terms only).  khi == SN_ENT_EMPTY: an empty slot */
+#define SN_ENT_EMPTY 0xEEEEEEEEEEEEEEEEull
+struct SnEnt {
+    uint64_t klo, khi;           /* the term's identity key (dev_common.h) */
+    uint64_t boff;               /* its bytes in the call's term blob: a term of >= 16 bytes is compared with them */
+    uint32_t len, slot;
+};
+static inline __host__ __device__ uint32_t sn_hash(uint64_t klo, uint64_t khi) {
+    return (uint32_t)(((klo ^ (khi * 0x9E3779B97F4A7C15ull)) * 0xD6E8FEB86659FD93ull) >> 32);
+}
+struct SnQuery {
+    uint32_t tab_off;            /* the query's table: tab[tab_off, tab_off + tab_size) */
+    uint32_t tab_size;           /* a power of two <= SN_TAB_MAX; 0: the query has no found term */
+    uint32_t lmax;               /* its longest found term: a longer token cannot match */
+    uint32_t pad;
+};
+struct SnJob {
+    uint64_t base, len;          /* the document's bytes in the corpus */
+    uint32_t query;
+    uint32_t flags;              /* TFIDF_SNIP_NO_DOC */
+    uint32_t pad[2];
+};
+/* a job's result as the emit kernel leaves it */
+struct SnOut {
+    uint32_t flags, ntokens, nmatch, nterms_matched, win_tok[2], cover, hits;
+    uint64_t win_byte[2];
+    uint32_t nmarks, pad;
+    uint64_t mlo;                /* the first mark's record in the sub-batch's list */
+    uint64_t text_len;
+};
+/* the call's distinct-per-query terms -> their keys and whether the vocabulary holds them */
+struct SnLookupArgs {
+    const uint8_t* tbytes;       /* term i = tbytes[toff[i], toff[i + 1]), NUL-free */
+    const uint64_t* toff;
+    uint32_t nterms;
+    VocabRO voc;
+    uint64_t* key;               /* 2 * nterms: klo, khi */
+    uint32_t* found;
+};
+int launch_sn_lookup(const SnLookupArgs& a, hipStream_t s);
+/* jobs -> their documents: pos[j] is the document's output position (TERMS_NO_POS: not held) */
+int launch_sn_jobs(const uint32_t* pos, const uint32_t* job_query, uint32_t njobs, const uint32_t* order,
+                   const uint64_t* doc_off, SnJob* jobs, hipStream_t s);
+/* One pass over the tiles [t0, t1) of a batch of jobs.  Tile t belongs to the job j with
+ * tile_first[j] <= t < tile_first[j + 1] and is its tile t - tile_first[j]: the bytes
+ * [p0 + k * SN_TILE, + SN_TILE) of the document, p0 = its first byte minus the misalignment of its
+ * address, so every group inside the document is one aligned 16-byte load.  A token belongs to the
+ * tile that holds its first byte.  Count pass (rec null): tile_tok[t], tile_match[t].  Write pass:
+ * both arrays hold their exclusive scans, and the tile's matches go to rec[tile_match[t] - rec0 + ..]
+ * in position order as (byte offset lo, hi, token ordinal in the document, len << 8 | slot). */
+struct SnScanArgs {
+    const uint8_t* corpus;
+    const SnJob* jobs;           /* of the batch */
+    const uint32_t* tile_first;  /* njobs + 1 */
+    uint32_t njobs;
+    uint32_t t0, t1;
+    const SnQuery* queries;
+    const SnEnt* tab;
+    const uint8_t* tbytes;
+    uint32_t* tile_tok;
+    uint32_t* tile_match;
+    uint4* rec;
+    uint32_t rec0;
+};
+int launch_sn_scan(const SnScanArgs& a, uint32_t ncu, hipStream_t s);
+/* per job of the batch: tot[2 j] = its tokens, tot[2 j + 1] = its matches, from the scanned tile arrays */
+int launch_sn_totals(const uint32_t* tile_first, uint32_t njobs, const uint32_t* tile_tok, const uint32_t* tile_match,
+                     uint32_t* tot, hipStream_t s);
+/* The jobs [j0, j1) of a batch whose match lists lie in rec from rec0 = tile_match[tile_first[j0]] on.
+ * Select: slice x of SN_SLICE candidates belongs to the job jj with slice_first[jj] <= x <
+ * slice_first[jj + 1] (jj relative to j0); best[jj] takes the maximum of cover << 44 | hits << 32 |
+ * ~position over the job's candidates (a total key: the maximum is unique), mask[4 jj ..] the OR of
+ * the document's slots.  Both zeroed by the caller. */
+struct SnSelArgs {
+    const SnJob* jobs;
+    const uint32_t* tile_first;
+    const uint32_t* tile_tok;
+    const uint32_t* tile_match;
+    uint32_t j0, j1;
+    const uint4* rec;
+    const uint32_t* slice_first; /* j1 - j0 + 1 */
+    uint32_t nslices;            /* slice_first[j1 - j0] */
+    unsigned long long* best;
+    unsigned long long* mask;
+    uint32_t window, max_marks, want_text;
+    const uint8_t* corpus;
+    SnOut* out;                  /* j1 - j0 */
+};
+int launch_sn_select(const SnSelArgs& a, uint32_t ncu, hipStream_t s);
+/* centring, the recount, the window's byte bounds: one workgroup per job, striding */
+int launch_sn_emit(const SnSelArgs& a, uint32_t ncu, hipStream_t s);
+/* the marks and the window's bytes of every job to mark_*[mark_off[jj] ..] and text[text_off[jj] ..] */
+struct SnFillArgs {
+    const SnJob* jobs;
+    uint32_t j0, j1;
+    const uint4* rec;
+    const SnOut* out;
+    const uint64_t* mark_off;    /* j1 - j0 + 1, relative to the sub-batch */
+    const uint64_t* text_off;
+    const uint8_t* corpus;
+    uint64_t* mark_byte;
+    uint32_t* mark_len;
+    uint32_t* mark_slot;
+    uint8_t* text;
+};
+int launch_sn_fill(const SnFillArgs& a, uint32_t ncu, hipStream_t s);
 
 #endif

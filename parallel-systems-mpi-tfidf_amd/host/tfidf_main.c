@@ -60,6 +60,16 @@
  *                 go to suggest.txt (--suggest-file FILE) as q<i>\t<token>\t<word>\t<dist>\t<df>;
  *                 needs --fuzzy or --prefix-ops (exit 2); also as `tfidf --model FILE --suggest
  *                 FILE`, without input/ or output.txt.
+ *   --snippets W  after the hits file, the best passage of W tokens (1..1024) of every hit
+ *                 (tfidf_snippet / tfidf_group_snippet) goes to snippets.txt (--snippets-file FILE),
+ *                 one line per hit: q<i>\tdoc<N>\t<first token>\t<cover>/<query terms>\t<text>,
+ *                 every marked term in [ ] (at most --snippet-marks M, default 32), bytes below
+ *                 0x20 as blanks, trailing blanks trimmed.  The query text is what went to the
+ *                 ranking call: behind the analyzer, under --fuzzy / --prefix-ops the rewritten
+ *                 line, with --query-ops / --query-all / --min-match the must and should texts
+ *                 joined (must-not words are not highlighted).  Works with --bm25 and --shards;
+ *                 needs --query; not with --ngrams or --model (exit 2).  The text is the corpus as
+ *                 the counter saw it (behind the analyzer).
  *
  * Keywords (the k best-scoring words of every document, tfidf_top_terms):
  *   --keywords K          after output.txt (and after the hits file of --query), one line
@@ -499,6 +509,76 @@ static void write_hits(const tfidf_hits* h, int* rc) {
     if (f && fclose(f) != 0) *rc = TFIDF_E_OUTPUT;
 }
 
+/* ---- --snippets: the best passage of every hit (tfidf_snippet / tfidf_group_snippet) ---- */
+static struct {
+    int window;         /* 0: no snippets, calls and bytes as without the option */
+    int marks;
+    const char* file;
+} g_snip = {0, 32, "snippets.txt"};
+
+/* After the hits file: the hits are the jobs, `qs` the text that went to the ranking call.  One line
+ * per hit: q<i>\tdoc<N>\t<s'>\t<cover>/<|U|>\t<text>, every marked term in [ ], bytes below 0x20
+ * as blanks, trailing blanks trimmed. */
+static int write_snippets(tfidf_ctx* ctx, tfidf_group* g, const tfidf_queries* qs, const tfidf_hits* h) {
+    if (!g_snip.window) return TFIDF_OK;
+    size_t nj = 0;
+    for (uint32_t q = 0; q < h->nqueries; ++q) nj += h->nhits[q];
+    uint32_t* jq = (uint32_t*)malloc((nj + 1) * sizeof(uint32_t));
+    uint32_t* jd = (uint32_t*)malloc((nj + 1) * sizeof(uint32_t));
+    if (!jq || !jd) { free(jq); free(jd); return TFIDF_E_NOMEM; }
+    nj = 0;
+    for (uint32_t q = 0; q < h->nqueries; ++q)
+        for (uint32_t i = 0; i < h->nhits[q]; ++i) {
+            jq[nj] = q;
+            jd[nj++] = h->doc[(size_t)q * h->k + i];
+        }
+    tfidf_snippet_params pr;
+    memset(&pr, 0, sizeof(pr));
+    pr.size = sizeof(pr);
+    pr.window = (uint32_t)g_snip.window;
+    pr.max_marks = (uint32_t)g_snip.marks;
+    pr.flags = TFIDF_SNIP_TEXT;
+    tfidf_snippets s;
+    int rc = g ? tfidf_group_snippet(g, qs, jq, jd, (uint32_t)nj, &pr, &s) : tfidf_snippet(ctx, qs, jq, jd, (uint32_t)nj, &pr, &s);
+    if (!rc) {
+        FILE* f = fopen(g_snip.file, "w");
+        if (!f) printf("Error Opening File: %s\n", g_snip.file);
+        for (size_t j = 0; f && j < nj; ++j) {
+            const uint8_t* t = s.text + s.text_off[j];
+            const uint64_t n = s.text_off[j + 1] - s.text_off[j], base = s.win_byte[2 * j];
+            const uint64_t m0 = s.mark_off[j], m1 = s.mark_off[j + 1];
+            uint8_t* line = (uint8_t*)malloc((size_t)(n + 2 * (m1 - m0) + 1));
+            if (!line) { rc = TFIDF_E_NOMEM; break; }
+            uint64_t len = 0, at = 0;
+            for (uint64_t m = m0; m < m1; ++m) {   /* the marks lie inside the text, in position order */
+                const uint64_t b = s.mark_byte[m] - base, e = b + s.mark_len[m];
+                memcpy(line + len, t + at, (size_t)(b - at));
+                len += b - at;
+                line[len++] = '[';
+                memcpy(line + len, t + b, (size_t)(e - b));
+                len += e - b;
+                line[len++] = ']';
+                at = e;
+            }
+            memcpy(line + len, t + at, (size_t)(n - at));
+            len += n - at;
+            for (uint64_t i = 0; i < len; ++i)
+                if (line[i] < 0x20u) line[i] = ' ';
+            while (len && line[len - 1] == ' ') --len;
+            fprintf(f, "q%u\tdoc%u\t%u\t%u/%llu\t", jq[j] + 1, jd[j], s.win_tok[2 * j], s.cover[j],
+                    (unsigned long long)(s.qterm_off[jq[j] + 1] - s.qterm_off[jq[j]]));
+            fwrite(line, 1, (size_t)len, f);
+            free(line);
+            fputc('\n', f);
+        }
+        if (f && fclose(f) != 0) rc = TFIDF_E_OUTPUT;
+        tfidf_snippets_free(&s);
+    }
+    free(jq);
+    free(jd);
+    return rc;
+}
+
 /* --query with --query-ops, --query-all or --min-match: the lines' tokens sorted into the three
  * texts (query_ops.h), each text through the analyzer and the n-grams like the lines themselves */
 static int run_clause_queries(tfidf_ctx* ctx, tfidf_group* g) {
@@ -551,6 +631,34 @@ static int run_clause_queries(tfidf_ctx* ctx, tfidf_group* g) {
         rc = g ? tfidf_group_query_clauses(g, &cl, g_query.top, &h) : tfidf_query_clauses(ctx, &cl, g_query.top, &h);
     }
     if (!rc) write_hits(&h, &rc);
+    if (!rc && g_snip.window) {   /* the must and should texts joined; must-not words are not highlighted */
+        tfidf_queries joined;
+        memset(&joined, 0, sizeof(joined));
+        uint64_t* jo = (uint64_t*)malloc(((size_t)nq + 1) * sizeof(uint64_t));
+        uint8_t* jb = (uint8_t*)malloc((size_t)(tn[QOPS_MUST] + tn[QOPS_SHOULD] + nq + 1));
+        if (!jo || !jb) rc = TFIDF_E_NOMEM;
+        uint64_t at = 0;
+        for (uint32_t q = 0; !rc && q < nq; ++q) {
+            jo[q] = at;
+            for (int c = 0; c < 2; ++c) {
+                const int x = c ? QOPS_SHOULD : QOPS_MUST;
+                const uint64_t n = to[x][q + 1] - to[x][q];
+                memcpy(jb + at, tb[x] + to[x][q], (size_t)n);
+                at += n;
+                if (!c) jb[at++] = ' ';
+            }
+        }
+        if (!rc) {
+            jo[nq] = at;
+            joined.bytes = jb;
+            joined.nbytes = at;
+            joined.q_off = jo;
+            joined.nqueries = nq;
+            rc = write_snippets(ctx, g, &joined, &h);
+        }
+        free(jo);
+        free(jb);
+    }
     tfidf_hits_free(&h);
     free(mm);
     for (int c = 0; c < 3; ++c) { free(tb[c]); free(to[c]); }
@@ -598,6 +706,7 @@ static int run_queries(tfidf_ctx* ctx, tfidf_group* g) {
         rc = g ? tfidf_group_query(g, &qs, g_query.top, &h) : tfidf_query(ctx, &qs, g_query.top, &h);
     }
     if (!rc) write_hits(&h, &rc);
+    if (!rc) rc = write_snippets(ctx, g, &qs, &h);
     tfidf_hits_free(&h);
     free(bytes);
     free(off);
@@ -1248,6 +1357,7 @@ static int usage(void) {
                     "[--input DIR] [--output FILE] [--query FILE [--top K] [--hits FILE] [--bm25 [--bm25-k1 X] [--bm25-b Y]] [--query-ops] [--query-all] [--min-match M] "
                     "[--fuzzy D|auto] [--prefix-ops] [--fuzzy-no-transpose] [--fuzzy-prefix P] [--max-expansions E]] "
                     "[--suggest FILE [--suggest-file FILE]] "
+                    "[--snippets W [--snippet-marks M] [--snippets-file FILE]] "
                     "[--keywords K [--keywords-file FILE]] "
                     "[--similar K [--similar-docs FILE] [--similar-file FILE]] "
                     "[--clusters K [--clusters-iter I] [--clusters-seeds FILE] [--clusters-terms T] [--clusters-file FILE]] "
@@ -1287,6 +1397,8 @@ static int usage(void) {
                     "--fuzzy-prefix P bytes must match exactly), the best --max-expansions E (default 50) by distance, then df; "
                     "--prefix-ops reads a token ending in '*' as a prefix; --suggest FILE writes the matches of FILE's tokens "
                     "instead of ranking with them, also from --model FILE\n"
+                    "  --snippets W writes the best passage of W tokens of every hit of --query to snippets.txt, the matched words "
+                    "in [ ] (at most --snippet-marks M); not with --ngrams or --model\n"
                     "  --ngrams SPEC adds word n-grams behind the analyzer: SPEC is N (= 1-N) or A-B with 1 <= A <= B <= 8; "
                     "the words of a gram are joined by '_' or by the byte of --ngram-joiner C\n");
     return 2;
@@ -1336,6 +1448,14 @@ int main(int argc, char** argv) {
         else if (!strcmp(argv[i], "--suggest") && i + 1 < argc) g_expand.suggest = argv[++i];
         else if (!strcmp(argv[i], "--suggest-file") && i + 1 < argc) g_expand.suggest_file = argv[++i];
         else if (!strcmp(argv[i], "--query-all")) g_query.all = 1;
+        else if (!strcmp(argv[i], "--snippets") && i + 1 < argc) {
+            g_snip.window = atoi(argv[++i]);
+            if (g_snip.window < 1 || g_snip.window > (int)TFIDF_SNIP_MAX_WINDOW) return usage();
+        } else if (!strcmp(argv[i], "--snippet-marks") && i + 1 < argc) {
+            g_snip.marks = atoi(argv[i + 1]);
+            if (g_snip.marks < 0 || g_snip.marks > (int)TFIDF_SNIP_MAX_MARKS || (g_snip.marks == 0 && strcmp(argv[i + 1], "0"))) return usage();
+            ++i;
+        } else if (!strcmp(argv[i], "--snippets-file") && i + 1 < argc) g_snip.file = argv[++i];
         else if (!strcmp(argv[i], "--min-match") && i + 1 < argc) {
             char* end = NULL;
             const char* a = argv[++i];
@@ -1540,6 +1660,10 @@ int main(int argc, char** argv) {
         }
     }
     if (g_model.load) {   /* a model holds no pairs: nothing to rank, list or print */
+        if (g_snip.window) {
+            fprintf(stderr, "tfidf: --snippets cannot be combined with --model: a model holds no corpus\n");
+            return 2;
+        }
         if (!g_transform.dir && !g_expand.suggest) {
             fprintf(stderr, "tfidf: --model needs --transform DIR\n");
             return 2;
@@ -1551,6 +1675,11 @@ int main(int argc, char** argv) {
         }
         if (tfidf_device_count() <= 0) return fail(TFIDF_E_NODEV);
         return run_model(device >= 0 ? device : 0);
+    }
+    if (g_snip.window && (!g_query.file || g_ng.on)) {
+        fprintf(stderr, g_ng.on ? "tfidf: --snippets cannot be combined with --ngrams: a gram is no passage of the text\n"
+                                : "tfidf: --snippets W needs --query FILE\n");
+        return 2;
     }
     if (g_query.bm25 && !g_query.file) {   /* nothing to rank: say so instead of ignoring the switch */
         fprintf(stderr, "tfidf: --bm25, --bm25-k1 and --bm25-b need --query FILE\n");

@@ -60,6 +60,8 @@ EXPORTS = [
     "tfidf_nb_predict_rows", "tfidf_nb_export", "tfidf_last_nb_info", "tfidf_result_nb_fit", "tfidf_nb_model_predict",
     "tfidf_match_check", "tfidf_match_terms", "tfidf_term_matches_free", "tfidf_group_match_terms",
     "tfidf_model_match_terms", "tfidf_last_match_info",
+    "tfidf_snippets_check", "tfidf_snippets_free", "tfidf_snippet", "tfidf_group_snippet", "tfidf_result_snippet",
+    "tfidf_last_snippet_info",
 ]
 QUERY_MAX_K = 1024  # TFIDF_QUERY_MAX_K
 RANK_TFIDF = 0  # TFIDF_RANK_TFIDF
@@ -110,6 +112,14 @@ MATCH_FUZZY = 0  # TFIDF_MATCH_FUZZY
 MATCH_PREFIX = 1  # TFIDF_MATCH_PREFIX
 MATCH_TRANSPOSE = 1  # TFIDF_MATCH_TRANSPOSE
 MATCH_DEFAULT_RECORDS = 262144  # the device match list's default capacity (tfidf_match_params.list_records == 0)
+SNIP_MAX_TERMS = 256  # TFIDF_SNIP_MAX_TERMS
+SNIP_MAX_JOBS = 1 << 20  # TFIDF_SNIP_MAX_JOBS
+SNIP_MAX_WINDOW = 1024  # TFIDF_SNIP_MAX_WINDOW
+SNIP_MAX_MARKS = 1024  # TFIDF_SNIP_MAX_MARKS
+SNIP_TEXT = 1  # TFIDF_SNIP_TEXT
+SNIP_NO_DOC = 1  # TFIDF_SNIP_NO_DOC
+SNIP_TRUNCATED = 2  # TFIDF_SNIP_TRUNCATED
+SNIP_MIN_SCRATCH = 65536  # TFIDF_SNIP_MIN_SCRATCH
 
 
 class Corpus(C.Structure):
@@ -453,6 +463,35 @@ class MatchInfo(C.Structure):
     ]
 
 
+class SnippetParams(C.Structure):
+    _fields_ = [
+        ("size", C.c_uint64), ("window", C.c_uint32), ("max_marks", C.c_uint32), ("flags", C.c_uint32),
+        ("reserved", C.c_uint32), ("scratch_bytes", C.c_uint64),
+    ]
+
+
+class Snippets(C.Structure):
+    _fields_ = [
+        ("njobs", C.c_uint32), ("nqueries", C.c_uint32), ("flags", C.POINTER(C.c_uint32)),
+        ("ntokens", C.POINTER(C.c_uint32)), ("nmatch", C.POINTER(C.c_uint32)),
+        ("nterms_matched", C.POINTER(C.c_uint32)), ("win_tok", C.POINTER(C.c_uint32)),
+        ("win_byte", C.POINTER(C.c_uint64)), ("cover", C.POINTER(C.c_uint32)), ("hits", C.POINTER(C.c_uint32)),
+        ("mark_off", C.POINTER(C.c_uint64)), ("mark_byte", C.POINTER(C.c_uint64)), ("mark_len", C.POINTER(C.c_uint32)),
+        ("mark_slot", C.POINTER(C.c_uint32)), ("text_off", C.POINTER(C.c_uint64)), ("text", C.POINTER(C.c_uint8)),
+        ("qterm_off", C.POINTER(C.c_uint64)), ("qterm_pos", C.POINTER(C.c_uint64)), ("qterm_len", C.POINTER(C.c_uint32)),
+        ("qterm_found", C.POINTER(C.c_uint8)),
+    ]
+
+
+class SnippetInfo(C.Structure):
+    _fields_ = [
+        ("size", C.c_uint64), ("njobs", C.c_uint32), ("nbatches", C.c_uint32), ("nsubbatches", C.c_uint32),
+        ("nbig", C.c_uint32), ("ntiles", C.c_uint64), ("nbytes", C.c_uint64), ("ntokens", C.c_uint64),
+        ("nmatches", C.c_uint64), ("scratch_bytes", C.c_uint64), ("ms_lookup", C.c_double), ("ms_count", C.c_double),
+        ("ms_write", C.c_double), ("ms_select", C.c_double), ("ms_emit", C.c_double), ("ms_total", C.c_double),
+    ]
+
+
 class DirPlan(C.Structure):
     _fields_ = [
         ("ndocs", C.c_uint32), ("nshards", C.c_uint32), ("doc_ids", C.POINTER(C.c_uint32)),
@@ -618,6 +657,14 @@ def lib() -> C.CDLL:
         L.tfidf_term_matches_free.argtypes = [C.POINTER(TermMatches)]
         L.tfidf_term_matches_free.restype = None
         L.tfidf_last_match_info.argtypes = [C.c_void_p, C.POINTER(MatchInfo)]
+        L.tfidf_snippets_check.argtypes = [C.POINTER(SnippetParams)]
+        L.tfidf_snippets_free.argtypes = [C.POINTER(Snippets)]
+        L.tfidf_snippets_free.restype = None
+        snip = [C.POINTER(Queries), C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(SnippetParams), C.POINTER(Snippets)]
+        L.tfidf_snippet.argtypes = [C.c_void_p] + snip
+        L.tfidf_group_snippet.argtypes = [C.c_void_p] + snip
+        L.tfidf_result_snippet.argtypes = [C.POINTER(Result), C.POINTER(Corpus)] + snip
+        L.tfidf_last_snippet_info.argtypes = [C.c_void_p, C.POINTER(SnippetInfo)]
         if L.tfidf_abi_version() != ABI_VERSION:
             raise RuntimeError(f"{LIB_PATH}: ABI version {L.tfidf_abi_version()}, binding expects {ABI_VERSION} "
                                f"(stale build: rebuild with __graft_entry__.build())")
@@ -1313,6 +1360,93 @@ def model_match_terms(model: dict, patterns, kinds=None, max_edits=None, params:
                         "tfidf_model_match_terms", **kw)
 
 
+def snippet_params(window: int = 32, max_marks: int = 32, text: bool = True, scratch_bytes: int = 0, flags=None,
+                   size=None) -> SnippetParams:
+    """A tfidf_snippet_params; flags and size override what text and sizeof give."""
+    p = SnippetParams()
+    p.size = C.sizeof(SnippetParams) if size is None else size
+    p.window, p.max_marks = window, max_marks
+    p.flags = (SNIP_TEXT if text else 0) if flags is None else flags
+    p.scratch_bytes = scratch_bytes
+    return p
+
+
+def snippet_check(params: SnippetParams = None, **kw) -> int:
+    """tfidf_snippets_check's return code (host only).  Keywords as snippet_params."""
+    p = params if params is not None else snippet_params(**kw)
+    return int(lib().tfidf_snippets_check(C.byref(p)))
+
+
+def hits_to_jobs(hits: dict):
+    """The (query, document) pairs of a query() result, row by row."""
+    return [(q, int(hits["doc"][q, j])) for q in range(len(hits["nhits"])) for j in range(int(hits["nhits"][q]))]
+
+
+def _snippets(fn, handles, queries, jobs, hits, params, what: str, **kw) -> dict:
+    """tfidf_snippet / tfidf_group_snippet / tfidf_result_snippet.  jobs: (query index, global document
+    id) pairs, or hits: a dict from query().  Returns the per-job arrays, marks: per job a list of
+    (byte offset in the document, length, slot), text: per job the window's bytes (None without
+    text), and qterms: per query a list of (offset in the query, length, found)."""
+    if jobs is None:
+        jobs = hits_to_jobs(hits) if hits is not None else []
+    qs, _keep = _queries(queries)
+    jq = np.ascontiguousarray([j[0] for j in jobs], dtype=np.uint32)
+    jd = np.ascontiguousarray([j[1] for j in jobs], dtype=np.uint32)
+    p = params if params is not None else snippet_params(**kw)
+    t = Snippets()
+    _chk(fn(*handles, C.byref(qs), _ptr(jq) if len(jobs) else None, _ptr(jd) if len(jobs) else None, len(jobs),
+            C.byref(p), C.byref(t)), what)
+    try:
+        J, Q = int(t.njobs), int(t.nqueries)
+
+        def arr(q, n, dt):
+            return np.ctypeslib.as_array(q, shape=(n,)).astype(dt, copy=True) if n else np.zeros(0, dtype=dt)
+
+        moff = arr(t.mark_off, J + 1, np.uint64).tolist()
+        toff = arr(t.text_off, J + 1, np.uint64).tolist()
+        qoff = arr(t.qterm_off, Q + 1, np.uint64).tolist()
+        mb, ml, ms = (arr(a, moff[-1], dt).tolist() for a, dt in
+                      ((t.mark_byte, np.uint64), (t.mark_len, np.uint32), (t.mark_slot, np.uint32)))
+        tb = bytes(arr(t.text, toff[-1], np.uint8))
+        qp, ql, qf = (arr(a, qoff[-1], dt).tolist() for a, dt in
+                      ((t.qterm_pos, np.uint64), (t.qterm_len, np.uint32), (t.qterm_found, np.uint8)))
+        want_text = bool(p.flags & SNIP_TEXT)
+        return {
+            "flags": arr(t.flags, J, np.uint32), "ntokens": arr(t.ntokens, J, np.uint32),
+            "nmatch": arr(t.nmatch, J, np.uint32), "nterms_matched": arr(t.nterms_matched, J, np.uint32),
+            "win_tok": arr(t.win_tok, 2 * J, np.uint32).reshape(J, 2),
+            "win_byte": arr(t.win_byte, 2 * J, np.uint64).reshape(J, 2),
+            "cover": arr(t.cover, J, np.uint32), "hits": arr(t.hits, J, np.uint32),
+            "marks": [list(zip(mb[moff[j]:moff[j + 1]], ml[moff[j]:moff[j + 1]], ms[moff[j]:moff[j + 1]]))
+                      for j in range(J)],
+            "text": [tb[toff[j]:toff[j + 1]] if want_text else None for j in range(J)],
+            "qterms": [list(zip(qp[qoff[q]:qoff[q + 1]], ql[qoff[q]:qoff[q + 1]], qf[qoff[q]:qoff[q + 1]]))
+                       for q in range(Q)],
+        }
+    finally:
+        lib().tfidf_snippets_free(C.byref(t))
+
+
+def result_snippets(res: dict, data, off, queries, jobs=None, hits=None, doc_ids=None, params: SnippetParams = None,
+                    **kw) -> dict:
+    """tfidf_result_snippet (host only, plain C): the definition over a fetched result's term table
+    (res["terms"]) and the host corpus the run had.  Keywords as snippet_params."""
+    terms = res["terms"]
+    toff = np.zeros(len(terms) + 1, dtype=np.uint64)
+    if terms:
+        toff[1:] = np.cumsum([len(t) for t in terms], dtype=np.uint64)
+    tb = np.frombuffer(b"".join(terms) + b"\0", dtype=np.uint8)
+    r = Result()
+    r.nterms = len(terms)
+    r.term_off = toff.ctypes.data_as(C.POINTER(C.c_uint64))
+    r.term_bytes = tb.ctypes.data_as(C.POINTER(C.c_uint8))
+    c, _keep = _host_corpus(data, off)
+    ids = None if doc_ids is None else np.ascontiguousarray(doc_ids, dtype=np.uint32)
+    c.doc_ids = None if ids is None else ids.ctypes.data
+    return _snippets(lib().tfidf_result_snippet, (C.byref(r), C.byref(c)), queries, jobs, hits, params,
+                     "tfidf_result_snippet", **kw)
+
+
 def synth_host(seed: int, V: int, mode: int, cdf, doc_ids, ntok):
     """Host generation (csrc/synth.h).  Returns (bytes uint8, doc_off uint64)."""
     ntok = np.ascontiguousarray(ntok, dtype=np.uint64)
@@ -1541,6 +1675,19 @@ class Engine:
         t.size = C.sizeof(MatchInfo)
         _chk(lib().tfidf_last_match_info(self.h, C.byref(t)), "tfidf_last_match_info")
         return {k: getattr(t, k) for k, _ in MatchInfo._fields_ if k != "size"}
+
+    def snippets(self, queries, jobs=None, hits=None, params: SnippetParams = None, **kw) -> dict:
+        """Best passage and match marks of (query, document) jobs over the resident corpus
+        (tfidf_snippet).  jobs: (query index, global document id) pairs, or hits: a dict from
+        query(); keywords as snippet_params (window, max_marks, text, scratch_bytes)."""
+        return _snippets(lib().tfidf_snippet, (self.h,), queries, jobs, hits, params, "tfidf_snippet", **kw)
+
+    def snippet_info(self) -> dict:
+        """Counters and device times of the last snippets (tfidf_last_snippet_info)."""
+        t = SnippetInfo()
+        t.size = C.sizeof(SnippetInfo)
+        _chk(lib().tfidf_last_snippet_info(self.h, C.byref(t)), "tfidf_last_snippet_info")
+        return {n: getattr(t, n) for n, _ in SnippetInfo._fields_ if n != "size"}
 
     def terms_info(self) -> dict:
         """Counters and device times of the last top_terms (tfidf_last_terms_info)."""
@@ -1962,6 +2109,10 @@ class Group:
         rank's count."""
         return _match_terms(lib().tfidf_group_match_terms, self.h, patterns, kinds, max_edits, params,
                             "tfidf_group_match_terms", **kw)
+
+    def snippets(self, queries, jobs=None, hits=None, params: SnippetParams = None, **kw) -> dict:
+        """Snippets over all shards (tfidf_group_snippet); see Engine.snippets."""
+        return _snippets(lib().tfidf_group_snippet, (self.h,), queries, jobs, hits, params, "tfidf_group_snippet", **kw)
 
     def similar(self, k: int = 10, docs=None) -> dict:
         """The k nearest neighbours of each document over all shards (tfidf_group_similar): the
