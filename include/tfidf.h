@@ -214,6 +214,12 @@ typedef struct tfidf_run_info {
 #define TFIDF_RUN_K1_ST   4u  /* retired: round 3's k_tokcount_st (removed in round 5), never set */
 #define TFIDF_RUN_K1_SL   8u  /* ... run as k_tokcount_sl (the default, vocabulary table <= 32M slots);
                                  neither ST nor SL with VS set: k_tokcount_vs (larger tables) */
+#define TFIDF_RUN_REC_PACK 32u  /* K1 emitted packed records: one word (count, slot) per complete
+                                   document's record (k_tokcount_sl, table <= 4M slots, env TFIDF_REC_PACK
+                                   not 0) */
+#define TFIDF_RUN_REC_PACK_KEPT 64u  /* ... and they stayed one word through DF and the score kernels
+                                        (V <= 65536, ranks no wider than the slot field); clear: unpacked
+                                        after K1 */
 #define TFIDF_RUN_XCHG_DENSE 16u  /* multi-rank: the DF exchange used the dense all-reduce form
                                      (else the hash-owner all-to-all; single rank: no exchange) */
 int tfidf_last_run_info(tfidf_ctx* ctx, tfidf_run_info* info);

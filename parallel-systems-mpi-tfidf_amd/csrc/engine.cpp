@@ -190,6 +190,8 @@ int tfidf_open(int device, tfidf_ctx** out) {
     ctx->xb_stage_max = kxb ? (uint32_t)atoi(kxb) : ~0u;
     const char* kds = getenv("TFIDF_DF_SPLIT");
     ctx->df_split = !(kds && !strcmp(kds, "0"));
+    const char* krp = getenv("TFIDF_REC_PACK");
+    ctx->rec_pack = !(krp && !strcmp(krp, "0"));
     const char* kn = getenv("TFIDF_TEST_XNOMEM_RANK");
     ctx->xnomem_rank = kn ? atoi(kn) : -1;
     /* the numeric range knobs (knobs.h): unset or rejected, the member's default stays */
@@ -714,6 +716,10 @@ static int run_local(tfidf_ctx* ctx, const CorpusDev& c, const uint32_t* dev_ids
     /* tokcount_sl over a high-cardinality table (past K1_ST_MAX_CAP slots): half-size chunks,
      * as tokcount_vs, since nearly every token is a new pair for its LDS table */
     const uint32_t cb = ctx->k1_sl ? (ctx->vcap > K1_ST_MAX_CAP ? CHUNK_BYTES : CHUNK_BYTES_ST) : CHUNK_BYTES;
+    /* packed records: k_tokcount_sl over a table whose slot leaves the count 10 bits or more */
+    ctx->run_pack = ctx->rec_pack && ctx->k1_sl && ctx->vcap <= K1_ST_MAX_CAP;
+    ctx->run_pack_kept = false;
+    const uint32_t sbits = (uint32_t)__builtin_popcountll(ctx->vcap - 1);   /* the capacity is a power of two */
     const uint64_t nchunks = span ? (span + cb - 1) / cb : 0;
     if (ctx->rec_cap == 0) ctx->rec_cap = span / 6 + 4096;
     if (ctx->part_cap == 0) ctx->part_cap = span / 64 + 4096;
@@ -791,7 +797,7 @@ static int run_local(tfidf_ctx* ctx, const CorpusDev& c, const uint32_t* dev_ids
             ctx->k1out_valid = true;
         }
         LCHK(launch_tokcount_sl(c, ctx->chunk_start.as<uint64_t>(), ctx->chunk_doc.as<uint32_t>(), 0, nchunks, vd,
-                                ctx->k1out_dev.as<K1Out>(), s, ctx_ncu(ctx), &k1_wgs));
+                                ctx->k1out_dev.as<K1Out>(), s, ctx_ncu(ctx), &k1_wgs, ctx->run_pack ? 1u : 0u));
     } else if (nchunks && ctx->k1_vs)
         LCHK(launch_tokcount_vs(c, ctx->chunk_start.as<uint64_t>(), ctx->chunk_doc.as<uint32_t>(), 0, nchunks, vd, o, s,
                                 ctx_ncu(ctx), &k1_wgs));
@@ -909,6 +915,13 @@ static int run_local(tfidf_ctx* ctx, const CorpusDev& c, const uint32_t* dev_ids
         const int rc = enqueue_doc_order(ctx, dev_ids, N, ctx->stream2);
         if (rc) return rc;
     }
+    /* K1's packed records stay one word where the DF pass and the ranks allow it (the LDS
+     * histogram, ranks no wider than the slot field); otherwise one pass splits them into
+     * rec_slot / rec_cnt here and the run goes on with two-word records */
+    ctx->run_pack_kept = ctx->run_pack && df_keeps_packed(V, sbits);
+    if (ctx->run_pack && !ctx->run_pack_kept)
+        LCHK(launch_rec_unpack(ctx->rec_slot.as<uint32_t>(), ctx->rec_cnt.as<uint32_t>(), R_main, sbits, s));
+    const uint32_t df_pack = ctx->run_pack_kept ? sbits : 0u;
     /* split DF: with partial records to merge, the main records' histogram (which needs only
      * the term ranks) starts on stream2 now and runs beside the merge stage's short
      * launches; the merged records are added after the merge (accumulate pass below) */
@@ -930,7 +943,8 @@ static int run_local(tfidf_ctx* ctx, const CorpusDev& c, const uint32_t* dev_ids
         HIPCHK(hipEventRecord(ctx->ev_vrank, s));
         HIPCHK(hipStreamWaitEvent(ctx->stream2, ctx->ev_vrank, 0));
         const int dl = launch_df_hist(ctx->rec_slot.as<uint32_t>(), R_main, nullptr, R_main, ctx->rank_of_slot.as<uint32_t>(),
-                                      r16, V, cap, (uint32_t*)(cnt + 3), ctx->df_local.as<uint32_t>(), da, ctx->stream2);
+                                      r16, V, cap, (uint32_t*)(cnt + 3), ctx->df_local.as<uint32_t>(), da, ctx->stream2,
+                                      false, df_pack);
         if (dl == -2) {   /* its own scratch was short: grow it (not the arena) and retry */
             ctx->df_scratch_min = da.peak + da.peak / 2 + 4096;
             return 1;
@@ -1061,7 +1075,7 @@ static int run_local(tfidf_ctx* ctx, const CorpusDev& c, const uint32_t* dev_ids
         /* also rewrites every record's slot as its term rank (K5 then needs no rank gather) */
         LCHK(launch_df_hist(ctx->rec_slot.as<uint32_t>(), R_main, merged_count, R_total,
                             ctx->rank_of_slot.as<uint32_t>(), r16, V, cap, (uint32_t*)(cnt + 3),
-                            ctx->df_local.as<uint32_t>(), ar, s));
+                            ctx->df_local.as<uint32_t>(), ar, s, false, df_pack));
     }
     ctx->run_V = V;
     ctx->run_cap = cap;
@@ -1313,7 +1327,9 @@ static int run_post(tfidf_ctx* ctx, uint64_t Nt) {
     }
     a.ndocs = N;
     a.nterms = V;
-    a.rank_bits = V > 1 ? 32u - (uint32_t)__builtin_clz(V - 1) : 1u;
+    a.rank_bits = k5_rank_bits(V);
+    a.rec_pack = ctx->run_pack_kept ? 1u : 0u;   /* the packed DF pass wrote rank << pack_cb | count */
+    a.pack_cb = ctx->run_pack_kept ? 32u - a.rank_bits : 0u;
     a.rec_total = R_total;
     a.slot_cap = cap;
     a.status = (uint32_t*)(cnt + 3);
@@ -1591,6 +1607,7 @@ extern "C" int tfidf_last_run_info(tfidf_ctx* ctx, tfidf_run_info* out) {
     for (int i = 0; i < S_NSTAGES; ++i) info->ms_stage[i] = ctx->ms_stage[i];
     info->nstages = S_NSTAGES;
     info->flags = (ctx->k1_vs ? TFIDF_RUN_K1_VS : 0u) | (ctx->k1_sl ? TFIDF_RUN_K1_SL : 0u) |
+                  (ctx->run_pack ? TFIDF_RUN_REC_PACK : 0u) | (ctx->run_pack_kept ? TFIDF_RUN_REC_PACK_KEPT : 0u) |
                   (ctx->xp && ctx->last_dense ? TFIDF_RUN_XCHG_DENSE : 0u);
     info->device_allocs = g_dev_allocs.load(std::memory_order_relaxed);
     info->device_alloc_bytes = g_dev_alloc_bytes.load(std::memory_order_relaxed);

@@ -145,6 +145,12 @@ struct tfidf_ctx {
      * beside the merge stage, the merged records' is added on the main stream after it */
     bool df_split = true;           /* env TFIDF_DF_SPLIT=0: one DF pass after the merge */
     Event ev_vrank, ev_dfmain;
+    /* packed records: k_tokcount_sl over a table of at most K1_ST_MAX_CAP slots emits a
+     * complete document's record as one word; the run keeps it one word through DF and the score
+     * kernels where df_keeps_packed allows, and unpacks it after K1 otherwise */
+    bool rec_pack = true;           /* env TFIDF_REC_PACK=0: two-word records throughout */
+    bool run_pack = false;          /* this run's K1 emitted packed records */
+    bool run_pack_kept = false;     /* ... and they stayed packed through DF and the score kernels */
     DevBuf df_scratch;
     size_t df_scratch_min = 0;      /* grown when the split DF pass reported a shortfall (retried) */
     Arena arena2;

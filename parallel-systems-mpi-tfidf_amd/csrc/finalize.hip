@@ -764,7 +764,10 @@ __device__ __forceinline__ uint32_t dfh_cslot(uint32_t slot) { return (slot * 0x
  * instead of 4.4 GB).  A u16 counter then moves 0x8000 into the global df whenever it
  * reaches 0x8000: the one add that returned 0x7FFF does it, so every crossing is moved once
  * and no counter passes 0x8000 + the adds in flight (< 0xFFFF): no field wraps or carries. */
-template <bool WIDE>
+/* PACK: the unranked records are K1's packed words, count << sbits | slot; the word written back
+ * is rank << cb | count with cb = 32 - rank_bits (the rank left-aligned: K5's sort key as it
+ * stands).  The merged records behind them stay plain ranks (their counts are in rec_cnt). */
+template <bool WIDE, bool PACK>
 __global__ __launch_bounds__(DFH_NT) void k_df_hist_lds(uint32_t* __restrict__ rec_slot, uint64_t nrec,
                                                         const uint32_t* __restrict__ nrec_extra,
                                                         const uint32_t* __restrict__ rank_of_slot,
@@ -772,7 +775,7 @@ __global__ __launch_bounds__(DFH_NT) void k_df_hist_lds(uint32_t* __restrict__ r
                                                         uint64_t slot_cap, uint64_t ranked_from,
                                                         uint32_t* __restrict__ status, uint64_t per,
                                                         uint32_t* __restrict__ part /* [grid][V/2 words] */,
-                                                        uint32_t* __restrict__ df) {
+                                                        uint32_t* __restrict__ df, uint32_t sbits, uint32_t cb) {
     extern __shared__ __attribute__((aligned(16))) uint32_t bins[]; /* V/2 words of two u16 counters */
     const uint32_t W = (V + 1) / 2;
     for (uint32_t k = threadIdx.x; k < W; k += DFH_NT) bins[k] = 0;
@@ -817,11 +820,20 @@ __global__ __launch_bounds__(DFH_NT) void k_df_hist_lds(uint32_t* __restrict__ r
     };
     for (uint32_t j = threadIdx.x; j < nr; j += (uint32_t)DFH_B * DFH_NT) {
         uint32_t sl[DFH_B], r[DFH_B], g[DFH_B];
+        uint32_t pc[PACK ? DFH_B : 1];   /* PACK: the records' counts */
         const uint32_t ofs = j * 4u;
 #pragma unroll
         for (int q = 0; q < DFH_B; ++q) {
             const uint32_t v = __builtin_amdgcn_raw_buffer_load_b32(rs, ofs + (uint32_t)q * DFH_NT * 4u, 0, 2 /* nt */);
             sl[q] = j + (uint32_t)q * DFH_NT < nr ? v : 0xFFFFFFFFu;
+            if constexpr (PACK) {
+                if (j + (uint32_t)q * DFH_NT < rk) {   /* a packed record (the merged ones hold ranks) */
+                    pc[q] = v >> sbits;
+                    sl[q] = v & ((1u << sbits) - 1u);
+                } else {
+                    pc[q] = 0u;
+                }
+            }
         }
         store_prev();
         /* classify without branches around loads: every lane reads its cache entry; a
@@ -862,7 +874,8 @@ __global__ __launch_bounds__(DFH_NT) void k_df_hist_lds(uint32_t* __restrict__ r
 #pragma unroll
         for (int q = 0; q < DFH_B; ++q) {
             /* records carry term ranks from here on: K5 reads them without a gather */
-            rp[q] = r[q];
+            if constexpr (PACK) rp[q] = (r[q] << cb) | pc[q];
+            else rp[q] = r[q];
             pvalid |= sl[q] != 0xFFFFFFFFu && j + (uint32_t)q * DFH_NT < rk ? 1u << q : 0u;
             if (sl[q] == 0xFFFFFFFFu) continue;
             const uint32_t sh = 16 * (r[q] & 1);
@@ -1075,7 +1088,11 @@ size_t df_hist_scratch(uint64_t nrec_max, uint32_t V) {
 
 int launch_df_hist(uint32_t* rec_slot, uint64_t nrec, const uint32_t* nrec_extra, uint64_t nrec_max,
                    const uint32_t* rank_of_slot, const uint16_t* rank16, uint32_t V, uint64_t slot_cap,
-                   uint32_t* status, uint32_t* df, Arena& ar, hipStream_t s, bool accumulate) {
+                   uint32_t* status, uint32_t* df, Arena& ar, hipStream_t s, bool accumulate, uint32_t pack_sbits) {
+    /* packed records [0, nrec): only the LDS histogram has a packed instance, and the ranks
+     * must fit the field the slots leave (df_keeps_packed: the caller unpacks otherwise) */
+    if (pack_sbits && !df_keeps_packed(V, pack_sbits)) return -1;
+    const uint32_t pack_cb = 32u - k5_rank_bits(V);
     /* records [0, nrec) hold vocabulary slots (K1), the merged ones after them term ranks */
     const uint64_t ranked_from = nrec;
     if (V == 0) return 0;
@@ -1092,12 +1109,21 @@ int launch_df_hist(uint32_t* rec_slot, uint64_t nrec, const uint32_t* nrec_extra
         if (!part) return -2;
         if (!accumulate && hipMemsetAsync(df, 0, (size_t)V * 4, s) != hipSuccess) return -1;
         const size_t lds = (size_t)((W + 1) & ~1u) * 4 + (size_t)DFH_CK * 8;
-        if (per > DFH_RECS)
-            k_df_hist_lds<true><<<nparts, DFH_NT, lds, s>>>(rec_slot, nrec, nrec_extra, rank_of_slot, rank16, V,
-                                                            slot_cap, ranked_from, status, per, part, df);
+        if (pack_sbits) {
+            if (per > DFH_RECS)
+                k_df_hist_lds<true, true><<<nparts, DFH_NT, lds, s>>>(rec_slot, nrec, nrec_extra, rank_of_slot, rank16, V,
+                                                                      slot_cap, ranked_from, status, per, part, df,
+                                                                      pack_sbits, pack_cb);
+            else
+                k_df_hist_lds<false, true><<<nparts, DFH_NT, lds, s>>>(rec_slot, nrec, nrec_extra, rank_of_slot, rank16,
+                                                                       V, slot_cap, ranked_from, status, per, part, df,
+                                                                       pack_sbits, pack_cb);
+        } else if (per > DFH_RECS)
+            k_df_hist_lds<true, false><<<nparts, DFH_NT, lds, s>>>(rec_slot, nrec, nrec_extra, rank_of_slot, rank16, V,
+                                                                   slot_cap, ranked_from, status, per, part, df, 0u, 0u);
         else
-            k_df_hist_lds<false><<<nparts, DFH_NT, lds, s>>>(rec_slot, nrec, nrec_extra, rank_of_slot, rank16, V,
-                                                             slot_cap, ranked_from, status, per, part, df);
+            k_df_hist_lds<false, false><<<nparts, DFH_NT, lds, s>>>(rec_slot, nrec, nrec_extra, rank_of_slot, rank16, V,
+                                                                    slot_cap, ranked_from, status, per, part, df, 0u, 0u);
         k_df_colsum<<<dim3(grid_for(V), (nparts + DFC_G - 1) / DFC_G), NT, 0, s>>>(part, nparts, V, df);
         ar.release(m);
         return ok();
@@ -1127,6 +1153,32 @@ int launch_df_hist(uint32_t* rec_slot, uint64_t nrec, const uint32_t* nrec_extra
     if (!accumulate && hipMemsetAsync(df, 0, (size_t)V * 4, s) != hipSuccess) return -1;
     k_df_hist_atomic<<<4096, NT, 0, s>>>(rec_slot, nrec, nrec_extra, rank_of_slot, slot_cap, ranked_from, V, status,
                                          df);
+    return ok();
+}
+
+/* K1's packed records back into two words, four records per thread (runs that do not keep
+ * them packed through DF: df_keeps_packed) */
+__global__ void k_rec_unpack(uint32_t* __restrict__ rec_slot, uint32_t* __restrict__ rec_cnt, uint64_t n, uint32_t sbits) {
+    const uint64_t i0 = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) * 4ull;
+    const uint32_t smask = (1u << sbits) - 1u;
+    if (i0 + 4 <= n && (((uintptr_t)rec_slot | (uintptr_t)rec_cnt) & 15u) == 0) {
+        const uint4 w = *reinterpret_cast<const uint4*>(rec_slot + i0);
+        *reinterpret_cast<uint4*>(rec_slot + i0) = make_uint4(w.x & smask, w.y & smask, w.z & smask, w.w & smask);
+        *reinterpret_cast<uint4*>(rec_cnt + i0) = make_uint4(w.x >> sbits, w.y >> sbits, w.z >> sbits, w.w >> sbits);
+        return;
+    }
+    for (uint64_t i = i0; i < n && i < i0 + 4; ++i) {
+        const uint32_t w = rec_slot[i];
+        rec_slot[i] = w & smask;
+        rec_cnt[i] = w >> sbits;
+    }
+}
+int launch_rec_unpack(uint32_t* rec_slot, uint32_t* rec_cnt, uint64_t n, uint32_t sbits, hipStream_t s) {
+    if (!n) return 0;
+    if (sbits == 0 || sbits >= 32) return -1;
+    const uint64_t nthreads = (n + 3) / 4, blocks = (nthreads + NT - 1) / NT;
+    if (blocks > 0x7FFFFFFFull) return -1;
+    k_rec_unpack<<<(unsigned)blocks, NT, 0, s>>>(rec_slot, rec_cnt, n, sbits);
     return ok();
 }
 
@@ -1275,13 +1327,18 @@ __device__ __forceinline__ bool k5_by_wave(const K5Args& a, uint32_t n, bool pre
 /* (the fields it uses are passed as values: a reference to the kernel's argument struct
  * would put the struct on the stack, and every field the caller reads would become a
  * scratch load — one in-order vmcnt wait behind its prefetch loads) */
-__device__ __noinline__ void k5_radix(uint32_t rank_bits, const uint32_t* rec_cnt, const double* idf_rank,
+/* PACK: the keys are the packed records themselves, rank << lowb | count (lowb = K5Args.pack_cb):
+ * the passes run over the rank's bits [lowb, 32) and the emission splits the word (rec_cnt
+ * unused); otherwise lowb = K5_IDX_BITS. */
+template <bool PACK>
+__device__ __noinline__ void k5_radix(uint32_t rank_bits, uint32_t lowb, const uint32_t* rec_cnt, const double* idf_rank,
                                       uint32_t* out_term, uint32_t* out_cnt, double* out_score, uint32_t* buf0,
                                       uint32_t* buf1, uint32_t* h, uint32_t n, uint64_t rb, uint64_t ob, double ds) {
     const uint32_t lane = threadIdx.x & 63;
     const uint64_t below = (1ull << lane) - 1ull;
+    if constexpr (!PACK) lowb = K5_IDX_BITS;   /* a constant for the compiler */
     uint32_t cur = 0;
-    for (uint32_t sh = K5_IDX_BITS; sh < K5_IDX_BITS + rank_bits; sh += 8) {
+    for (uint32_t sh = lowb; sh < lowb + rank_bits; sh += 8) {
         const uint32_t* src = cur ? buf1 : buf0;
         uint32_t* dst = cur ? buf0 : buf1;
         h[4 * lane] = 0; h[4 * lane + 1] = 0; h[4 * lane + 2] = 0; h[4 * lane + 3] = 0;
@@ -1335,14 +1392,15 @@ __device__ __noinline__ void k5_radix(uint32_t rank_bits, const uint32_t* rec_cn
         }
 #pragma unroll
         for (int q = 0; q < K5_BATCH; ++q) {
-            cnt[q] = rec_cnt[rb + (key[q] & ((1u << K5_IDX_BITS) - 1u))];
-            idf[q] = G(idf_rank)[key[q] >> K5_IDX_BITS];
+            if constexpr (PACK) cnt[q] = key[q] & ((1u << lowb) - 1u);
+            else cnt[q] = rec_cnt[rb + (key[q] & ((1u << K5_IDX_BITS) - 1u))];
+            idf[q] = G(idf_rank)[key[q] >> lowb];
         }
 #pragma unroll
         for (int q = 0; q < K5_BATCH; ++q) {
             const uint32_t j = j0 + 64 * q + lane;
             if (j < n) {
-                sto(&out_term[ob + j], (uint32_t)(key[q] >> K5_IDX_BITS));
+                sto(&out_term[ob + j], (uint32_t)(key[q] >> lowb));
                 sto(&out_cnt[ob + j], (uint32_t)(cnt[q]));
                 sto(&out_score[ob + j], (double)(((double)cnt[q] / ds) * idf[q])); /* TFIDF.c:202,243-244 */
             }
@@ -1361,6 +1419,29 @@ __device__ __noinline__ void k5_radix(uint32_t rank_bits, const uint32_t* rec_cn
  *   presorted    merged runs (finalize's partial merge) are emitted as they are. */
 constexpr int K5_PF = 8;                 /* records prefetched per lane: documents up to 512 pairs */
 constexpr int K5_RQ = K5_WAVE / 64;      /* rank registers per lane: documents up to K5_WAVE pairs */
+/* packed records (K5Args.rec_pack) are one word: the registers the counts' prefetch held take
+ * K5_PF_PACK rows of records instead, all K5_RQ of them by default, so that no document of the
+ * wave kernel loads records after its prefetch */
+#ifndef K5_PF_PACK
+#define K5_PF_PACK K5_RQ
+#endif
+static_assert(K5_PF_PACK >= 1 && K5_PF_PACK <= K5_RQ, "prefetched rows of a packed document");
+template <int PF>
+__device__ __forceinline__ void k5_prefetch_packed(const K5Args& a, const uint4& m, uint32_t lane, uint32_t (&s)[PF]) {
+    const uint32_t n = m.z & 0x3FFFFFFFu;
+    const uint64_t rb = ((uint64_t)m.y << 32) | m.x;
+    const bool ok = n != 0u && n <= K5_WAVE && rb + n <= a.rec_total;
+#pragma unroll
+    for (int q = 0; q < PF; ++q) {
+        const uint32_t j = 64u * q + lane;
+        s[q] = (ok && j < n) ? a.rec_slot[rb + j] : 0u;
+    }
+}
+/* a packed record's rank, checked as k5_rank checks a plain one (a bad record becomes rank 0's) */
+__device__ __forceinline__ uint32_t k5_word(const K5Args& a, uint32_t w) {
+    if ((w >> a.pack_cb) >= a.nterms) { atomicOr(a.status, ST_BOUNDS); w &= (1u << a.pack_cb) - 1u; }
+    return w;
+}
 __device__ __forceinline__ void k5_prefetch(const K5Args& a, const uint4& m, uint32_t lane, uint32_t (&s)[K5_PF],
                                             uint32_t (&c)[K5_PF]) {
     const uint32_t n = m.z & 0x3FFFFFFFu;
@@ -1383,9 +1464,15 @@ __device__ __forceinline__ uint32_t lane_id_fresh() {
 
 /* WIDE: the instance launched when ranks exceed 32 - K5_IDX_BITS bits (its extra path
  * costs registers the common instance must not pay: c2 score 0.88 -> 1.16 ms with it) */
-template <bool WIDE, bool BYDF>
+/* PACK (K5Args.rec_pack): a record is one word, rank << pack_cb | count, and its own sort key —
+ * ranks are distinct within a document, so ordering the words orders the ranks and the count
+ * rides along: no counts in LDS, no (rank, index) keys, no count read at the emission.  In that
+ * instance r[] holds the words of an unsorted document and the ranks of a presorted one. */
+template <bool WIDE, bool BYDF, bool PACK>
 __global__ __launch_bounds__(NT, WIDE ? K5_WPS_WIDE : K5_WPS) void k_score_wave(K5Args a) {
     static_assert(WIDE || !BYDF, "idf by df only with wide ranks (V > 2^21; k5_radix reads idf by rank)");
+    static_assert(!(WIDE && PACK), "a packed word needs no index bits: no wide form");
+    constexpr int PF = PACK ? K5_PF_PACK : K5_PF;   /* rows of records prefetched */
     __shared__ __attribute__((aligned(16))) uint32_t kb[NT / 64][2][K5_WAVE];
     __shared__ uint32_t hist[NT / 64][K5_NB];
     const uint32_t w = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -1409,8 +1496,10 @@ __global__ __launch_bounds__(NT, WIDE ? K5_WPS_WIDE : K5_WPS) void k_score_wave(
     uint4 m_cur = li < lcount ? gload(a.meta + (i_cur)) : make_uint4(0, 0, 0, 0);
     uint4 m_nxt = li + stride < lcount ? gload(a.meta + (i_nxt)) : make_uint4(0, 0, 0, 0);
     uint64_t ob_cur = li < lcount ? G(a.out_off)[i_cur] : 0ull;
-    uint32_t s_cur[K5_PF], c_cur[K5_PF];
-    k5_prefetch(a, m_cur, lane, s_cur, c_cur);
+    uint32_t s_cur[PF], c_cur[PACK ? 1 : K5_PF];
+    if constexpr (PACK) k5_prefetch_packed<PF>(a, m_cur, lane, s_cur);
+    else k5_prefetch(a, m_cur, lane, s_cur, c_cur);
+    const uint32_t pcb = PACK ? a.pack_cb : 0u, pcm = (1u << pcb) - 1u;   /* a packed word's count field */
     for (; li < lcount; li += stride) {
         /* the lane index recomputed per document (an asm the compiler cannot hoist): held
          * across the loop it and the LDS addresses derived from it were spilled, and each
@@ -1428,27 +1517,32 @@ __global__ __launch_bounds__(NT, WIDE ? K5_WPS_WIDE : K5_WPS) void k_score_wave(
          * waits for the ranks leave the prefetch loads in flight */
         uint32_t r[K5_RQ];
 #pragma unroll
-        for (int q = 0; q < K5_PF; ++q) {
+        for (int q = 0; q < PF; ++q) {
             const uint32_t j = 64u * q + lane;
-            r[q] = (small_doc && j < n) ? k5_rank(a, s_cur[q]) : 0xFFFFFFFFu;
-            if (small_doc && j < n) buf0[j] = c_cur[q]; /* counts by record index */
+            if constexpr (PACK) {
+                r[q] = (small_doc && j < n) ? (presorted ? k5_rank(a, s_cur[q]) : k5_word(a, s_cur[q])) : 0xFFFFFFFFu;
+            } else {
+                r[q] = (small_doc && j < n) ? k5_rank(a, s_cur[q]) : 0xFFFFFFFFu;
+                if (small_doc && j < n) buf0[j] = c_cur[q]; /* counts by record index */
+            }
         }
-        if (small_doc && n > 64u * K5_PF) { /* beyond the prefetch: loaded here */
-            uint32_t sx[K5_RQ - K5_PF];
+        if (PF < K5_RQ && small_doc && n > 64u * PF) { /* beyond the prefetch: loaded here */
+            uint32_t sx[PF < K5_RQ ? K5_RQ - PF : 1];
 #pragma unroll
-            for (int q = K5_PF; q < K5_RQ; ++q) {
+            for (int q = PF; q < K5_RQ; ++q) {
                 const uint32_t j = 64u * q + lane;
-                sx[q - K5_PF] = j < n ? a.rec_slot[rb + j] : 0u;
-                if (j < n) buf0[j] = a.rec_cnt[rb + j];
+                sx[q - PF] = j < n ? a.rec_slot[rb + j] : 0u;
+                if constexpr (!PACK) if (j < n) buf0[j] = a.rec_cnt[rb + j];
             }
 #pragma unroll
-            for (int q = K5_PF; q < K5_RQ; ++q) {
+            for (int q = PF; q < K5_RQ; ++q) {
                 const uint32_t j = 64u * q + lane;
-                r[q] = j < n ? k5_rank(a, sx[q - K5_PF]) : 0xFFFFFFFFu;
+                if constexpr (PACK) r[q] = j < n ? (presorted ? k5_rank(a, sx[q - PF]) : k5_word(a, sx[q - PF])) : 0xFFFFFFFFu;
+                else r[q] = j < n ? k5_rank(a, sx[q - PF]) : 0xFFFFFFFFu;
             }
         } else {
 #pragma unroll
-            for (int q = K5_PF; q < K5_RQ; ++q) r[q] = 0xFFFFFFFFu;
+            for (int q = PF; q < K5_RQ; ++q) r[q] = 0xFFFFFFFFu;
         }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
@@ -1459,7 +1553,8 @@ __global__ __launch_bounds__(NT, WIDE ? K5_WPS_WIDE : K5_WPS) void k_score_wave(
             ob_cur = inx < lcount ? G(a.out_off)[i_cur] : 0ull;
             i_nxt = inx + stride < lcount ? pos_of(inx + stride) : 0u;
             m_nxt = inx + stride < lcount ? gload(a.meta + (i_nxt)) : make_uint4(0, 0, 0, 0);
-            k5_prefetch(a, m_cur, lane, s_cur, c_cur);
+            if constexpr (PACK) k5_prefetch_packed<PF>(a, m_cur, lane, s_cur);
+            else k5_prefetch(a, m_cur, lane, s_cur, c_cur);
         }
         if (n == 0) continue;
         if (!k5_by_wave(a, n, presorted)) { /* k_score_large's document */
@@ -1471,7 +1566,11 @@ __global__ __launch_bounds__(NT, WIDE ? K5_WPS_WIDE : K5_WPS) void k_score_wave(
 #pragma unroll
             for (int q = 0; q < K5_RQ; ++q) {
                 const uint32_t j = 64u * q + lane;
-                if (j < n) k5_emit<BYDF>(a, ob + j, ds, r[q], buf0[j]);
+                if constexpr (PACK) {   /* a merged document's counts: the two-word region */
+                    if (j < n) k5_emit<BYDF>(a, ob + j, ds, r[q], a.rec_cnt[rb + j]);
+                } else {
+                    if (j < n) k5_emit<BYDF>(a, ob + j, ds, r[q], buf0[j]);
+                }
             }
             continue;
         }
@@ -1506,14 +1605,14 @@ __global__ __launch_bounds__(NT, WIDE ? K5_WPS_WIDE : K5_WPS) void k_score_wave(
             }
             double idf[QC];
 #pragma unroll
-            for (int q = 0; q < QC; ++q) idf[q] = (64u * q + lane < n) ? k5_idf<BYDF>(a, r[q]) : 0.0;
+            for (int q = 0; q < QC; ++q) idf[q] = (64u * q + lane < n) ? k5_idf<BYDF>(a, r[q] >> pcb) : 0.0;
 #pragma unroll
             for (int q = 0; q < QC; ++q) {
                 const uint32_t j = 64u * q + lane;
                 if (j < n) {
                     const uint64_t o = ob + pos[q];
-                    const uint32_t cnt = buf0[j];
-                    sto(&a.out_term[o], (uint32_t)(r[q]));
+                    const uint32_t cnt = PACK ? (r[q] & pcm) : buf0[j];
+                    sto(&a.out_term[o], (uint32_t)(r[q] >> pcb));
                     sto(&a.out_cnt[o], (uint32_t)(cnt));
                     sto(&a.out_score[o], (double)(((double)cnt / ds) * idf[q]));   /* TFIDF.c:202,243-244 */
                 }
@@ -1523,7 +1622,7 @@ __global__ __launch_bounds__(NT, WIDE ? K5_WPS_WIDE : K5_WPS) void k_score_wave(
             continue;
         }
         if (n <= K5_SMALL) {
-            uint32_t key = r[0], val = lane < n ? buf0[lane] : 0u;
+            uint32_t key = r[0], val = (!PACK && lane < n) ? buf0[lane] : 0u;
 #pragma unroll
             for (uint32_t k = 2; k <= 64; k <<= 1) {
 #pragma unroll
@@ -1533,13 +1632,14 @@ __global__ __launch_bounds__(NT, WIDE ? K5_WPS_WIDE : K5_WPS) void k_score_wave(
                     if (take_min ? (pk < key) : (pk > key)) { key = pk; val = pv; }
                 }
             }
-            if (lane < n) k5_emit<BYDF>(a, ob + lane, ds, key, val);
+            if (lane < n) k5_emit<BYDF>(a, ob + lane, ds, key >> pcb, PACK ? (key & pcm) : val);
             continue;
         }
         /* ---- bucket sort: ranks are distinct within a document, so an element's position
          * is its bucket's start plus the number of smaller keys in its bucket.  Buckets by
          * the rank's top K5_NB_BITS bits hold ~n/512 keys each. ---- */
-        const uint32_t hsh = a.rank_bits > K5_NB_BITS ? a.rank_bits - K5_NB_BITS : 0u;
+        /* PACK: the word's top K5_NB_BITS bits (the rank is left-aligned) */
+        const uint32_t hsh = PACK ? 32u - K5_NB_BITS : a.rank_bits > K5_NB_BITS ? a.rank_bits - K5_NB_BITS : 0u;
 #pragma unroll
         for (uint32_t q = 0; q < K5_NB / 64; ++q) h[q * 64 + lane] = 0;
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -1619,19 +1719,19 @@ __global__ __launch_bounds__(NT, WIDE ? K5_WPS_WIDE : K5_WPS) void k_score_wave(
 #pragma unroll
             for (int q = 0; q < K5_RQ; ++q) {
                 const uint32_t j = 64u * q + lane;
-                if (j < n) buf0[j] = (r[q] << K5_IDX_BITS) | j;
+                if (j < n) buf0[j] = PACK ? r[q] : (r[q] << K5_IDX_BITS) | j;
             }
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
             if constexpr (!WIDE)   /* the wide instance runs only for wide ranks: handed off above */
-                k5_radix(a.rank_bits, a.rec_cnt, a.idf_rank, a.out_term, a.out_cnt, a.out_score, buf0, buf1, h, n,
-                         rb, ob, ds);
+                k5_radix<PACK>(a.rank_bits, PACK ? pcb : K5_IDX_BITS, a.rec_cnt, a.idf_rank, a.out_term, a.out_cnt,
+                               a.out_score, buf0, buf1, h, n, rb, ob, ds);
             continue;
         }
 #pragma unroll
         for (int q = 0; q < K5_RQ; ++q) {
             const uint32_t j = 64u * q + lane;
-            if (j < n) buf1[atomicAdd(&h[r[q] >> hsh], 1u)] = (r[q] << K5_IDX_BITS) | j;
+            if (j < n) buf1[atomicAdd(&h[r[q] >> hsh], 1u)] = PACK ? r[q] : (r[q] << K5_IDX_BITS) | j;
         }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
@@ -1646,7 +1746,7 @@ __global__ __launch_bounds__(NT, WIDE ? K5_WPS_WIDE : K5_WPS) void k_score_wave(
             const uint32_t j = 64u * q + lane;
             pp[q] = 0u;
             if (j < n) {
-                const uint32_t k = (r[q] << K5_IDX_BITS) | j, d = r[q] >> hsh;
+                const uint32_t k = PACK ? r[q] : (r[q] << K5_IDX_BITS) | j, d = r[q] >> hsh;
                 const uint32_t gs = d ? h[d - 1] : 0u, ge = h[d];
                 uint32_t less = 0;
                 for (uint32_t f = gs; f < ge; ++f) less += buf1[f] < k ? 1u : 0u;
@@ -1657,7 +1757,7 @@ __global__ __launch_bounds__(NT, WIDE ? K5_WPS_WIDE : K5_WPS) void k_score_wave(
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 #pragma unroll
         for (int q = 0; q < K5_RQ; ++q)
-            if (64u * q + lane < n) buf1[pp[q]] = (r[q] << K5_IDX_BITS) | (64u * q + lane);
+            if (64u * q + lane < n) buf1[pp[q]] = PACK ? r[q] : (r[q] << K5_IDX_BITS) | (64u * q + lane);
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
         /* Emission: every idf of a batch is gathered before any of its stores, and a batch
@@ -1673,14 +1773,15 @@ __global__ __launch_bounds__(NT, WIDE ? K5_WPS_WIDE : K5_WPS) void k_score_wave(
 #pragma unroll
             for (int q = 0; q < EB; ++q) {
                 const uint32_t j = j0 + 64 * q + lane;
-                idf[q] = k5_idf<BYDF>(a, (j < n ? buf1[j] : 0u) >> K5_IDX_BITS);
+                idf[q] = k5_idf<BYDF>(a, (j < n ? buf1[j] : 0u) >> (PACK ? pcb : K5_IDX_BITS));
             }
 #pragma unroll
             for (int q = 0; q < EB; ++q) {
                 const uint32_t j = j0 + 64 * q + lane;
                 if (j < n) {
-                    const uint32_t key = buf1[j], cnt = buf0[key & ((1u << K5_IDX_BITS) - 1u)];
-                    sto(&a.out_term[ob + j], (uint32_t)(key >> K5_IDX_BITS));
+                    const uint32_t key = buf1[j];
+                    const uint32_t cnt = PACK ? (key & pcm) : buf0[key & ((1u << K5_IDX_BITS) - 1u)];
+                    sto(&a.out_term[ob + j], (uint32_t)(key >> (PACK ? pcb : K5_IDX_BITS)));
                     sto(&a.out_cnt[ob + j], (uint32_t)(cnt));
                     sto(&a.out_score[ob + j], (double)(((double)cnt / ds) * idf[q])); /* TFIDF.c:202,243-244 */
                 }
@@ -1697,7 +1798,9 @@ __global__ __launch_bounds__(NT, WIDE ? K5_WPS_WIDE : K5_WPS) void k_score_wave(
 /* Two instances share the list: MAXN = K5_MAX / 2 with 1024 buckets (38 KB of LDS: four
  * workgroups per CU) takes presorted documents and those of <= K5_MAX / 2 pairs; MAXN =
  * K5_MAX (72 KB: two per CU) the rest.  The bucket counters alias the radix scratch. */
-template <uint32_t MAXN, uint32_t NBB, bool BYDF>
+/* PACK (K5Args.rec_pack): an unsorted document's records are single loads, split into rank and
+ * count as they enter LDS; presorted documents read the two-word region as ever. */
+template <uint32_t MAXN, uint32_t NBB, bool BYDF, bool PACK>
 __global__ __launch_bounds__(NT) void k_score_large(K5Args a) {
     constexpr uint32_t NB = 1u << NBB;
     __shared__ uint32_t kbuf[2][MAXN];
@@ -1775,14 +1878,19 @@ __global__ __launch_bounds__(NT) void k_score_large(K5Args a) {
         for (int e = 0; e < K5L_EB; ++e) {
             const uint32_t j = j0 + NT * e + tid;
             sl[e] = j < n ? a.rec_slot[rb + j] : 0u;
-            cn[e] = j < n ? a.rec_cnt[rb + j] : 0u;
+            if constexpr (!PACK) cn[e] = j < n ? a.rec_cnt[rb + j] : 0u;
         }
 #pragma unroll
         for (int e = 0; e < K5L_EB; ++e) {
             const uint32_t j = j0 + NT * e + tid;
             if (j < n) {
-                kbuf[0][j] = k5_rank(a, sl[e]);
-                vbuf[0][j] = cn[e];
+                if constexpr (PACK) {
+                    kbuf[0][j] = k5_rank(a, sl[e] >> a.pack_cb);
+                    vbuf[0][j] = sl[e] & ((1u << a.pack_cb) - 1u);
+                } else {
+                    kbuf[0][j] = k5_rank(a, sl[e]);
+                    vbuf[0][j] = cn[e];
+                }
             }
         }
     }
@@ -1979,7 +2087,9 @@ __device__ __forceinline__ void k5s_batch(const K5Args& a, const uint32_t* L, ui
         ob = G(a.out_off)[i];
     }
 }
-template <bool BYDF>
+/* PACK (K5Args.rec_pack): an unsorted document's records are single loads; the word is split
+ * into rank and count where its idf gather is issued. */
+template <bool BYDF, bool PACK>
 __global__ __launch_bounds__(256, K5S_OCC) void k_score_small(K5Args a) {
     __shared__ __attribute__((aligned(16))) uint32_t kb[K5S_WG][K5_SMALL_DOC + 4];
     __shared__ uint4 bm[K5S_WG][64];      /* the current batch's metadata (the next one: registers) */
@@ -2039,13 +2149,17 @@ __global__ __launch_bounds__(256, K5S_OCC) void k_score_small(K5Args a) {
             const uint32_t j = 64u * q + lane;
             const bool v = j < d.n;
             r[q] = v ? a.rec_slot[d.rb + j] : 0xFFFFFFFFu;
-            c[q] = v ? a.rec_cnt[d.rb + j] : 0u;
+            c[q] = (v && (!PACK || d.presorted)) ? a.rec_cnt[d.rb + j] : 0u;
         }
     };
-    auto load_idf = [&](const K5SDoc& d, uint32_t (&r)[Q], double (&f)[Q]) {
+    auto load_idf = [&](const K5SDoc& d, uint32_t (&r)[Q], uint32_t (&c)[Q], double (&f)[Q]) {
 #pragma unroll
         for (int q = 0; q < Q; ++q) {
             const bool v = 64u * q + lane < d.n;
+            if (PACK && v && !d.presorted) {
+                c[q] = r[q] & ((1u << a.pack_cb) - 1u);
+                r[q] >>= a.pack_cb;
+            }
             if (v) r[q] = k5_rank(a, r[q]);
             f[q] = v ? k5_idf<BYDF>(a, r[q]) : 0.0;
         }
@@ -2055,7 +2169,7 @@ __global__ __launch_bounds__(256, K5S_OCC) void k_score_small(K5Args a) {
     double f0[Q];
     load_rec(D0, r0, c0);
     load_rec(D1, r1, c1);
-    load_idf(D0, r0, f0);
+    load_idf(D0, r0, c0, f0);
     for (uint32_t k = 0; k < cnt; ++k) {
         if (k && (k & 63u) == 0u) {   /* doc k starts batch curb + 1 */
             bm[w][lane] = mnxt;
@@ -2069,7 +2183,7 @@ __global__ __launch_bounds__(256, K5S_OCC) void k_score_small(K5Args a) {
         uint32_t r2[Q], c2[Q];
         double f1[Q];
         load_rec(D2, r2, c2);
-        load_idf(D1, r1, f1);
+        load_idf(D1, r1, c1, f1);
         /* document k: positions, then the output */
         const uint32_t n = D0.n;
         uint32_t pos[Q];
@@ -2157,9 +2271,10 @@ __global__ __launch_bounds__(256) void k_emit_split(K5Args a) {
     }
 }
 static void launch_score_wave(const K5Args& a, bool wide, uint32_t wg, hipStream_t s) {
-    if (!wide) k_score_wave<false, false><<<wg, NT, 0, s>>>(a);
-    else if (a.idf_by_df) k_score_wave<true, true><<<wg, NT, 0, s>>>(a);
-    else k_score_wave<true, false><<<wg, NT, 0, s>>>(a);
+    if (a.rec_pack) k_score_wave<false, false, true><<<wg, NT, 0, s>>>(a);   /* never wide (launch_score_order) */
+    else if (!wide) k_score_wave<false, false, false><<<wg, NT, 0, s>>>(a);
+    else if (a.idf_by_df) k_score_wave<true, true, false><<<wg, NT, 0, s>>>(a);
+    else k_score_wave<true, false, false><<<wg, NT, 0, s>>>(a);
 }
 static void launch_emit_split(const K5Args& a, int ncu, hipStream_t s) {
     if (a.idf_by_df) k_emit_split<true><<<(unsigned)ncu * 4u, 256, 0, s>>>(a);
@@ -2167,12 +2282,15 @@ static void launch_emit_split(const K5Args& a, int ncu, hipStream_t s) {
 }
 static void launch_score_large(const K5Args& a, uint32_t grid, hipStream_t s) {
     static_assert(K5_MAX % 2 == 0 && K5_MAX / 2 >= 1024, "k_score_large instances");
-    if (a.idf_by_df) {
-        k_score_large<(uint32_t)K5_MAX / 2, 10, true><<<grid, NT, 0, s>>>(a);
-        k_score_large<(uint32_t)K5_MAX, 11, true><<<grid, NT, 0, s>>>(a);
+    if (a.rec_pack) {
+        k_score_large<(uint32_t)K5_MAX / 2, 10, false, true><<<grid, NT, 0, s>>>(a);
+        k_score_large<(uint32_t)K5_MAX, 11, false, true><<<grid, NT, 0, s>>>(a);
+    } else if (a.idf_by_df) {
+        k_score_large<(uint32_t)K5_MAX / 2, 10, true, false><<<grid, NT, 0, s>>>(a);
+        k_score_large<(uint32_t)K5_MAX, 11, true, false><<<grid, NT, 0, s>>>(a);
     } else {
-        k_score_large<(uint32_t)K5_MAX / 2, 10, false><<<grid, NT, 0, s>>>(a);
-        k_score_large<(uint32_t)K5_MAX, 11, false><<<grid, NT, 0, s>>>(a);
+        k_score_large<(uint32_t)K5_MAX / 2, 10, false, false><<<grid, NT, 0, s>>>(a);
+        k_score_large<(uint32_t)K5_MAX, 11, false, false><<<grid, NT, 0, s>>>(a);
     }
 }
 int launch_score_order(const K5Args& a, Arena& ar, hipStream_t s, hipStream_t s2, hipEvent_t ev_fork,
@@ -2202,7 +2320,10 @@ int launch_score_order(const K5Args& a, Arena& ar, hipStream_t s, hipStream_t s2
     }
     const int ncu = ncu_ctx ? (int)ncu_ctx : ncu_dev;
     const uint32_t wg_need = (a.ndocs + NT / 64 - 1) / (NT / 64);
-    const bool wide = a.rank_bits + K5_IDX_BITS > 32;
+    /* packed records are their own keys: no index bits beside the rank, so no wide form; the
+     * word's fields must add up, and its kernels read idf by rank */
+    if (a.rec_pack && (a.pack_cb == 0 || a.pack_cb + a.rank_bits != 32 || a.idf_by_df)) return -1;
+    const bool wide = !a.rec_pack && a.rank_bits + K5_IDX_BITS > 32;
     const uint32_t wg_cu = wide ? (uint32_t)K5_WPS_WIDE : 4u;   /* 40 KB LDS: 4 per CU; wide: its registers */
     const uint32_t wg = wg_need < (uint32_t)ncu * wg_cu ? wg_need : (uint32_t)ncu * wg_cu;
     const uint32_t grid = a.ndocs < 2048u ? a.ndocs : 2048u; /* persistent over the handed-off list */
@@ -2216,8 +2337,9 @@ int launch_score_order(const K5Args& a, Arena& ar, hipStream_t s, hipStream_t s2
     if (scan_excl_u32(a.cls_off, a.cls_off, 3ull * a.cls_nblk + 1, ar, s)) return -1;
     k_k5_scatter<<<a.cls_nblk, 256, 0, s>>>(a);
     if (a.idf_by_df && !wide) return -1;   /* the engine sets idf_by_df only with wide ranks */
-    if (a.idf_by_df) k_score_small<true><<<(unsigned)ncu * (unsigned)K5S_OCC, 256, 0, s>>>(a);
-    else k_score_small<false><<<(unsigned)ncu * (unsigned)K5S_OCC, 256, 0, s>>>(a);
+    if (a.rec_pack) k_score_small<false, true><<<(unsigned)ncu * (unsigned)K5S_OCC, 256, 0, s>>>(a);
+    else if (a.idf_by_df) k_score_small<true, false><<<(unsigned)ncu * (unsigned)K5S_OCC, 256, 0, s>>>(a);
+    else k_score_small<false, false><<<(unsigned)ncu * (unsigned)K5S_OCC, 256, 0, s>>>(a);
     /* k_score_large after the wave kernel on the same stream (beside it on the side stream,
      * round 5's A/B: c2 score 0.74 vs 0.76 ms but c4 3.18-3.29 vs 3.04-3.11 and c5 0.83 vs
      * 0.81) */

@@ -131,10 +131,13 @@ int launch_tokcount_vs(const CorpusDev& c, const uint64_t* chunk_start, const ui
                                         TFIDF_SL_MAXCAP lowers it), tokcount_vs beyond */
 /* K1 default (tokcount_sl.hip): one workgroup per chunk, straight-line rounds; the output
  * block is read from device memory (o_dev: a K1Out the engine copies there per run).
- * 16-byte aligned corpus base; -3 when the vocabulary exceeds K1_SL_MAX_CAP slots */
+ * 16-byte aligned corpus base; -3 when the vocabulary exceeds K1_SL_MAX_CAP slots.
+ * pack != 0 (tables up to K1_ST_MAX_CAP slots): a complete document's record leaves as one word
+ * in rec_slot, count << sbits | slot (sbits = log2 of the capacity), and rec_cnt is not written
+ * for it; a document with a count of 1 << (32 - sbits) or more leaves as partial records */
 int launch_tokcount_sl(const CorpusDev& c, const uint64_t* chunk_start, const uint32_t* chunk_doc, uint64_t c0,
                        uint64_t c1, const VocabDev& v, const K1Out* o_dev, hipStream_t s, uint32_t ncu = 0,
-                       uint32_t* grid = nullptr);
+                       uint32_t* grid = nullptr, uint32_t pack = 0);
 
 
 /* vocabulary finalisation */
@@ -197,9 +200,23 @@ int launch_dense_emit(const uint32_t* dense, uint32_t nb, uint32_t V, const uint
 
 /* DF.  accumulate: add into df instead of overwriting it (the split DF of a run with
  * partial records, whose main records are counted beside the merge stage) */
+/* bits of the largest term rank of V terms (K5Args.rank_bits) */
+static inline uint32_t k5_rank_bits(uint32_t V) { return V > 1 ? 32u - (uint32_t)__builtin_clz(V - 1) : 1u; }
+/* Packed records (K1's count << sbits | slot words, launch_tokcount_sl's pack) stay packed through
+ * DF when the LDS histogram takes V and a rank fits the field the slot had: the count field then
+ * keeps its 32 - sbits bits or more. */
+static inline bool df_keeps_packed(uint32_t V, uint32_t sbits) {
+    return V != 0 && V <= DFH_MAXV && sbits != 0 && sbits < 32 && k5_rank_bits(V) <= sbits;
+}
+/* pack_sbits != 0 (only where df_keeps_packed): records [0, nrec) are K1's packed words; each is
+ * rewritten as rank << (32 - k5_rank_bits(V)) | count, the merged records after them as ever */
 int launch_df_hist(uint32_t* rec_slot, uint64_t nrec, const uint32_t* nrec_extra, uint64_t nrec_max,
                    const uint32_t* rank_of_slot, const uint16_t* rank16, uint32_t V, uint64_t slot_cap,
-                   uint32_t* status, uint32_t* df, Arena& ar, hipStream_t s, bool accumulate = false);
+                   uint32_t* status, uint32_t* df, Arena& ar, hipStream_t s, bool accumulate = false,
+                   uint32_t pack_sbits = 0);
+/* K1's packed records [0, n) of rec_slot (count << sbits | slot) back into two words: the slot in
+ * rec_slot, the count in rec_cnt (runs whose DF pass or ranks do not take packed records) */
+int launch_rec_unpack(uint32_t* rec_slot, uint32_t* rec_cnt, uint64_t n, uint32_t sbits, hipStream_t s);
 /* device scratch launch_df_hist takes from its arena (an upper bound) */
 size_t df_hist_scratch(uint64_t nrec_max, uint32_t V);
 int launch_df_mark(const uint32_t* df, uint32_t V, uint32_t* present, hipStream_t s);
@@ -248,6 +265,11 @@ struct K5Args {
     uint32_t* out_term;          /* output order: term rank */
     uint32_t* out_cnt;           /*               wordCount */
     double* out_score;           /*               tf * idf */
+    uint32_t rec_pack;           /* nonzero: a document's records are single words in rec_slot,
+                                    rank << pack_cb | count (the packed DF pass wrote them), and rec_cnt
+                                    is not read for them; presorted (merged) documents keep rank and
+                                    count in rec_slot / rec_cnt.  0: two words throughout */
+    uint32_t pack_cb;            /* the packed word's count bits: 32 - rank_bits */
 };
 /* ncu sizes the persistent score kernels (k_score_small, the wave kernel, the chunk tasks): the
  * context's CU count, 0: the launcher asks the device */

@@ -1,7 +1,8 @@
 /*
  * knobs.h — the numeric range knobs tfidf_open reads from the environment: one table, one parse
  * function.  Plain C++ with no HIP dependency (tests/native/knobs_test.cpp builds it alone).
- * The string and flag knobs (TFIDF_K1, TFIDF_XCHG, TFIDF_XAGG, TFIDF_STAMPS, TFIDF_DF_SPLIT, the
+ * The string and flag knobs (TFIDF_K1, TFIDF_XCHG, TFIDF_XAGG, TFIDF_STAMPS, TFIDF_DF_SPLIT,
+ * TFIDF_REC_PACK, the
  * two TFIDF_TEST_*_RANK hooks) stay in tfidf_open.
  */
 #ifndef TFIDF_KNOBS_H

@@ -324,12 +324,19 @@ __device__ __forceinline__ uint32_t wave_agg_add_rtn(uint32_t* ctr, uint32_t idx
     return k;
 }
 
+/* Packed records (k_tokcount_sl's PACK instance): SL_PACK_STAGE 1 stages a record as its one
+ * word (one LDS write and read fewer per record, a compare and a select per entry more); 0
+ * stages key and count as ever and packs at the store. */
+#ifndef SL_PACK_STAGE
+#define SL_PACK_STAGE 0
+#endif
 /* The flush's second half: every entry has been placed in the staging area (the table's own
  * TK/TC words: records [0, nrec), partial records [nrec, nrec + npart), key and count), so the
  * group's records leave as ONE contiguous run from rb and its partial records as one from pb
  * — consecutive lanes store consecutive words (round 4 stored each entry at its document's
  * base + rank from the lane that held it: scattered partial lines, 0.33 ms of c2's K1 for
  * 0.5 GB, profiles/r05_k1_ablations_c2.txt).  Then the whole table is cleared. */
+template <bool PACK>
 __device__ __forceinline__ void sl_write_staged(SlShared& S, const K1Out* o, uint32_t gd0, uint32_t sb, uint32_t nrec,
                                                 uint32_t npart, unsigned long long rb, unsigned long long pb,
                                                 bool rec_ok, bool part_ok) {
@@ -341,11 +348,17 @@ __device__ __forceinline__ void sl_write_staged(SlShared& S, const K1Out* o, uin
     uint32_t* const part_cnt = o->part_cnt;
     const uint32_t smask = (1u << sb) - 1u;
     lds_barrier();
-    if (rec_ok && !SL_ABL_ST)
-        for (uint32_t i = (uint32_t)tid; i < nrec; i += NT) {
-            gmem(rec_slot)[rb + i] = S.TK[i] & smask;
-            gmem(rec_cnt)[rb + i] = S.TC[i];
+    if (rec_ok && !SL_ABL_ST) {
+        if constexpr (PACK) {   /* the record's one word, count << sb | slot: rec_cnt is not written */
+            for (uint32_t i = (uint32_t)tid; i < nrec; i += NT)
+                gmem(rec_slot)[rb + i] = SL_PACK_STAGE ? S.TK[i] : (S.TC[i] << sb) | (S.TK[i] & smask);
+        } else {
+            for (uint32_t i = (uint32_t)tid; i < nrec; i += NT) {
+                gmem(rec_slot)[rb + i] = S.TK[i] & smask;
+                gmem(rec_cnt)[rb + i] = S.TC[i];
+            }
         }
+    }
     if (part_ok && !SL_ABL_ST)
         for (uint32_t i = (uint32_t)tid; i < npart; i += NT) {
             const uint32_t k = S.TK[nrec + i];
@@ -359,10 +372,28 @@ __device__ __forceinline__ void sl_write_staged(SlShared& S, const K1Out* o, uin
     for (int j = tid; j < 2 * TB / 4; j += NT) t[j] = make_uint4(0, 0, 0, 0);   /* TK and TC are adjacent */
 }
 
+/* Packed records (pack != 0) hold count << sb | slot: a count of 1 << (32 - sb) or more has no
+ * room, so its document is marked in S.dpart before the flush decides the documents' states and
+ * leaves whole as partial records (full counts) through the merge.  The common flush pays an OR
+ * per entry and one wave-uniform test. */
+template <int N>
+__device__ __forceinline__ void sl_mark_wide(SlShared& S, const uint32_t (&ek)[N], const uint32_t (&ec)[N], uint32_t sb) {
+    const uint32_t lim = 1u << (32u - sb);
+    /* lim is a power of two: the OR of the counts reaches it exactly when one of them does */
+    uint32_t any = 0;
+#pragma unroll
+    for (int j = 0; j < N; ++j) any |= ec[j];
+    if (__ballot(any >= lim) == 0ull) return;
+#pragma unroll
+    for (int j = 0; j < N; ++j)
+        if (ek[j] && ec[j] >= lim) S.dpart[(ek[j] & 0x7FFFFFFFu) >> sb] = 1;
+}
+
 /* Emits the group's table entries as records (complete documents: the record stream;
  * documents crossing the chunk, over K5's in-LDS sort size or with overflow records: the
  * partial stream) — any number of documents: per-document counts by wave-aggregated LDS
  * adds, a block scan, every entry written at its document's base + its rank. */
+template <bool PACK>
 __device__ __forceinline__ void sl_flush(SlShared& S, const K1Out* o, uint32_t gd0, uint32_t ng, uint32_t sb) {
     const int tid = threadIdx.x;
     lds_barrier();
@@ -375,6 +406,7 @@ __device__ __forceinline__ void sl_flush(SlShared& S, const K1Out* o, uint32_t g
         ec[j] = S.TC[j * NT + tid];
         if (ek[j]) wave_agg_add(&S.f.dcnt[0], (ek[j] & 0x7FFFFFFFu) >> sb);
     }
+    if constexpr (PACK) sl_mark_wide(S, ek, ec, sb);
     lds_barrier();
     uint32_t packed = 0;
     if ((uint32_t)tid < ng) {
@@ -420,11 +452,15 @@ __device__ __forceinline__ void sl_flush(SlShared& S, const K1Out* o, uint32_t g
             const uint32_t k = wave_agg_add_rtn(&S.f.drun[0], rel);
             const uint32_t dof = S.f.doff[rel];
             const uint32_t loc = (S.f.dstate[rel] == 2 ? (dof & 0xFFFFu) : nrec + (dof >> 16)) + k;
-            S.TK[loc] = key;
-            S.TC[loc] = ec[j];
+            if (PACK && SL_PACK_STAGE && loc < nrec) {
+                S.TK[loc] = (ec[j] << sb) | (key & ((1u << sb) - 1u));
+            } else {
+                S.TK[loc] = key;
+                S.TC[loc] = ec[j];
+            }
         }
     }
-    sl_write_staged(S, o, gd0, sb, nrec, npart, rb, pb, rec_ok, part_ok);
+    sl_write_staged<PACK>(S, o, gd0, sb, nrec, npart, rb, pb, rec_ok, part_ok);
 }
 
 /* The flush of a group of at most FEW documents (most chunks hold one or two): per-thread
@@ -442,6 +478,7 @@ constexpr uint32_t FEW = 8;
 #define SLF_STAMP(k) do {} while (0)
 #define SLF_ARGS
 #endif
+template <bool PACK>
 __device__ __forceinline__ void sl_flush_few(SlShared& S, const K1Out* o, uint32_t gd0, uint32_t ng, uint32_t sb SLF_ARGS) {
     const int tid = threadIdx.x;
     const int lane = tid & 63, w = tid >> 6;
@@ -456,6 +493,7 @@ __device__ __forceinline__ void sl_flush_few(SlShared& S, const K1Out* o, uint32
         ec[j] = S.TC[j * NT + tid];
         c4 += (ek[j] >> 31) << (4u * ((ek[j] & 0x7FFFFFFFu) >> sb));
     }
+    if constexpr (PACK) sl_mark_wide(S, ek, ec, sb);   /* S.dpart is read after the barrier below */
     static_assert(EPT < 16 && FEW == 8, "4-bit per-document entry counts of eight documents");
     uint32_t pk[FEW / 2], inc[FEW / 2];
 #pragma unroll
@@ -534,6 +572,7 @@ __device__ __forceinline__ void sl_flush_few(SlShared& S, const K1Out* o, uint32
                                     rank[2] + (lb1.x | (lb1.y << 16)), rank[3] + (lb1.z | (lb1.w << 16)));
     }
     const uint16_t* const lr16 = reinterpret_cast<const uint16_t*>(&S.q.lrank[tid]);
+    const uint32_t nrec_st = S.fl_nrec;   /* staging indices below it are records */
     uint32_t run = 0;   /* 4-bit per-document counts of this thread's entries placed so far */
 #pragma unroll
     for (int j = 0; j < EPT; ++j) {
@@ -542,12 +581,16 @@ __device__ __forceinline__ void sl_flush_few(SlShared& S, const K1Out* o, uint32
             const uint32_t rel4 = 4u * ((key & 0x7FFFFFFFu) >> sb);
             const uint32_t loc = (uint32_t)lr16[rel4 >> 2] + ((run >> rel4) & 15u);
             run += 1u << rel4;
-            S.TK[loc] = key;
-            S.TC[loc] = ec[j];
+            if (PACK && SL_PACK_STAGE && loc < nrec_st) {
+                S.TK[loc] = (ec[j] << sb) | (key & ((1u << sb) - 1u));
+            } else {
+                S.TK[loc] = key;
+                S.TC[loc] = ec[j];
+            }
         }
     }
     const unsigned long long rb = S.rec_base, pb = S.part_base;
-    sl_write_staged(S, o, gd0, sb, S.fl_nrec, S.fl_npart, rb, pb, rb != ~0ull, pb != ~0ull);
+    sl_write_staged<PACK>(S, o, gd0, sb, S.fl_nrec, S.fl_npart, rb, pb, rb != ~0ull, pb != ~0ull);
 }
 
 /* The LDS count of one round's keys (key32 = 1 << 31 | document in group << sb | vocabulary slot;
@@ -778,7 +821,8 @@ struct Round {
 
 }  // namespace
 
-template <bool FAST>
+/* PACK: complete documents' records leave as one word, count << sb | slot (the flush) */
+template <bool FAST, bool PACK>
 __global__ __launch_bounds__(NT, WG_PER_CU * NT / 256) void k_tokcount_sl(CorpusDev c, const uint64_t* __restrict__ chunk_start,
                                                                const uint32_t* __restrict__ chunk_doc, uint64_t c0,
                                                                uint64_t c1, VocabDev v, const K1Out* __restrict__ o,
@@ -1122,11 +1166,11 @@ __global__ __launch_bounds__(NT, WG_PER_CU * NT / 256) void k_tokcount_sl(Corpus
         SL_STAMP(7);
 #endif
 #ifdef SL_STAMPS
-        if (ng <= FEW) sl_flush_few(S, o, gd0, ng, sb, st_acc, st_t);
+        if (ng <= FEW) sl_flush_few<PACK>(S, o, gd0, ng, sb, st_acc, st_t);
 #else
-        if (ng <= FEW) sl_flush_few(S, o, gd0, ng, sb);
+        if (ng <= FEW) sl_flush_few<PACK>(S, o, gd0, ng, sb);
 #endif
-        else sl_flush(S, o, gd0, ng, sb);
+        else sl_flush<PACK>(S, o, gd0, ng, sb);
         if ((uint32_t)tid < ng) {
             const uint32_t n = S.dsz[tid];
             if (n) {
@@ -1159,13 +1203,16 @@ __global__ __launch_bounds__(NT, WG_PER_CU * NT / 256) void k_tokcount_sl(Corpus
 
 int launch_tokcount_sl(const CorpusDev& c, const uint64_t* chunk_start, const uint32_t* chunk_doc, uint64_t c0,
                        uint64_t c1, const VocabDev& v, const K1Out* o_dev, hipStream_t s, uint32_t ncu_ctx,
-                       uint32_t* grid_out) {
+                       uint32_t* grid_out, uint32_t pack) {
     if (grid_out) *grid_out = 0;
     if (c1 <= c0) return 0;
     if (v.mask >= (1ull << SLOT_BITS)) return -3;
     static_assert(sizeof(SlShared) * WG_PER_CU <= 163840, "LDS of WG_PER_CU workgroups per CU");
     static_assert(TB % NT == 0 && TB % BW == 0, "table rows");
     const uint32_t sbits = (uint32_t)__builtin_popcountll(v.mask);
+    /* a packed record's count field has at least 10 bits: tables up to K1_ST_MAX_CAP slots, the
+     * FAST instance's */
+    if (pack && v.mask + 1 > K1_ST_MAX_CAP) return -1;
     const uint32_t gcap = (1u << (31u - sbits)) >= (uint32_t)GCAP ? (uint32_t)GCAP : (1u << (31u - sbits));
     static int ncu = 0;   /* the device's, for a caller that passes no count */
     if (!ncu_ctx && !ncu) {
@@ -1183,8 +1230,10 @@ int launch_tokcount_sl(const CorpusDev& c, const uint64_t* chunk_start, const ui
      * 6.8 M -> 8.9 M, merge 3.0 -> 3.2 ms, 76.8 -> 75.8 GB/s, profiles/k1_fastcount_ab.txt), so
      * such tables keep the full count in every round */
     if (v.mask + 1 > K1_ST_MAX_CAP)
-        k_tokcount_sl<false><<<(unsigned)grid, NT, 0, s>>>(c, chunk_start, chunk_doc, c0, c1, v, o_dev, sbits, gcap);
+        k_tokcount_sl<false, false><<<(unsigned)grid, NT, 0, s>>>(c, chunk_start, chunk_doc, c0, c1, v, o_dev, sbits, gcap);
+    else if (pack)
+        k_tokcount_sl<true, true><<<(unsigned)grid, NT, 0, s>>>(c, chunk_start, chunk_doc, c0, c1, v, o_dev, sbits, gcap);
     else
-        k_tokcount_sl<true><<<(unsigned)grid, NT, 0, s>>>(c, chunk_start, chunk_doc, c0, c1, v, o_dev, sbits, gcap);
+        k_tokcount_sl<true, false><<<(unsigned)grid, NT, 0, s>>>(c, chunk_start, chunk_doc, c0, c1, v, o_dev, sbits, gcap);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
