@@ -200,7 +200,8 @@ def test_group_boundary_and_small_budget(engine, monkeypatch):
 
 def test_more_documents_than_a_top_k_slice(engine):
     """5000 documents: the dense accumulators are cut into two slices of 4096 and a second
-    top-k round merges their lists; most neighbours tie (few distinct vectors)"""
+    top-k round merges their lists; most neighbours tie (few distinct vectors).  The rounds beyond
+    (a second round with several slices, a third launch): test_gpu_topk_rounds.py"""
     rng = np.random.default_rng(6)
     docs = [b" ".join(b"w%02d" % int(j) for j in rng.integers(0, 60, 3)) for _ in range(5000)]
     data, off = docs_to_arrays(docs)
